@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the PIT mask-estimation training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dry]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dry] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 launches itself as N ranks (``python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1``, one rank per GPU over RCCL); when it is already running under
@@ -54,6 +54,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP32_MFMA_PEAK_TFLOPS = 157.3  # v_mfma_f32_16x16x4_f32 dense peak (MI355X_MICROARCH.md)
 FP16_MFMA_PEAK_TFLOPS = 2500.  # v_mfma_f32_32x32x16_f16 dense peak (MI355X_MICROARCH.md)
 LOSS_WEIGHTS = dict(pit_ips_loss=1., pit_mse_loss=0.)      # pit/train.py:68-71
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_PARAM_ELEMENTS = 12 << 20  # of which the parameters (float32): a seeded sample of every tensor beyond this in all
 
 CONFIGS = {
     'c2': dict(model='pit', batch=32, fs=8000, K=2, micro=1,
@@ -110,6 +112,10 @@ def parse_args(argv=None):
     ap.add_argument('--row-slots', action='store_true',
                     help='with --ragged: 2 x batch examples end to end in `batch` row slots (model.row_slots), the timed step itself '
                          '(the default line reports the same as value_ragged_row_slots)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the LAST timed step computed as DIR/<name>.npy (float32 / float64, '
+                         f'<= {DUMP_BYTES >> 20} MB in all): its losses, its gradient norm and the parameters it left behind (a fixed, '
+                         'seeded sample of them where they exceed the budget) - two builds compared output for output')
     return ap.parse_args(argv)
 
 
@@ -136,6 +142,41 @@ def synthetic_batch(seed, batch, K, n, device, lengths=None):
         for b, nb in enumerate(lengths):
             s[b, :, nb:] = 0.
     return dict(y=s.sum(1).to(device), s=s.to(device), num_samples=list(lengths) if lengths is not None else [n] * batch)
+
+
+def last_step_outputs(model, losses=None, grad_norm=None):
+    """What the last timed step leaves a caller (--dump-outputs): {name: float array}.  The parameters come whole while they fit
+    DUMP_PARAM_ELEMENTS; beyond that every tensor gives the same share of its elements at indices drawn from a fixed seed (the
+    shapes are fixed by the configuration, so two runs pick the same entries)."""
+    import numpy as np
+    import torch
+    out = {}
+    if losses is not None:
+        out['loss'] = np.asarray(losses, dtype=np.float64).reshape(-1)
+    if grad_norm is not None:
+        out['grad_norm'] = np.asarray([grad_norm], dtype=np.float64)
+    sd = model.state_dict()
+    total = sum(v.numel() for v in sd.values())
+    share = min(1., DUMP_PARAM_ELEMENTS / max(1, total))
+    rng = np.random.default_rng(20240917)
+    for name, v in sd.items():
+        flat = v.detach().reshape(-1).to('cpu', torch.float32).numpy()
+        if share < 1.:
+            k = max(1, int(flat.size * share))
+            flat = flat[np.sort(rng.choice(flat.size, k, replace=False))]
+        out[f'param.{name}'] = flat
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_BYTES - 128 * len(arrays), f'--dump-outputs: {nbytes} bytes exceed the budget'
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(d / f'{name}.npy', a)
 
 
 def cpu_baseline_variant(threads, max_seconds=12., b=4):
@@ -550,6 +591,24 @@ def main():
     from padertorch_amd import _lib
     # what step() runs on: the headline's batch, or (value_ragged) a batch of SURVEY 8d's length distribution
     variant = dict(ragged=bool(args.ragged), frames=frames_per_micro, data=None)
+    last_step = {}                # --dump-outputs: the losses and optimizer summary of the last timed eager step
+    dumped = {}
+
+    def snapshot(graphed=None):
+        """--dump-outputs: what the last timed step computed, taken right behind the timed region (before anything runs another
+        step).  A replayed step hands its caller the staged scalars (GraphedStep.scalars) and the parameters it rewrote."""
+        if not args.dump_outputs or rank != 0:
+            return
+        losses = grad_norm = None
+        if graphed is not None:
+            losses = [float(host[-1]) for what, host, _, _ in graphed._stage.jobs if what == 'loss']
+            grad_norm = graphed.scalars().get('grad_norm')
+        elif last_step:
+            losses = [float(v) for v in last_step['losses']]
+            gn = last_step['summary']['scalars'].get('grad_norm')
+            grad_norm = None if gn is None else float(gn)
+        dumped.clear()
+        dumped.update(last_step_outputs(model, losses, grad_norm))
 
     if args.dry:
         data = None
@@ -603,6 +662,7 @@ def main():
             if timed:
                 counted[1] += counted[0] % TIMER_EVERY == 0
                 counted[0] += 1
+            losses = [] if timed and args.dump_outputs else None       # (--dump-outputs: what this step hands its caller)
             buckets = trainer._buckets
             for m in range(micro):
                 if buckets is not None:
@@ -620,8 +680,12 @@ def main():
                 feats = features(src)
                 assert sum(feats['num_frames']) == variant['frames'], (sum(feats['num_frames']), variant['frames'])
                 loss, _, _, _ = trainer.train_step(model, feats, device)
+                if losses is not None:
+                    losses.append(loss.detach())
                 trainer.backward(loss)
-            trainer.optimizer_step()
+            summary = trainer.optimizer_step()
+            if losses is not None:
+                last_step.update(losses=losses, summary=summary)
 
     def sync():
         if world > 1:
@@ -770,6 +834,7 @@ def main():
                 graphed()
             graphed.times = []                 # GPU time of graph A / the exchange / graph B per step, HIP events on the step's stream
             elapsed_graph = graph_loop(args.steps)
+            snapshot(graphed)
             graphed.times, graph_state['times'] = None, graphed.times
             # per-kernel HIP events: an eager pass of the same step (same protocol) behind the timed region, as for N = 1
             ev_steps = max(TIMER_EVERY, min(args.steps, 10 * TIMER_EVERY))
@@ -780,7 +845,9 @@ def main():
         for _ in range(args.warmup):
             step(False)
         if not use_graph:
-            return timed_loop(args.steps, timed=True)
+            elapsed_eager = timed_loop(args.steps, timed=True)
+            snapshot()
+            return elapsed_eager
         # N = 1: the optimizer step as ONE captured hipGraph, checks at the end of the same step (reference semantics)
         from padertorch_amd.train.graphed import GraphedStep
         trainer._check_pending(flush=True)
@@ -807,6 +874,7 @@ def main():
             graphed()
         sync()
         elapsed_graph = time.perf_counter() - t0
+        snapshot(graphed)
         if args.dp_graph:
             graphed.times, graph_state['times'] = None, graphed.times
         # per-kernel HIP events cannot be recorded inside a replay: the same launches are bracketed in an eager pass of the same step
@@ -840,6 +908,8 @@ def main():
     buckets = trainer._buckets
     _lib.KERNEL_TIMERS = None
     frames_per_step = frames_per_micro * micro
+    if dumped:
+        write_outputs(args.dump_outputs, dumped)
 
     extras = {}
     t_trace = time.perf_counter()
@@ -1174,6 +1244,8 @@ def main():
                 'lstm_weight_gradients': 'autograd, main stream' if args.no_overlap else 'in place, side stream next to the next recurrence',
             },
         }
+        if dumped:
+            out['dump_outputs'] = dict(dir=str(args.dump_outputs), arrays=len(dumped), bytes=sum(a.nbytes for a in dumped.values()))
         if args.dry:
             out['dry'] = True
             out['roofline'] = None

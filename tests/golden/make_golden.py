@@ -28,6 +28,8 @@ Fixtures:
                           key, gradients of all parameters; with and without the VAD head / the normalisation
   g10_summary_data.npz    summary/tbx_utils.py mask_to_image / stft_to_image / spectrogram_to_image over batch_first x colour x
                           origin; data/batch.py Sorter and data/utils.py collate_fn results
+  g12_trainer_calls.json  every call the reference Trainer makes on OUR PIT model class over 3 iterations (order, arguments,
+                          review losses) and the checkpoint files it writes: replayed by test_reference_trainer_dropin.py
   g8_logmel.npz           contrib/je/modules/features.py MelTransform (forward / inverse / maxima) and
                           the extractor front-end (stacked pt.ops.STFT -> power -> MelTransform); the
                           filterbank comes from the shim's restatement of paderbox.get_fbanks (parity
@@ -637,10 +639,79 @@ def g11():
     np.savez_compressed(HERE / 'g11_mask_estimator.npz', **out)
 
 
+def g12():
+    """The reference Trainer driving OUR PIT model class (3 iterations, virtual_minibatch_size=2, a summary every iteration): every
+    call it makes on the model, in order, with the losses of each review.  tests/test_reference_trainer_dropin.py replays the record
+    on the model without the reference.  The one HIP-only op of the review is replaced by the oracle's loop (as in that test)."""
+    sys.path.insert(0, str(HERE.parent))
+    import test_reference_trainer_dropin as dropin
+    import padertorch_amd as pta
+    from padertorch_amd.ops import losses as pta_losses
+    from padertorch_amd.contrib.examples.source_separation.pit.model import PermutationInvariantTrainingModel as Ours
+
+    log = []
+
+    class Recording(Ours):
+        def example_to_device(self, example, device=None, memo=None):
+            log.append(['example_to_device', str(device)])
+            return super().example_to_device(example, device, memo)
+
+        def forward(self, batch):
+            log.append(['forward'])
+            return super().forward(batch)
+
+        def review(self, batch, model_out):
+            review = super().review(batch, model_out)
+            log.append(['review', {k: float(v) for k, v in review['losses'].items()}])
+            return review
+
+        def modify_summary(self, summary):
+            log.append(['modify_summary', sorted(summary.get('scalars', {}))])
+            return super().modify_summary(summary)
+
+        def train(self, mode=True):
+            log.append(['train', bool(mode)])
+            return super().train(mode)
+
+        def state_dict(self, *args, **kwargs):
+            log.append(['state_dict'])
+            return super().state_dict(*args, **kwargs)
+
+        def __setattr__(self, name, value):
+            if name == 'create_snapshot':
+                log.append(['create_snapshot', bool(value)])
+            super().__setattr__(name, value)
+
+    g6d = dict(np.load(HERE / 'g6_models.npz', allow_pickle=False))
+    keep = pta_losses.pit_mse_ips_losses
+    pta_losses.pit_mse_ips_losses = pta.ops.losses.pit_mse_ips_losses = dropin._oracle_pit_losses
+    try:
+        model = Recording(F=9, recurrent_layers=2, units=4, K=2)
+        model.load_state_dict({k[len('pit_sd_'):]: torch.from_numpy(v) for k, v in g6d.items() if k.startswith('pit_sd_')})
+        Ts = [int(t) for t in g6d['Ts']]
+        batch = {k: [g6d[f'in_{k}_{i}'] for i in range(len(Ts))] for k in ['Y_abs', 'X_abs', 'cos_phase_difference']}
+        batch['num_frames'] = Ts
+        examples = [{k: [v[b] for b in idx] for k, v in batch.items()} for idx in json.loads(str(g6d['train_example_indices']))]
+        log.clear()
+        with tempfile.TemporaryDirectory() as tmp:
+            trainer = pt.Trainer(model, tmp, pt.optimizer.Adam(gradient_clipping=1.),
+                                 loss_weights=dict(pit_ips_loss=1., pit_mse_loss=0.), summary_trigger=(1, 'iteration'),
+                                 checkpoint_trigger=(1000, 'iteration'), stop_trigger=(3, 'iteration'), virtual_minibatch_size=2)
+            trainer.train(examples, device='cpu')
+            assert trainer.iteration == 3, trainer.iteration
+            checkpoints = sorted(p.name for p in (Path(tmp) / 'checkpoints').iterdir())
+        calls = list(log)
+        for k, v in model.state_dict().items():          # the reference loop over OUR model lands on ITS OWN model's parameters
+            np.testing.assert_allclose(v.numpy(), g6d['pit_sd3_' + k], atol=1e-6, err_msg=k)
+    finally:
+        pta_losses.pit_mse_ips_losses = pta.ops.losses.pit_mse_ips_losses = keep
+    (HERE / 'g12_trainer_calls.json').write_text(json.dumps(dict(calls=calls, checkpoints=checkpoints), indent=0) + '\n')
+
+
 if __name__ == '__main__':
     assert os.path.isdir('/root/reference'), 'run in the build container'
     only = sys.argv[1:]
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12):
         if only and fn.__name__ not in only:
             continue
         fn()

@@ -59,3 +59,23 @@ def test_c4_micro_steps_single_allreduce_per_optimizer_step():
 def test_single_process_dry():
     out = _run()
     assert out['n_gpus'] == 1 and 'rccl' not in out
+
+
+def test_dump_outputs_are_float_arrays_within_budget_and_repeat(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's arrays as DIR/<name>.npy, float32 / float64, 64 MB at most in all (the 23.5 M
+    parameters of the PIT model are a seeded sample), the same from run to run; ``steps`` and ``ms_per_step`` as without it."""
+    import numpy as np
+    runs = []
+    for name in ('a', 'b'):
+        out = _run('--steps', '3', '--dump-outputs', str(tmp_path / name))
+        assert out['steps'] == 3 and out['ms_per_step'] > 0
+        files = sorted((tmp_path / name).glob('*.npy'))
+        assert len(files) == out['dump_outputs']['arrays'] > 0
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.name: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert 'param.linear2.weight.npy' in arrays
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys()
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)

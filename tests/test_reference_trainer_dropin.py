@@ -5,14 +5,13 @@ Part 1 (always): the surface the reference Trainer and its hooks touch on a mode
 ``example_to_device(example, device)``, ``__call__(example)``, ``review(example, out)``, ``modify_summary`` and a
 settable ``create_snapshot`` flag; the reference's ``state_dict`` keys.
 
-Part 2 (build container only, skipped where /root/reference does not exist): the real reference Trainer - imported
-with the stand-ins of tests/golden/ref_shim for its absent third-party dependencies - trains OUR model class for
-three iterations on the CPU.  The product has no CPU path, so the one HIP-only op of the review
-(``ops.losses.pit_mse_ips_losses``) is replaced by the oracle's loop for the duration of the test; everything else
-(model class, forward, review, PaddedList outputs, example_to_device, summaries, checkpoints) is the shipped code
-driven by the reference's loop."""
-import os
-import sys
+Part 2: the real reference Trainer trained OUR model class for three iterations on the CPU; golden g12 records every call
+it made on the model (``tests/golden/make_golden.py``, where the reference is imported with the stand-ins of
+tests/golden/ref_shim), and the test replays that record on the model.  The product has no CPU path, so the one HIP-only
+op of the review (``ops.losses.pit_mse_ips_losses``) is replaced by the oracle's loop, in the record and in the replay;
+everything else (model class, forward, review, PaddedList outputs, example_to_device, summaries, checkpoints) is the
+shipped code answering the reference loop's calls."""
+import json
 from pathlib import Path
 
 import numpy as np
@@ -71,17 +70,17 @@ def _oracle_pit_losses(mask, observation, target, cos_phase_difference=None, len
     return torch.stack([torch.stack(mse).mean(), torch.stack(ips).mean()]), None, None
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='needs the reference tree (build container)')
 def test_reference_trainer_trains_our_model(g6, tmp_path, monkeypatch):
-    monkeypatch.syspath_prepend('/root/reference')                          # stays for the lazy imports of the loop
-    monkeypatch.syspath_prepend(str(REPO / 'tests' / 'golden' / 'ref_shim'))
-    try:
-        import padertorch as pt                      # the REFERENCE
-    except Exception as e:                           # pragma: no cover
-        pytest.skip(f'reference not importable: {e!r}')
+    """Every call the reference Trainer made on this model class while training it (golden g12: recorded by
+    ``tests/golden/make_golden.py`` with the real reference loop, 3 iterations, virtual_minibatch_size=2, a summary every
+    iteration), replayed in the recorded order: each call has to be answered as it was, and the loop's arithmetic between the calls
+    (weighted loss, accumulated backward, global-norm clip, Adam: ``trainer.py:357-393,512-532,608-620``) lands on the parameters the
+    reference loop over ITS OWN model produced."""
+    from oracle import torch_ref
     from padertorch_amd.ops import losses
     monkeypatch.setattr(losses, 'pit_mse_ips_losses', _oracle_pit_losses)
     monkeypatch.setattr(pta.ops.losses, 'pit_mse_ips_losses', _oracle_pit_losses, raising=False)
+    record = json.loads((REPO / 'tests' / 'golden' / 'g12_trainer_calls.json').read_text())
 
     model = PermutationInvariantTrainingModel(F=9, recurrent_layers=2, units=4, K=2)
     model.load_state_dict({k[len('pit_sd_'):]: torch.from_numpy(v) for k, v in g6.items()
@@ -89,14 +88,47 @@ def test_reference_trainer_trains_our_model(g6, tmp_path, monkeypatch):
     Ts = [int(t) for t in g6['Ts']]
     batch = {k: [g6[f'in_{k}_{i}'] for i in range(len(Ts))] for k in ['Y_abs', 'X_abs', 'cos_phase_difference']}
     batch['num_frames'] = Ts
-    examples = [{k: [v[b] for b in idx] for k, v in batch.items()} for idx in g6['train_example_indices']]
+    examples = iter([{k: [v[b] for b in idx] for k, v in batch.items()} for idx in g6['train_example_indices']])
 
-    trainer = pt.Trainer(model, str(tmp_path), pt.optimizer.Adam(gradient_clipping=1.),
-                         loss_weights=dict(pit_ips_loss=1., pit_mse_loss=0.), summary_trigger=(1, 'iteration'),
-                         checkpoint_trigger=(1000, 'iteration'), stop_trigger=(3, 'iteration'), virtual_minibatch_size=2)
-    trainer.train(examples, device='cpu')
-    assert trainer.iteration == 3
-    # the reference loop over OUR model lands on the parameters the reference loop over ITS OWN model produced
+    lw = dict(pit_ips_loss=1., pit_mse_loss=0.)
+    opt = torch.optim.Adam(model.parameters())                              # optimizer.py:71-90 defaults
+    (tmp_path / 'checkpoints').mkdir()
+    micro = steps = saved = 0
+    example = out = None
+    for call, *args in record['calls']:
+        if call == 'train':
+            model.train(args[0])
+        elif call == 'create_snapshot':
+            model.create_snapshot = args[0]
+        elif call == 'example_to_device':
+            example = model.example_to_device(next(examples), args[0])
+        elif call == 'forward':
+            out = model(example)
+        elif call == 'review':
+            review = model.review(example, out)
+            assert set(review['losses']) == set(args[0])
+            for k, v in args[0].items():
+                np.testing.assert_allclose(float(review['losses'][k].detach()), v, atol=1e-6, err_msg=k)
+            torch_ref.review_to_loss(review, lw).backward()                 # accumulate, not average
+            micro += 1
+            if micro == 2:                                                  # virtual_minibatch_size=2
+                torch.nn.utils.clip_grad_norm_(list(model.parameters()), 1.)
+                opt.step()
+                opt.zero_grad()
+                micro, steps = 0, steps + 1
+        elif call == 'modify_summary':
+            summary = dict(scalars={k: [1., 3.] for k in args[0]}, histograms={}, images={})
+            assert set(model.modify_summary(summary)['scalars']) == set(args[0])
+        elif call == 'state_dict':
+            name = record['checkpoints'][saved]
+            torch.save(model.state_dict(), tmp_path / 'checkpoints' / name)
+            saved += 1
+        else:
+            raise AssertionError(f'unknown call in the record: {call}')
+    assert steps == 3 and micro == 0 and next(examples, None) is None
     for k, v in model.state_dict().items():
         np.testing.assert_allclose(v.numpy(), g6['pit_sd3_' + k], atol=1e-6, err_msg=k)
-    assert (tmp_path / 'checkpoints' / 'ckpt_latest.pth').exists()
+    # the last checkpoint the reference wrote (ckpt_latest links to it) holds those parameters
+    last = torch.load(tmp_path / 'checkpoints' / record['checkpoints'][saved - 1])
+    for k, v in last.items():
+        np.testing.assert_allclose(v.numpy(), g6['pit_sd3_' + k], atol=1e-6, err_msg=k)
