@@ -61,14 +61,18 @@ class StaticSlotBatcher:
     ``steps``: the grid's capacity in time steps, or a LIST of capacities (buckets: a batch takes the smallest grid it fits; default: enough for every batch whose frames sum to ``headroom`` x the mean of a
     U[max / 2, max] length distribution, rounded up to 8).  A batch that does not fit - more examples, a longer example, more frames than
     the grid has room for - comes back as it is (the model then takes its host-side route: ``model.row_slots`` / PackedSequence, eagerly);
-    ``refused`` counts them.  Two layouts are used in turn: the tables of batch i + 1 may be written while batch i's step still reads its
-    own.  The padded tensors are made on ``device`` from the host tensors of the batch (pinned memory makes the copies asynchronous).
+    ``refused`` counts them.  The padded tensors are made on ``device`` from the host tensors of the batch (pinned memory makes the copies
+    asynchronous).
+
+    Lifetime: every returned example OWNS its ``StaticSlots`` - a new object per batch, never rewritten by a later call - so its tables
+    describe that batch for as long as the caller holds it (a materialised list, ``Trainer(virtual_minibatch_size > 2)``, any prefetch
+    depth), and the tables of batch i + 1 can be written while batch i's step still reads its own.  The objects of one bucket share one
+    signature (shapes only), so one captured graph serves all of them (``GraphedStep(clone_inputs=True)`` copies each into its own).
     """
 
     def __init__(self, examples, slots, max_samples, device, stft=None, steps=None, headroom=1.08):
         import torch
         from ..ops import STFT
-        from ..ops.sequence import StaticSlots
         self.stft = stft if stft is not None else STFT(512, 128)
         self.examples, self.slots, self.max_samples = int(examples), int(slots), int(max_samples)
         self.device = torch.device(device)
@@ -80,8 +84,6 @@ class StaticSlotBatcher:
         # every bucket is one example signature, i.e. one captured graph (set ``trainer.graph_capacity`` to the number of buckets: two are kept by default)
         self.buckets = sorted({int(v) for v in (steps if isinstance(steps, (list, tuple)) else [steps])})
         self.steps = self.buckets[-1]
-        self._rings = {cap: [StaticSlots(self.examples, self.slots, cap, self.padded_time, self.device) for _ in range(2)] for cap in self.buckets}
-        self._turn = {cap: 0 for cap in self.buckets}
         self.refused = 0
         self.taken = {cap: 0 for cap in self.buckets}
 
@@ -91,7 +93,7 @@ class StaticSlotBatcher:
     def __call__(self, batch):
         import numpy as np
         import torch
-        from ..ops.sequence import SlotLayout
+        from ..ops.sequence import SlotLayout, StaticSlots
         num_samples = [int(n) for n in batch['num_samples']]
         frames = self.frames_of(num_samples)
         ok = len(frames) == self.examples and max(num_samples) <= self.max_samples and min(frames) >= 1 and sum(frames) <= self.steps * self.slots
@@ -118,6 +120,6 @@ class StaticSlotBatcher:
             K = int(np.asarray(batch['s'][0]).shape[0]) if not torch.is_tensor(batch['s'][0]) else int(batch['s'][0].shape[0])
             out['s'] = padded(batch['s'], (K,))
         out['num_samples'] = torch.tensor(num_samples, dtype=torch.int32).to(self.device)
-        self._turn[cap] ^= 1
-        out['slots'] = self._rings[cap][self._turn[cap]].set(frames)
+        # (a layout of its own: a shared one would be rewritten under a batch the caller still holds)
+        out['slots'] = StaticSlots(B, self.slots, cap, self.padded_time, self.device).set(frames)
         return out

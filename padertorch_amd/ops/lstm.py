@@ -609,6 +609,11 @@ class _LstmLayerFn(torch.autograd.Function):
         lib = _lib.load()
         st = _lib.stream(dhy.device)
         x, w_ih, w_hh, gates, c, hy, h0, c0 = ctx.saved_tensors
+        # the backward scratch the forward recurrence has prefilled (pattern, zeroed bias sums / arrival words / error words) serves ONE
+        # backward pass: this one leaves its hand-off planes and bias sums in it.  A second pass through the same graph
+        # (retain_graph=True, torch.autograd.grad twice) takes a scratch of its own that its launch fills and zeroes (prefilled = 0)
+        scratch_b, pre_b = ctx.scratch_b
+        ctx.scratch_b = (None, 0)
         ndir, G, H = w_hh.shape
         state_grad = False
         carry = None
@@ -746,9 +751,9 @@ class _LstmLayerFn(torch.autograd.Function):
                       and not state_grad and not dx_needs_rows
                       and lib.ptmi_lstm_backward_planes_ok(T, ndir, meta.max_batch, meta.rows, H))
         if use_tp:
-            flags = ctx.scratch_b[0] if ctx.scratch_b[0] is not None else torch.empty(
+            flags = scratch_b if scratch_b is not None else torch.empty(
                 int(lib.ptmi_lstm_scratch_elems(T, ndir, meta.max_batch, H, 1)), dtype=torch.int32, device=dhy.device)
-            pre = int(ctx.scratch_b[1]) if flags is ctx.scratch_b[0] else 0
+            pre = int(pre_b) if flags is scratch_b else 0
             cuts = [T * i // chunks for i in range(chunks + 1)]
             carry = torch.empty((ndir, meta.max_batch, H), dtype=torch.float32, device=dhy.device) if chunks > 1 else None
             B_ = meta.max_batch
@@ -783,7 +788,7 @@ class _LstmLayerFn(torch.autograd.Function):
             dg_t = None
         if not use_tp and (chunks > 1 or state_grad):
             dg = torch.empty_like(gates)
-            flags = ctx.scratch_b[0] if ctx.scratch_b[0] is not None else torch.empty(
+            flags = scratch_b if scratch_b is not None else torch.empty(
                 int(lib.ptmi_lstm_scratch_elems(T, ndir, meta.max_batch, H, 1)), dtype=torch.int32, device=dhy.device)
             carry = torch.empty((ndir, meta.max_batch, H), dtype=torch.float32, device=dhy.device)
             cuts = [T * i // chunks for i in range(chunks + 1)]
@@ -794,7 +799,7 @@ class _LstmLayerFn(torch.autograd.Function):
             def launch(i):
                 return torch.ops.ptmi.lstm_recurrence_backward_range(
                     gates, c, c0, dhy, w_t, dg, flags, carry, meta.bs_dev, meta.offs_dev, T, meta.max_batch, meta.rows, H,
-                    ndir, cuts[i], cuts[i + 1], int(ctx.scratch_b[1]) if flags is ctx.scratch_b[0] else 0, dcn)
+                    ndir, cuts[i], cuts[i + 1], int(pre_b) if flags is scratch_b else 0, dcn)
             if launch(0):
                 for i in range(1, chunks):
                     snap = amax_word.clone()                     # max |dgates| so far: the operand scale of this part
@@ -818,7 +823,7 @@ class _LstmLayerFn(torch.autograd.Function):
         if dg is None and not use_tp:
             dg, flags = torch.ops.ptmi.lstm_recurrence_backward(
                 gates, c, c0, dhy, w_t, meta.bs_dev, meta.offs_dev, meta.bs_host.ctypes.data, meta.offs_host.ctypes.data,
-                T, meta.max_batch, meta.rows, H, ndir, PERSISTENT, ctx.scratch_b[0], int(ctx.scratch_b[1]), masks)
+                T, meta.max_batch, meta.rows, H, ndir, PERSISTENT, scratch_b, int(pre_b), masks)
         if flags is not None:
             if CHECK_PERSISTENT_ERRORS:
                 check_errors()

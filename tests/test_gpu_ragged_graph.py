@@ -189,21 +189,43 @@ def test_dc_model_on_static_slots_equals_row_slots_and_shares_one_graph(tmp_path
 def test_trainer_trains_a_ragged_stream_on_one_graph(tmp_path):
     """The user's path end to end: a stream of variable-length utterances (``pit/data.py:20-33``) -> ``data.row_slot_batches`` ->
     ``data.StaticSlotBatcher`` -> ``Trainer.train(graph_steps=True)``.  ``example_to_device`` makes the features from the device-side
-    lengths, the first batch runs eagerly, the second captures, all later ones replay through that ONE graph although every batch has
-    its own length pattern; a batch that does not fit the grid runs eagerly in between.  Parameters equal those of the eager loop."""
+    lengths, the first step runs eagerly, the second captures, all later ones replay through that ONE graph although every batch has
+    its own length pattern; a batch that does not fit the grid runs eagerly in between.  Parameters equal those of the eager loop.
+    The batches are all materialised before the first step (and ``micro`` = ``virtual_minibatch_size`` > 2 holds three at once): every
+    batch keeps its OWN tables, and the eager loop's first two steps equal those of the host-side lengths route (``model.row_slots``:
+    the batches as ``row_slot_batches`` made them), which no shared device table reaches."""
+    _ragged_stream(tmp_path, micro=1)
+
+
+def test_trainer_trains_a_ragged_stream_three_batches_per_step(tmp_path):
+    """The same with ``virtual_minibatch_size=3``: the Trainer holds three batches of the batcher at once (``list(islice(...))``)."""
+    _ragged_stream(tmp_path, micro=3)
+
+
+def _ragged_stream(tmp_path, micro):
     import padertorch_amd as pt
     from padertorch_amd.data import StaticSlotBatcher, row_slot_batches
     from padertorch_amd.train import graphed as G
     rng = np.random.RandomState(4)
-    lens = [int(v) for v in rng.randint(3200, 6401, 8 * 7)]
-    lens[8 * 3:8 * 4] = [6400] * 8                                  # the fourth batch is too long for the grid: handed back, eager
+    n_batches = 7 if micro == 1 else 12
+    lens = [int(v) for v in rng.randint(3200, 6401 if micro == 1 else 5201, 8 * n_batches)]     # (micro = 3: every batch fits)
+    refused = 3 if micro == 1 else None
+    if refused is not None:
+        lens[8 * refused:8 * (refused + 1)] = [6400] * 8          # the fourth batch is too long for the grid: handed back, eager
     stream = [dict(y=(0.1 * rng.randn(n)).astype(np.float32), s=(0.1 * rng.randn(2, n)).astype(np.float32), num_samples=n, example_id=f'u{i}')
               for i, n in enumerate(lens)]
+    iterations = n_batches // micro
 
-    def run(graph, path):
-        batcher = StaticSlotBatcher(examples=8, slots=4, max_samples=6400, device=DEV, steps=96)
-        data = [batcher(b) for b in row_slot_batches(stream, row_slots=4, fill=2.0)]
-        assert batcher.refused == 1 and 'slots' not in data[3]
+    def run(graph, path, slots=True):
+        if slots:
+            batcher = StaticSlotBatcher(examples=8, slots=4, max_samples=6400, device=DEV, steps=96)
+            data = [batcher(b) for b in row_slot_batches(stream, row_slots=4, fill=2.0)]
+            assert batcher.refused == (refused is not None) and (refused is None or 'slots' not in data[refused])
+            for i, d in enumerate(data):
+                if i != refused:
+                    assert d['slots'].frames.tolist() == batcher.frames_of(d['num_samples'].tolist()), i
+        else:
+            data = list(row_slot_batches(stream, row_slots=4, fill=2.0))
         model = _pit(48)
         model.row_slots = 4                                          # (the route of a batch that was handed back)
         made = []
@@ -211,16 +233,21 @@ def test_trainer_trains_a_ragged_stream_on_one_graph(tmp_path):
         G.GraphedStep.__init__ = lambda self, *a, **k: (made.append(1), plain(self, *a, **k))[1]
         try:
             t = pt.Trainer(model, path, pt.optimizer.Adam(gradient_clipping=1.), loss_weights=LW, summary_trigger=(1, 'iteration'),
-                           checkpoint_trigger=(1000, 'iteration'), stop_trigger=(7, 'iteration'), graph_steps=graph)
+                           checkpoint_trigger=(1000, 'iteration'), stop_trigger=(iterations, 'iteration'), graph_steps=graph,
+                           virtual_minibatch_size=micro)
             t.train(data, device=DEV)
         finally:
             G.GraphedStep.__init__ = plain
         return model, t, len(made)
     ma, ta, _ = run(False, tmp_path / 'a')
     mb, tb, captures = run(True, tmp_path / 'b')
-    assert ta.iteration == tb.iteration == 7 and captures == 1, captures
+    mc, tc, _ = run(False, tmp_path / 'c', slots=False)
+    assert ta.iteration == tb.iteration == tc.iteration == iterations and captures == 1, captures
     for (k, v), (_, w) in zip(ma.state_dict().items(), mb.state_dict().items()):
         np.testing.assert_allclose(w.cpu().numpy(), v.cpu().numpy(), rtol=0, atol=1e-6, err_msg=k)
     la = [s[2]['loss'] for s in ta.summaries if s[1] == 'training']
     lb = [s[2]['loss'] for s in tb.summaries if s[1] == 'training']
+    lc = [s[2]['loss'] for s in tc.summaries if s[1] == 'training']
+    assert len(la) == len(lb) == len(lc) >= 2
     np.testing.assert_allclose(lb, la, rtol=1e-5)
+    np.testing.assert_allclose(la[:2], lc[:2], rtol=1e-5)

@@ -181,3 +181,37 @@ def test_static_slot_batcher_makes_device_data_examples_or_hands_the_batch_back(
     assert outs[0]['slots'] is not outs[1]['slots']          # two layouts in turn
     tight = StaticSlotBatcher(examples=8, slots=4, max_samples=4800, device='cpu', steps=41)
     assert not isinstance(tight(next(row_slot_batches(stream, row_slots=4, fill=2.0))).get('slots'), StaticSlots) and tight.refused == 1
+
+
+def _tables_of(st):
+    return dict(zip(('frames', 'src_of_grid', 'grid_of_flat', 'prev', 'masks'), st.static_tensors()))
+
+
+@pytest.mark.parametrize('buckets', [[80], [48, 80]])
+def test_static_slot_batcher_batches_keep_their_own_tables(buckets):
+    """Every example ``data.StaticSlotBatcher`` returns keeps the tables of ITS batch for as long as the caller holds it: a list of
+    materialised batches (what ``Trainer(virtual_minibatch_size > 2)`` and a deep prefetch hold) - one bucket, and two buckets
+    interleaved -, each checked table by table against a fresh ``StaticSlots`` set to the batch's own frame counts, and no two live
+    examples share a tensor.  (A ring of two layouts per bucket handed batch i the tables of batch i + 2.)"""
+    from padertorch_amd.data import StaticSlotBatcher, row_slot_batches
+    from padertorch_amd.ops.sequence import StaticSlots
+    rng = np.random.RandomState(7)
+    lens = [int(v) for v in rng.randint(2400, 4001, 8 * 7)]
+    if len(buckets) > 1:           # every other batch short enough for the small grid
+        for i in range(0, 7, 2):
+            lens[8 * i:8 * (i + 1)] = [int(v) for v in rng.randint(1000, 2001, 8)]
+    stream = [dict(y=rng.randn(n).astype(np.float32), s=rng.randn(2, n).astype(np.float32), num_samples=n) for n in lens]
+    batcher = StaticSlotBatcher(examples=8, slots=4, max_samples=4800, device='cpu', steps=buckets)
+    data = [batcher(b) for b in row_slot_batches(stream, row_slots=4, fill=2.0)]
+    assert batcher.refused == 0 and len(data) == 7
+    if len(buckets) > 1:
+        assert [d['slots'].steps for d in data] == [buckets[i % 2] for i in range(7)], [d['slots'].steps for d in data]
+    assert len({tuple(d['num_samples'].tolist()) for d in data}) == 7
+    for i, d in enumerate(data):
+        st = d['slots']
+        want = StaticSlots(8, 4, st.steps, batcher.padded_time, 'cpu').set(batcher.frames_of(d['num_samples'].tolist()))
+        for name, t in _tables_of(want).items():
+            assert torch.equal(_tables_of(st)[name], t), (i, name)
+    ptrs = [t.data_ptr() for d in data for t in d['slots'].static_tensors()]
+    assert len(set(ptrs)) == len(ptrs)
+    assert len({id(d['slots']) for d in data}) == len(data)
