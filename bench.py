@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the PIT mask-estimation training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dry] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dry] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up steps, the K timed steps, the arrays of
+``--dump-outputs``, the JSON line.  ``--full`` adds every side measurement listed below (per-kernel figures, the eager / host-to-device
+/ ragged variants, the stand-alone STFT rows, the CPU baseline, the all-reduce timings of N > 1) behind the timed steps; the timed
+steps, and so ``value`` / ``ms_per_step``, are the same with and without it.
 
 ``--gpus N`` with N > 1 launches itself as N ranks (``python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1``, one rank per GPU over RCCL); when it is already running under
@@ -17,7 +22,11 @@ Other configurations of BASELINE.json (parity / scaling cases, not the default l
   c3  PIT, batch 64, 16 kHz;  c4  c3 with 4 micro-steps per rank per optimizer step (the reference's
   virtual_minibatch_size = 4 x devices);  c5  deep-clustering model, K = 3, batch 64, 16 kHz.
 
-The JSON line also carries
+The headline:
+  value / ms_per_step   N = 1: the CAPTURED step (train.graphed.GraphedStep: every launch of the optimizer step in one hipGraph, replayed)
+                  with the loss / gradient-norm / watchdog checks at the end of the SAME step - one host synchronisation per step, errors
+                  raise in the iteration they belong to like the reference's (trainer.py:622-636, :740-780).
+With ``--full`` the JSON line also carries
   roofline        the ONE kernel with the most GPU time per step (as rocprofv3's summary of the same command names it), HIP-event
                   time of its launches inside the timed steps minus the bracket of an empty launch, against the peak that bounds
                   it; other_kernels lists every other hand-written kernel of the step the same way, plus the stand-alone STFT /
@@ -25,13 +34,11 @@ The JSON line also carries
   value_ragged    the same step on SURVEY 8d's training distribution (example lengths ~ U[3 s, 6 s]) in frames/s, ms_per_step_ragged;
   cpu_baseline    the oracle's torch-CPU port of the reference step (oracle/torch_ref.py) timed on this box's host
                   cores on a bounded sample (rank 0, N = 1 only), at 1 thread, 16 threads and all cores;
-  value / ms_per_step   N = 1: the CAPTURED step (train.graphed.GraphedStep: every launch of the optimizer step in one hipGraph, replayed)
-                  with the loss / gradient-norm / watchdog checks at the end of the SAME step - one host synchronisation per step, errors
-                  raise in the iteration they belong to like the reference's (trainer.py:622-636, :740-780);
   ms_per_step_eager_deferred / _end_of_step_checks / _sync_checks   the eager step of rounds 1-4 with the checks one step late (the host
                   runs ahead), at the end of the same step, and with the reference's two mid-step syncs;
   ms_per_step_h2d the same step with the waveform batch starting in (pinned) host memory;
-  rccl            (N > 1) world size, bucket layout and the time of a blocking all-reduce of the flat gradient buffer.
+  rccl            (N > 1) the time of a blocking all-reduce of the flat gradient buffer and of every layer bucket, the step without
+                  the exchange (scaling).  A plain run at N > 1 carries world size, bucket layout, the probed schedules and per_rank.
 ``--dry`` (no GPU needed; used by the CPU test suite): the same launcher, process group (gloo), gradient buckets
 and JSON line around a stub step.
 """
@@ -77,13 +84,16 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--config', choices=sorted(CONFIGS), default='c2')
     ap.add_argument('--dry', action='store_true', help='launcher / process group / buckets / JSON line around a stub step (CPU, gloo)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='behind the timed steps, every side measurement as well: per-kernel figures, eager / host-to-device / ragged variants, '
+                         'stand-alone STFT rows, CPU baseline, all-reduce timings (N > 1); the --no-* switches below drop parts of it')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
     ap.add_argument('--cpu-baseline-variant', type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument('--cpu-baseline-batch', type=int, default=4, help=argparse.SUPPRESS)
     ap.add_argument('--no-kernel-events', action='store_true',
-                    help='no eager pass with per-kernel HIP events behind the timed replays (profiling runs: the trace then holds the '
-                         'warm-up steps and the replays only)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the sync-checks / host-to-device / all-reduce side measurements')
+                    help='with --full: no eager pass with per-kernel HIP events behind the timed replays (profiling runs: the trace then '
+                         'holds the warm-up steps and the replays only)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the sync-checks / host-to-device / ragged / stand-alone STFT side measurements')
     ap.add_argument('--library-gemms', action='store_true',
                     help='dense layers on the BLAS library (TunableOp selections of scripts/tuned) instead of csrc/gemm.hip')
     ap.add_argument('--bf16', action='store_true',
@@ -266,7 +276,7 @@ def cpu_baseline(max_seconds=12., variant_timeout=60.):
 def replay_profile(symbol, config):
     """Average launch duration (ms) of the kernel whose name contains ``symbol`` in the committed rocprofv3 summary of THIS command's
     replays (``profiles/r6_kernel_trace_replay_<config>.txt``: ``rocprofv3 --kernel-trace --stats -- python bench.py --config <config>
-    --no-extras --no-kernel-events --no-cpu-baseline``: the warm-up steps and the replayed graph, no eager measurement passes).  A
+    --full --no-extras --no-kernel-events --no-cpu-baseline``: the warm-up steps and the replayed graph, no eager measurement passes).  A
     replay takes no event records between its nodes (external events are refused on ROCm: ``scripts/mb/graph_events.py``), so this
     is where the kernels of the TIMED mode are timed; None without a committed profile."""
     f = REPO / 'profiles' / f'r6_kernel_trace_replay_{config}.txt'
@@ -836,7 +846,10 @@ def main():
             elapsed_graph = graph_loop(args.steps)
             snapshot(graphed)
             graphed.times, graph_state['times'] = None, graphed.times
-            # per-kernel HIP events: an eager pass of the same step (same protocol) behind the timed region, as for N = 1
+            # per-kernel HIP events (--full): an eager pass of the same step (same protocol) behind the timed region, as for N = 1
+            if not args.full:
+                graph_state['eager_deferred_ms'] = None
+                return elapsed_graph
             ev_steps = max(TIMER_EVERY, min(args.steps, 10 * TIMER_EVERY))
             for _ in range(2):
                 step(False)
@@ -878,8 +891,8 @@ def main():
         if args.dp_graph:
             graphed.times, graph_state['times'] = None, graphed.times
         # per-kernel HIP events cannot be recorded inside a replay: the same launches are bracketed in an eager pass of the same step
-        # behind the timed region (rocprofv3's summary of this command sees the replays' kernels themselves: profiles/)
-        if args.no_kernel_events:
+        # behind the timed region, with --full (rocprofv3's summary of this command sees the replays' kernels themselves: profiles/)
+        if not args.full or args.no_kernel_events:
             graph_state['eager_deferred_ms'] = None
             return elapsed_graph
         ev_steps = max(TIMER_EVERY, min(args.steps, 10 * TIMER_EVERY))
@@ -918,7 +931,7 @@ def main():
         if os.environ.get('PTMI_BENCH_TRACE'):
             print(f'[bench {time.perf_counter() - t_trace:8.2f} s] {what}', file=sys.stderr, flush=True)
     trace('timed steps done')
-    if not args.dry and not args.no_extras:
+    if not args.dry and args.full and not args.no_extras:
         nx = max(5, min(args.steps, 50))
         if use_graph:
             graphed = graph_state['step']
@@ -1110,40 +1123,7 @@ def main():
     rccl = None
     if world > 1:
         flat = trainer._flat.flat
-        reps = 2 if args.dry else 10
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-        sync()
-        ar_ms = (time.perf_counter() - t0) / reps * 1e3
-        # every layer bucket on its own (what the overlapped schedule issues under the backward pass, last bucket first)
-        bucket_ms = []
-        for start, end, _ in (buckets.buckets if buckets is not None else [[0, flat.numel(), 0]]):
-            seg = flat[start:end]
-            sync()
-            t0 = time.perf_counter()
-            for _ in range(reps):
-                dist.all_reduce(seg, op=dist.ReduceOp.SUM)
-            sync()
-            bucket_ms.append((time.perf_counter() - t0) / reps * 1e3)
-        flat.zero_()
         nbytes = flat.numel() * 4
-        # the same step WITHOUT the exchange (every rank on its own gradients; the last thing the run does to the replicas): what the
-        # measured step is an efficiency of, and what the two schedules predict from it
-        local_ms = None
-        if not args.dry:
-            set_overlap(False)
-            # (a measurement bracket of this script, not a switch of the Trainer: on THIS object the data-parallel branch of
-            #  optimizer_step / clip_grad answers "no process group" - nothing on the product path reads a bench flag)
-            trainer._dp_active = lambda: False
-            try:
-                for _ in range(2):
-                    step(False)
-                nl = max(3, min(args.steps, 20))
-                local_ms = timed_loop(nl) / nl * 1e3
-            finally:
-                del trainer._dp_active
         # which GPU every rank is bound to (one process per GPU: the ranks must sit on DISTINCT devices - two ranks on one GPU would
         # halve the recurrences' CUs under each other and deadlock RCCL's intra-node transport)
         if args.dry:
@@ -1163,24 +1143,61 @@ def main():
             rccl_version = None
         rccl = dict(world_size=dist.get_world_size(), backend=backend, overlap_allreduce=buckets is not None, schedule=schedule,
                     rccl_version=rccl_version, ranks=ranks,
-                    # what to read the measured figures against: a ring all-reduce over xGMI moves 2 (W - 1) / W x bytes per rank and is
-                    # bound by ONE link's ~153 GB/s per direction between neighbours (MI355X_MICROARCH.md); with 7 links per GPU RCCL
-                    # runs several rings in parallel, so the bus bandwidth of a 94 MB buffer at W = 8 is expected between ~150 (one
-                    # ring) and ~600 GB/s, i.e. 0.3 - 1.1 ms per all-reduce, under 15 % of the B = 32 step and overlappable with the
-                    # backward pass (layer buckets)
-                    expected=dict(bus_bandwidth_gbs=[150., 600.], blocking_all_reduce_ms_at_w8=[0.27, 1.1],
-                                  weak_scaling_efficiency_floor=0.85),
                     buckets=[b[1] - b[0] for b in buckets.buckets] if buckets is not None else [flat.numel()],
-                    flat_gradient_bytes=nbytes, blocking_all_reduce_ms=ar_ms, bucket_all_reduce_ms=bucket_ms,
-                    # weak scaling read against THIS run's own numbers: the step without any exchange, the step as timed, and what the two
-                    # schedules predict (nothing hidden: local + blocking all-reduce; everything hidden: local).  DESIGN.md section 5
-                    # predicts 0.27 - 1.1 ms for the 94 MB bucket at W = 8.
-                    scaling=dict(ms_per_step_without_exchange=local_ms,
-                                 measured_efficiency=None if local_ms is None else local_ms / (elapsed / args.steps * 1e3),
-                                 predicted_efficiency_unoverlapped=None if local_ms is None else local_ms / (local_ms + ar_ms),
-                                 predicted_efficiency_fully_overlapped=None if local_ms is None else 1.0),
-                    bus_bandwidth_gbs=2. * (world - 1) / world * nbytes / (ar_ms * 1e-3) / 1e9,
+                    flat_gradient_bytes=nbytes,
                     time_per_all_reduce_host_ms=trainer.timer.get('time_per_all_reduce', 0.) / max(1, trainer._opt_step) * 1e3)
+    if world > 1 and args.full:
+        # (--full) the exchange on its own, and the step without it
+        reps = 2 if args.dry else 10
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+        sync()
+        ar_ms = (time.perf_counter() - t0) / reps * 1e3
+        # every layer bucket on its own (what the overlapped schedule issues under the backward pass, last bucket first)
+        bucket_ms = []
+        for start, end, _ in (buckets.buckets if buckets is not None else [[0, flat.numel(), 0]]):
+            seg = flat[start:end]
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                dist.all_reduce(seg, op=dist.ReduceOp.SUM)
+            sync()
+            bucket_ms.append((time.perf_counter() - t0) / reps * 1e3)
+        flat.zero_()
+        # the same step WITHOUT the exchange (every rank on its own gradients; the last thing the run does to the replicas): what the
+        # measured step is an efficiency of, and what the two schedules predict from it
+        local_ms = None
+        if not args.dry:
+            set_overlap(False)
+            # (a measurement bracket of this script, not a switch of the Trainer: on THIS object the data-parallel branch of
+            #  optimizer_step / clip_grad answers "no process group" - nothing on the product path reads a bench flag)
+            trainer._dp_active = lambda: False
+            try:
+                for _ in range(2):
+                    step(False)
+                nl = max(3, min(args.steps, 20))
+                local_ms = timed_loop(nl) / nl * 1e3
+            finally:
+                del trainer._dp_active
+        rccl.update(
+            # what to read the measured figures against: a ring all-reduce over xGMI moves 2 (W - 1) / W x bytes per rank and is
+            # bound by ONE link's ~153 GB/s per direction between neighbours (MI355X_MICROARCH.md); with 7 links per GPU RCCL
+            # runs several rings in parallel, so the bus bandwidth of a 94 MB buffer at W = 8 is expected between ~150 (one
+            # ring) and ~600 GB/s, i.e. 0.3 - 1.1 ms per all-reduce, under 15 % of the B = 32 step and overlappable with the
+            # backward pass (layer buckets)
+            expected=dict(bus_bandwidth_gbs=[150., 600.], blocking_all_reduce_ms_at_w8=[0.27, 1.1],
+                          weak_scaling_efficiency_floor=0.85),
+            blocking_all_reduce_ms=ar_ms, bucket_all_reduce_ms=bucket_ms,
+            # weak scaling read against THIS run's own numbers: the step without any exchange, the step as timed, and what the two
+            # schedules predict (nothing hidden: local + blocking all-reduce; everything hidden: local).  DESIGN.md section 5
+            # predicts 0.27 - 1.1 ms for the 94 MB bucket at W = 8.
+            scaling=dict(ms_per_step_without_exchange=local_ms,
+                         measured_efficiency=None if local_ms is None else local_ms / (elapsed / args.steps * 1e3),
+                         predicted_efficiency_unoverlapped=None if local_ms is None else local_ms / (local_ms + ar_ms),
+                         predicted_efficiency_fully_overlapped=None if local_ms is None else 1.0),
+            bus_bandwidth_gbs=2. * (world - 1) / world * nbytes / (ar_ms * 1e-3) / 1e9)
 
     # where a rank's step time goes: wall-clock per step beside the GPU time of its parts - a first multi-GPU record
     # then separates the cost of the wire (exchange_ms: both collectives, on the step's stream) from the host's
@@ -1249,7 +1266,7 @@ def main():
         if args.dry:
             out['dry'] = True
             out['roofline'] = None
-        else:
+        elif args.full:
             # (ragged batches: the per-kernel figures assume frames_per_step / batch time steps per launch - a reported mode without them)
             trace('extras done')
             overhead = event_bracket_overhead_ms(device)
@@ -1284,7 +1301,7 @@ def main():
             out['value_to_device_inclusive'] = frames_per_step * world / (extras['ms_per_step_h2d_prefetched'] * 1e-3)
         if rccl is not None:
             out['rccl'] = rccl
-        if world == 1 and not args.no_cpu_baseline and not args.dry:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.dry:
             out['cpu_baseline'] = cpu_baseline()
     for h in hooks:
         h.remove()

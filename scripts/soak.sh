@@ -3,7 +3,7 @@
 # unsynchronised: the situation in which a kernel that waits for undispatched workgroups next to a persistent recurrence would hang)
 # and long runs; a recurrence watchdog timeout or a non-finite value ends bench.py with an error.  -> gpurun_out/soak.txt
 out=gpurun_out/soak.txt; mkdir -p gpurun_out; : > $out
-run() { local t0=$(date +%s.%N); timeout 600 python bench.py --no-cpu-baseline --no-extras "$@" 2>/dev/null | tail -1 | python -c "
+run() { local t0=$(date +%s.%N); timeout 600 python bench.py --full --no-cpu-baseline --no-extras "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); print('ok  %-28s %8.3f ms/step %9.0f frames/s' % (' '.join(sys.argv[1:]), d['ms_per_step'], d['value']))

@@ -23,7 +23,7 @@ def _run(*extra, **env_extra):
 
 
 def test_self_launch_two_ranks_bucketed_allreduce():
-    out = _run('--gpus', '2')
+    out = _run('--gpus', '2', '--full')
     assert out['n_gpus'] == 2 and out['dry'] is True and out['steps'] == 2
     assert out['config']['parallelism'] == 'dp2' and out['config']['global_batch'] == 64
     r = out['rccl']
@@ -59,6 +59,17 @@ def test_c4_micro_steps_single_allreduce_per_optimizer_step():
 def test_single_process_dry():
     out = _run()
     assert out['n_gpus'] == 1 and 'rccl' not in out
+
+
+def test_plain_run_leaves_the_side_measurements_to_full():
+    """A plain run does what the headline needs: the schedule it timed and the bucket layout, no all-reduce timings and no step
+    without the exchange (those come with --full)."""
+    out = _run('--gpus', '2')
+    assert out['n_gpus'] == 2 and out['value'] > 0 and out['ms_per_step'] > 0 and out['steps'] == 2 and out['warmup'] == 1
+    r = out['rccl']
+    assert r['world_size'] == 2 and r['schedule']['used'] == 'overlap' and sum(r['buckets']) == 23480914
+    assert not {'blocking_all_reduce_ms', 'bucket_all_reduce_ms', 'scaling', 'bus_bandwidth_gbs', 'expected'} & set(r), sorted(r)
+    assert 'cpu_baseline' not in out
 
 
 def test_dump_outputs_are_float_arrays_within_budget_and_repeat(tmp_path):

@@ -18,7 +18,7 @@ def test_bench_two_ranks_probe_all_schedules_and_time_the_captured_step():
     env = dict(os.environ, PTMI_BENCH_SHARE_GPU='1', PTMI_BENCH_UNITS='48', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--no-cpu-baseline'],
+    p = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(REPO))
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith('{')]
