@@ -194,6 +194,12 @@ def stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def device_key(device):
+    """``(type, index)`` with the index filled in (``cuda`` -> the current device): the key of every per-GPU registry."""
+    device = torch.device(device)
+    return device.type, device.index if device.index is not None else torch.cuda.current_device()
+
+
 #: when a list, ``timed`` brackets every kernel launch with HIP events recorded on the launch stream
 #: and appends ``(name, start_event, end_event)`` (bench.py's roofline figure); None = off
 KERNEL_TIMERS = None

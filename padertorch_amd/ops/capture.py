@@ -50,13 +50,10 @@ def zero_word(device, block_words=64):
 
 def reset_step_caches():
     """Forget everything the ops have cached from earlier steps that orders work (events) or stands for parameter values (forms)."""
-    from . import gemm as _gemm, lstm as _lstm
-    known = dict(_gemm._KNOWN)      # which forms the dense layers' parameters are used in: knowledge, not state - kept
-    _gemm.invalidate()              # operand scales / planes / stacked LSTM forms / the optimizer's update event
-    _gemm._KNOWN.update(known)
-    _lstm._EARLY_FORK.clear()
-    _gemm._WAITED.clear()
-    _lstm._WGRAD_DONE.clear()
+    from . import gemm as _gemm, lstm_forms as _forms, wgrad as _wgrad
+    _gemm.reset_step()              # operand scales / planes / stacked LSTM forms / the optimizer's update event
+    _forms.reset_step()             # the preparation queues a capture has forked
+    _wgrad.reset_step()             # the weight-gradient events of the last step
 
 
 @contextlib.contextmanager

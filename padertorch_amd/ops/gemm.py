@@ -84,8 +84,17 @@ def invalidate():
     _WEIGHT_PLANES.clear()
     _UPDATED.clear()
     _KNOWN.clear()
-    from . import lstm as _lstm
-    _lstm._STACKED.clear()
+    from . import lstm_forms as _forms
+    _forms.clear()
+
+
+def reset_step():
+    """:func:`invalidate` for a step boundary (``ops.capture``): drops everything that orders work or stands for parameter values,
+    keeps which forms the dense layers' parameters are used in (``_KNOWN``: knowledge, not state)."""
+    known = dict(_KNOWN)
+    invalidate()
+    _KNOWN.update(known)
+    _WAITED.clear()
 
 
 class _Words(threading.local):
@@ -155,7 +164,7 @@ def _cached(cache, key, p, make, limit, form=None):
                 cur.wait_event(hit[4])
                 _WAITED[cur.cuda_stream] = hit[4]
             # (no record_stream: the tensors' memory belongs to the preparation stream's pool, whose every piece of work is
-            # enqueued behind the optimizer kernel and so behind every reader - see ops.lstm._stacked_weights)
+            # enqueued behind the optimizer kernel and so behind every reader - see ops.lstm_forms)
         return hit[2]
     if len(cache) > limit:
         cache.clear()
@@ -173,7 +182,7 @@ def _cached(cache, key, p, make, limit, form=None):
 
 
 def prefetch_known(device, everything=False):
-    """Re-make, on the CURRENT stream (a side stream ordered behind the optimizer kernel: ``ops.lstm.packed_lstm``), the operand
+    """Re-make, on the CURRENT stream (a side stream ordered behind the optimizer kernel: ``ops.lstm_forms.fork_preparation``), the operand
     forms - maximum, fp16 planes in either orientation - that the dense layers asked for in earlier steps and that an optimizer step
     has made stale: a handful of small launches (~5 us each, 45 us per step of the PIT model) that otherwise sit in front of the
     first use on the main stream, between the last recurrence and the loss."""

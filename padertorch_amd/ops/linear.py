@@ -13,6 +13,7 @@ import torch
 from . import context as _context
 from . import gemm as _gemm
 from . import lstm as _lstm
+from . import wgrad as _wgrad
 
 __all__ = ['linear']
 
@@ -100,7 +101,7 @@ class _LinearFn(torch.autograd.Function):
             db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
             return dx, dw, db, None, None, None
         main = torch.cuda.current_stream(x.device)
-        side = _lstm._wgrad_stream(x.device) if oc.wgrad_side_stream else main
+        side = _wgrad.stream(x.device) if oc.wgrad_side_stream else main
         has_bias = ctx.has_bias
 
         def accumulate(start=None):
@@ -110,7 +111,7 @@ class _LinearFn(torch.autograd.Function):
                 else:
                     side.wait_stream(torch.cuda.current_stream(x.device))
             else:
-                main.wait_stream(_lstm._wgrad_stream(x.device))
+                main.wait_stream(_wgrad.stream(x.device))
             with torch.cuda.stream(side):
                 if _gemm.planes_enabled() and x.stride(1) == 1:
                     # (beside the top BLSTM layer's backward recurrence: co_resident_split_k)
@@ -129,7 +130,7 @@ class _LinearFn(torch.autograd.Function):
         from . import capture as _capture
         small = 2. * g.shape[0] * g.shape[1] * x.shape[1] <= DEFER_MAX_FLOP
         if DEFER_TO_RECURRENCE and small and (_capture.ACTIVE or DEFER_IN_EAGER) and side is not main and ctx.needs_input_grad[0]:
-            # enqueued behind - and started with - the recurrence launch of the BLSTM layer below (ops.lstm.flush_pending_wgrad;
+            # enqueued behind - and started with - the recurrence launch of the BLSTM layer below (ops.wgrad.flush_pending;
             # sync_deferred enqueues it when there is none).  Started here, linear2's weight gradient ran beside the input-gradient
             # chain relu' -> pack -> GEMM of linear1 that the top layer's backward recurrence waits for (that chain 151 us instead of
             # ~100 in the replay's timeline); a recurrence gives up ~7 % of the time of what runs beside it.  Round 6, one box,
@@ -138,7 +139,7 @@ class _LinearFn(torch.autograd.Function):
             # RCCL group with layer buckets, but the eager BUCKETED two-rank run over gloo (tests/test_gpu_graphed_dp.py: two processes on
             # one GPU) then ends 3e-4 away from the captured one - with linear1's deferred, not with linear2's alone; with or without
             # the start event - not understood, so not shipped.
-            _lstm._PENDING_WGRAD.append(accumulate)
+            _wgrad.defer(accumulate)
         else:
             accumulate()
         return dx, None, None, None, None, None

@@ -17,23 +17,18 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ..pack_meta import Layout
 
 __all__ = ['SlotLayout', 'StaticSlots']
 
 
-class _SlotMeta:
-    """What ``ops.lstm._LstmLayerFn`` reads of a batch layout (the fields of ``ops.lstm._PackMeta``) for rows = [T, slots]."""
+class _SlotMeta(Layout):
+    """The batch layout (``ops.pack_meta.Layout``) of rows = [T, slots]."""
 
     def __init__(self, layout, device):
         T, S = layout.T, layout.slots
         self.key = ('slots', S, tuple(layout.lengths), tuple(layout.slot), tuple(layout.t0))
-        self.T, self.max_batch, self.rows = T, S, T * S
-        self.bs_host = np.full(T, S, dtype=np.int32)
-        self.offs_host = (np.arange(T, dtype=np.int64) * S)
-        self.bs_dev = _lib.host_to_device(self.bs_host, torch.int32, device)
-        self.offs_dev = _lib.host_to_device(self.offs_host, torch.int64, device)
-        self.bs0 = S
-        self.equal_lengths = False                    # no shifted-view / hand-off-plane shortcuts: rows of different sequences neighbour
+        self._set_uniform_grid(T, S, device)
         rows = self.rows
         # predecessor row per direction (forward sense), `rows` = none (the zero row ops.lstm._recurrent_operands appends)
         alive, first, last = layout.alive, layout.first, layout.last          # [T, S] bool
@@ -49,7 +44,6 @@ class _SlotMeta:
         bits = (1 << np.arange(S, dtype=np.uint64))
         masks = np.stack([(m.astype(np.uint64) * bits).sum(1, dtype=np.uint64) for m in (alive, first, last)], 1)     # [T, 3]
         self.masks_dev = _lib.host_to_device(masks.view(np.int64).reshape(-1), torch.int64, device)
-        self.first_rows = self.last_rows = self.prev_h0_dev = self.padded_rows = None        # (initial / final states: not for slots)
 
 
 class SlotLayout:
@@ -132,20 +126,13 @@ def _cached_layout(lengths, slots, device_key):
     return SlotLayout(lengths, slots, torch.device(*device_key))
 
 
-class _StaticSlotMeta:
-    """The fields ``ops.lstm._LstmLayerFn`` reads of a batch layout for a grid of FIXED size whose pattern is device data."""
+class _StaticSlotMeta(Layout):
+    """The batch layout (``ops.pack_meta.Layout``) of a grid of FIXED size whose pattern is device data."""
 
     def __init__(self, T, S, prev_dev, masks_dev, device):
         self.key = ('static slots', S, T)
-        self.T, self.max_batch, self.rows = T, S, T * S
-        self.bs_host = np.full(T, S, dtype=np.int32)
-        self.offs_host = (np.arange(T, dtype=np.int64) * S)
-        self.bs_dev = _lib.host_to_device(self.bs_host, torch.int32, device)
-        self.offs_dev = _lib.host_to_device(self.offs_host, torch.int64, device)
-        self.bs0 = S
-        self.equal_lengths = False
+        self._set_uniform_grid(T, S, device)
         self.prev_dev, self.masks_dev = prev_dev, masks_dev
-        self.first_rows = self.last_rows = self.prev_h0_dev = self.padded_rows = None
 
 
 class _GatherRows(torch.autograd.Function):

@@ -472,8 +472,8 @@ class Trainer:
     def _abandon_capture(self, device):
         """After a capture that raised: nothing of it has run, but the host-side queues of the step path still name its tensors and
         events (weight-gradient closures waiting for their enqueue point, staged scalars, the device flag of the update gate)."""
-        from ..ops import capture as _capture, lstm as _lstm
-        del _lstm._PENDING_WGRAD[:]
+        from ..ops import capture as _capture, wgrad as _wgrad
+        _wgrad.abandon()
         self._stage_queue = []
         self._graph_stage = None
         self._loss_acc = None
@@ -902,7 +902,7 @@ class Trainer:
     def enable_bucketed_allreduce(self):
         """Data parallel with ``overlap_allreduce``: build the layer buckets over the flat gradient buffer and hook
         them to gradient completion.  Returns the autograd hook handles (``train`` removes them)."""
-        from ..ops import lstm as _lstm
+        from ..ops import wgrad as _wgrad
         # (a process group of ONE rank still takes the collective path: that is how the RCCL code is exercised on a
         # single-GPU box, tests/test_gpu_model.py::test_trainer_rccl_path_world_size_1)
         if not self._dp_active() or not self.overlap_allreduce or self._flat is None:
@@ -914,7 +914,7 @@ class Trainer:
         def side():
             # the weight-gradient stream of the stream that is current WHEN a gradient becomes ready (the backward pass runs under the
             # forward pass' stream): looked up then, not captured here - train() may be entered under another stream context
-            return _lstm._wgrad_stream(dev) if dev.type == 'cuda' else None
+            return _wgrad.stream(dev) if dev.type == 'cuda' else None
 
         def on_grad(p):
             buckets.ready((p,), side())

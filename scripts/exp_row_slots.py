@@ -63,7 +63,7 @@ faulthandler.dump_traceback_later(40, exit=True)
 for it in range(6):
     t0 = time.perf_counter()
     _slots._cached_layout.cache_clear()
-    pt.ops.lstm._meta.cache_clear()
+    pt.ops.pack_meta._meta.cache_clear()
     feats = pt.ops.pit_features(y, s, lens)
     loss, _, _, _ = trainer.train_step(model, feats, dev)
     t1 = time.perf_counter()

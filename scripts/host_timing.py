@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import padertorch_amd as pt
 from padertorch_amd.contrib.examples.source_separation.pit.model import PermutationInvariantTrainingModel
-from padertorch_amd.ops import lstm as _lstm
+from padertorch_amd.ops import lstm as _lstm, pack_meta
 import bench
 
 dev = torch.device('cuda', 0)
@@ -42,7 +42,7 @@ trainer._check_pending = timed_check
 
 def step():
     if RAGGED:
-        _lstm._meta.cache_clear()
+        pack_meta._meta.cache_clear()
     t0 = time.perf_counter()
     feats = pt.ops.pit_features(data['y'], data['s'], data['num_samples'])
     t1 = time.perf_counter()
