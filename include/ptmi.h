@@ -417,6 +417,43 @@ int ptmi_td_lincomb(const float* x, const float* y, const int32_t* lengths, cons
                     const float* coef_b, const float* coef_c, int64_t batch, int32_t K, int64_t T,
                     const int64_t* strides, float* out, ptmi_stream_t stream);
 
+/* ---- TasNet learned-basis encoder / decoder ---------------------------------------------------------
+ * Replaces torch.nn.Conv1d(1, N, L, stride) + relu of TasEncoder and torch.nn.ConvTranspose1d(N, 1, L, stride)
+ * of TasDecoder (padertorch/contrib/examples/source_separation/tasnet/tas_coders.py:9-135), the
+ * "mask x encoded -> decode" tail of TasNet.forward (tasnet/model.py:119-129), and their autograd backwards.
+ * All tensors fp32 and contiguous: signals [B, T], features [B, N, E], masks [K, B, N, E], weight [N, L]
+ * (either module's [N, 1, L] parameter).  No atomics; every sum has a fixed order (bit-reproducible); no
+ * allocation and no synchronisation (capturable).  B <= 65535.
+ *
+ * ptmi_tas_analysis : out[b,n,tau] = act(sum_l weight[n,l] x[b, tau stride + l] + bias[n]), tau < E; samples at or
+ *   beyond T read as zero (the zero padding of tas_coders.py:73-76 without the copy); bias [N] or NULL;
+ *   relu != 0: act = relu (tas_coders.py:87), else identity (the decoder's gradient w.r.t. its input).
+ * ptmi_tas_synthesis: y[k,b,t] = sum_n sum_{tau stride + l = t} p[b,n,tau] weight[n,l] + bias[0], t < T_out: the decoder's
+ *   T_out is (E - 1) stride + L (tas_coders.py:135); a sample no window reaches (stride > L, or t beyond that) gets the
+ *   bias alone; bias [1] or NULL.  mask [K, B, N, E]: p counts as mask[k] p, formed
+ *   on the fly (model.py:119-129); else K = 1.  gate [B, N, E] (without mask): p counts where gate > 0 (the
+ *   encoder's gradient w.r.t. its input: p = grad, gate = the encoder's output, T_out = T).
+ * ptmi_tas_masked_decode_backward: with A_k = analysis(gy[k]) (identity, no bias; never stored):
+ *   dmask[k,b,n,tau] = encoded[b,n,tau] A_k[b,n,tau], dencoded[b,n,tau] = sum_k mask[k,b,n,tau] A_k[b,n,tau];
+ *   gy [K, B, T].
+ * ptmi_tas_wgrad    : out[0 : N L]       = dW[n,l] = sum_{k,b,tau} g[b,n,tau] x[k,b, tau stride + l]
+ *                     out[N L : N L + N] = sum_{b,tau} g[b,n,tau]     (the encoder's bias gradient)
+ *                     out[N L + N]       = sum_{k,b,t} x[k,b,t]       (the decoder's bias gradient)
+ *   x [K, B, T] reads as zero beyond T.  mask / gate as in ptmi_tas_synthesis (g counts as mask[k] g, or where
+ *   gate > 0).  workspace: ptmi_tas_wgrad_workspace_elems(B, N, L, stride, E) floats of per-workgroup partial
+ *   sums, added in a fixed order by a second kernel. */
+int ptmi_tas_analysis(const float* x, const float* weight, const float* bias, float* out, int64_t B, int64_t T, int32_t N,
+                      int32_t L, int32_t stride, int64_t E, int32_t relu, ptmi_stream_t stream);
+int ptmi_tas_synthesis(const float* p, const float* mask, const float* gate, const float* weight, const float* bias, float* y,
+                       int32_t K, int64_t B, int32_t N, int32_t L, int32_t stride, int64_t E, int64_t T_out,
+                       ptmi_stream_t stream);
+int ptmi_tas_masked_decode_backward(const float* gy, const float* mask, const float* encoded, const float* weight, float* dmask,
+                                    float* dencoded, int32_t K, int64_t B, int64_t T, int32_t N, int32_t L, int32_t stride,
+                                    int64_t E, ptmi_stream_t stream);
+int64_t ptmi_tas_wgrad_workspace_elems(int64_t B, int32_t N, int32_t L, int32_t stride, int64_t E);
+int ptmi_tas_wgrad(const float* g, const float* mask, const float* gate, const float* x, int32_t K, int64_t B, int64_t T,
+                   int32_t N, int32_t L, int32_t stride, int64_t E, float* workspace, float* out, ptmi_stream_t stream);
+
 /* ---- Dense layers: fp32 GEMM on the 16-bit matrix cores (split operands) --------------------------
  * Replaces the library GEMMs behind torch.nn.LSTM's input projections and torch.nn.Linear in
  * padertorch/contrib/examples/source_separation/pit/model.py:60-66,97-104 and contrib/tcl/dc.py:32-40,61-66

@@ -67,6 +67,12 @@ SIGNATURES = {
     'ptmi_td_workspace_elems': (c_int64, [c_int64, c_int32, c_int64]),
     'ptmi_td_pair_stats': (c_int, [_P, _P, _P, c_int64, c_int32, c_int64, _I64P, _P, _P, _P]),
     'ptmi_td_lincomb': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _I64P, _P, _P]),
+    'ptmi_tas_analysis': (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, c_int32, _P]),
+    'ptmi_tas_synthesis': (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64, _P]),
+    'ptmi_tas_masked_decode_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                                c_int64, _P]),
+    'ptmi_tas_wgrad_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int64]),
+    'ptmi_tas_wgrad': (c_int, [_P, _P, _P, _P, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, _P, _P, _P]),
     'ptmi_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_unit_norm_forward': (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),

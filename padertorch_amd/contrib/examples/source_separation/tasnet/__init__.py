@@ -1,2 +1,2 @@
-from .tas_coders import StftEncoder, IstftDecoder  # noqa: F401
+from .tas_coders import StftEncoder, IstftDecoder, TasEncoder, TasDecoder  # noqa: F401
 from .loss import tasnet_loss  # noqa: F401

@@ -1,5 +1,13 @@
-"""STFT front and back end of the reference's TasNet variant on the HIP STFT
-(``padertorch/contrib/examples/source_separation/tasnet/tas_coders.py:138-240``).
+"""The coders of the reference's TasNet (``padertorch/contrib/examples/source_separation/tasnet/tas_coders.py``): the learned
+filterbank pair ``TasEncoder`` / ``TasDecoder`` (``:9-135``) on the kernels of ``padertorch_amd.ops.tas``, and the STFT pair
+(``:138-240``) on the HIP STFT.
+
+``TasEncoder(window_length, feature_size, stride, bias)``: ``[B, T]`` or ``[T]`` -> ``(relu(conv1d) [B, feature_size, frames], lengths)``;
+``TasDecoder`` (same arguments): ``[B, feature_size, frames] -> [B, (frames - 1) * stride + window_length]``, and
+``TasDecoder.masked(mask [K, B, N, frames], encoded [B, N, frames]) -> [K, B, samples]`` decodes ``mask[k] * encoded`` for every ``k``
+without forming the product (the tail of the reference's ``TasNet.forward``, ``tasnet/model.py:119-129``).  Both hold the torch
+convolution modules of the reference as PARAMETER CONTAINERS (``encoder_1d`` / ``decoder_1d``: same initialisation, ``state_dict`` keys
+and shapes, so reference checkpoints load); the convolutions themselves never run.
 
 ``StftEncoder(window_length, feature_size, stride)``: ``[..., T] -> [..., feature_size, frames]`` with the real
 parts of the ``feature_size / 2`` bins on top of the imaginary parts; ``IstftDecoder`` is its inverse.  Both are
@@ -10,7 +18,7 @@ doctests (``:140-155``, ``:197-209``) and checked in ``tests/test_gpu_td.py``:
 """
 import torch
 
-from .....ops import STFT
+from .....ops import STFT, tas
 
 
 class _StftCoder(torch.nn.Module):
@@ -36,3 +44,42 @@ class StftEncoder(_StftCoder):
 class IstftDecoder(_StftCoder):
     def forward(self, stft_signal) -> torch.Tensor:
         return self.stft.inverse(stft_signal.transpose(-1, -2))
+
+
+def _default_stride(window_length, stride):
+    return window_length // 2 if stride is None else stride
+
+
+class TasEncoder(torch.nn.Module):
+    def __init__(self, window_length: int = 20, feature_size: int = 256, stride: int = None, bias: bool = False):
+        super().__init__()
+        self.window_length, self.feature_size, self.stride = window_length, feature_size, _default_stride(window_length, stride)
+        self.encoder_1d = torch.nn.Conv1d(1, feature_size, window_length, stride=self.stride, padding=0, bias=bias)
+
+    def encoded_lengths(self, sequence_lengths, samples):
+        """The reference's frame count of every ``sequence_lengths`` entry of a batch that is ``samples`` long (host arithmetic)."""
+        return tas.tas_encoded_lengths(sequence_lengths, samples, self.window_length)
+
+    def forward(self, x, sequence_lengths: torch.Tensor = None):
+        """``x (B, T)`` or ``(T,)`` -> ``(w (B, N, T_enc), sequence_lengths in frames or None)``; nothing is masked by the lengths."""
+        assert x.dim() in [1, 2], f'The {self.__class__.__name__} ony supports 1D and 2D input, but got {x.shape}.'
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        w = tas.tas_encode(x, self.encoder_1d.weight, self.encoder_1d.bias, self.stride, self.window_length)
+        return w, self.encoded_lengths(sequence_lengths, x.shape[-1])
+
+
+class TasDecoder(torch.nn.Module):
+    def __init__(self, window_length: int = 20, feature_size: int = 256, stride: int = None, bias=False):
+        super().__init__()
+        self.window_length, self.feature_size, self.stride = window_length, feature_size, _default_stride(window_length, stride)
+        self.decoder_1d = torch.nn.ConvTranspose1d(feature_size, 1, kernel_size=window_length, stride=self.stride, bias=bias)
+
+    def forward(self, w) -> torch.Tensor:
+        """``w (B, N, T_enc)`` -> the time signal ``(B, T)``."""
+        return tas.tas_decode(w, self.decoder_1d.weight, self.decoder_1d.bias, self.stride)
+
+    def masked(self, mask, encoded) -> torch.Tensor:
+        """``mask (K, B, N, T_enc)``, ``encoded (B, N, T_enc)`` -> ``(K, B, T)``: ``forward(mask[k] * encoded)`` for every ``k`` in one
+        kernel, the product formed on the fly (forward and backward)."""
+        return tas.tas_masked_decode(mask, encoded, self.decoder_1d.weight, self.decoder_1d.bias, self.stride)

@@ -13,3 +13,5 @@ from . import lstm  # noqa: F401
 from . import linear  # noqa: F401
 from .lstm import packed_lstm  # noqa: F401
 from .unit_norm import unit_norm  # noqa: F401
+from . import tas  # noqa: F401
+from .tas import tas_encode, tas_decode, tas_masked_decode  # noqa: F401

@@ -20,6 +20,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.pack_planes_t / _n, torch.ops.ptmi.gemm_planes_   ptmi_pack_planes_t / _n, ptmi_gemm_planes   (nn.LSTM input projections, nn.Linear, all their gradients)
     torch.ops.ptmi.lstm_weight_prep                ptmi_lstm_weight_prep      (the nn.LSTM parameters' operand forms, once per optimizer step)
     torch.ops.ptmi.grad_norm, torch.ops.ptmi.adam_flat_  ptmi_grad_norm, ptmi_adam_flat (train/optimizer.py:27-42, trainer.py:512-532)
+    torch.ops.ptmi.tas_analysis / tas_synthesis / tas_masked_decode_backward / tas_wgrad   ptmi_tas_*
+                                                                              (tasnet/tas_coders.py:9-135, tasnet/model.py:119-129)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -171,6 +173,74 @@ def dc_loss_backward(x, t, gram, g_loss, row_frames, B, T, E, K, F, strides, zer
                           g_loss.data_ptr(), B, T, _lib.strides8(*strides), E, K, F, _lib.ptr(row_frames), dx.data_ptr(),
                           _lib.stream(x.device)), 'ptmi_dc_loss_backward')
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ TasNet learned-basis coders
+def _tas_dims(feat, weight):
+    B, N, E = feat.shape
+    assert weight.shape[0] == N and weight.is_contiguous() and feat.is_contiguous(), (feat.shape, weight.shape)
+    return B, N, E, weight.numel() // N
+
+
+@_register('tas_analysis(Tensor x, Tensor weight, Tensor? bias, int stride, int frames, bool relu) -> Tensor')
+def tas_analysis(x, weight, bias, stride, frames, relu):
+    """``x [B, T]``, ``weight [N, (1,) L]`` -> ``act(conv1d(x, weight, stride) + bias) [B, N, frames]``; ``x`` reads as zero from ``T`` on
+    (``ptmi_tas_analysis``)."""
+    B, T = x.shape
+    N = weight.shape[0]
+    L = weight.numel() // N
+    assert x.is_contiguous() and weight.is_contiguous()
+    out = torch.empty((B, N, frames), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.timed('tas_analysis', _lib.load().ptmi_tas_analysis, x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), out.data_ptr(),
+                          B, T, N, L, stride, frames, int(relu), _lib.stream(x.device)), 'ptmi_tas_analysis')
+    return out
+
+
+@_register('tas_synthesis(Tensor p, Tensor? mask, Tensor? gate, Tensor weight, Tensor? bias, int stride, int samples) -> Tensor')
+def tas_synthesis(p, mask, gate, weight, bias, stride, samples):
+    """``conv_transpose1d`` of ``p [B, N, E]`` (of ``mask[k] * p`` for every ``k`` with ``mask [K, B, N, E]``; of ``p * (gate > 0)`` with
+    ``gate``), cut to ``samples``: ``[B, samples]``, with ``mask`` ``[K, B, samples]`` (``ptmi_tas_synthesis``)."""
+    B, N, E, L = _tas_dims(p, weight)
+    K = 1
+    if mask is not None:
+        K = mask.shape[0]
+        assert mask.shape == (K, B, N, E) and mask.is_contiguous(), mask.shape
+    assert gate is None or (gate.shape == p.shape and gate.is_contiguous())
+    y = torch.empty((B, samples) if mask is None else (K, B, samples), dtype=torch.float32, device=p.device)
+    _lib.check(_lib.timed('tas_synthesis', _lib.load().ptmi_tas_synthesis, p.data_ptr(), _lib.ptr(mask), _lib.ptr(gate), weight.data_ptr(),
+                          _lib.ptr(bias), y.data_ptr(), K, B, N, L, stride, E, samples, _lib.stream(p.device)), 'ptmi_tas_synthesis')
+    return y
+
+
+@_register('tas_masked_decode_backward(Tensor gy, Tensor mask, Tensor encoded, Tensor weight, int stride) -> (Tensor, Tensor)')
+def tas_masked_decode_backward(gy, mask, encoded, weight, stride):
+    """``(dmask, dencoded)`` of ``y[k] = conv_transpose1d(mask[k] * encoded)`` for ``gy [K, B, T]`` (``ptmi_tas_masked_decode_backward``)."""
+    B, N, E, L = _tas_dims(encoded, weight)
+    K, _, T = gy.shape
+    assert mask.shape == (K, B, N, E) and gy.shape[1] == B and mask.is_contiguous() and gy.is_contiguous(), (mask.shape, gy.shape)
+    dmask, denc = torch.empty_like(mask), torch.empty_like(encoded)
+    _lib.check(_lib.timed('tas_masked_decode_backward', _lib.load().ptmi_tas_masked_decode_backward, gy.data_ptr(), mask.data_ptr(),
+                          encoded.data_ptr(), weight.data_ptr(), dmask.data_ptr(), denc.data_ptr(), K, B, T, N, L, stride, E,
+                          _lib.stream(gy.device)), 'ptmi_tas_masked_decode_backward')
+    return dmask, denc
+
+
+@_register('tas_wgrad(Tensor g, Tensor? mask, Tensor? gate, Tensor x, int stride, int window_length) -> Tensor')
+def tas_wgrad(g, mask, gate, x, stride, window_length):
+    """``[N L + N + 1]``: ``dW [N, L]``, ``sum_{b, tau} g [N]`` and ``sum x [1]`` (``ptmi_tas_wgrad``); ``g [B, N, E]``, ``x [B, T]`` or,
+    with ``mask [K, B, N, E]``, ``[K, B, T]``."""
+    lib = _lib.load()
+    B, N, E = g.shape
+    L = window_length
+    K = 1 if mask is None else mask.shape[0]
+    assert g.is_contiguous() and x.is_contiguous() and x.shape[:-1] == ((B,) if mask is None else (K, B)), (g.shape, x.shape)
+    assert mask is None or (mask.shape == (K, B, N, E) and mask.is_contiguous())
+    assert gate is None or (gate.shape == g.shape and gate.is_contiguous())
+    ws = torch.empty(int(lib.ptmi_tas_wgrad_workspace_elems(B, N, L, stride, E)), dtype=torch.float32, device=g.device)
+    out = torch.empty(N * L + N + 1, dtype=torch.float32, device=g.device)
+    _lib.check(_lib.timed('tas_wgrad', lib.ptmi_tas_wgrad, g.data_ptr(), _lib.ptr(mask), _lib.ptr(gate), x.data_ptr(), K, B, x.shape[-1],
+                          N, L, stride, E, ws.data_ptr(), out.data_ptr(), _lib.stream(g.device)), 'ptmi_tas_wgrad')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ dense layers
