@@ -454,6 +454,40 @@ int64_t ptmi_tas_wgrad_workspace_elems(int64_t B, int32_t N, int32_t L, int32_t 
 int ptmi_tas_wgrad(const float* g, const float* mask, const float* gate, const float* x, int32_t K, int64_t B, int64_t T,
                    int32_t N, int32_t L, int32_t stride, int64_t E, float* workspace, float* out, ptmi_stream_t stream);
 
+/* ---- Conv-TasNet separator: the non-GEMM part of a temporal convolution block -------------------------
+ * Replaces, inside _Conv1DBlock (padertorch/modules/convnet.py:114-161), the chain PReLU -> pad -> depthwise dilated
+ * Conv1d -> PReLU and the norms gLN / cLN of padertorch/contrib/jensheit/norm.py:10-70, forward and backward.
+ * All activations fp32 [B, T, C] contiguous, CHANNELS INNERMOST (the reference's [B, C, T] transposed).  No atomics;
+ * partial sums are fp64 and added in a fixed order (bit-reproducible); no allocation, no synchronisation
+ * (capturable).  Workspaces are caller-owned arrays of DOUBLES.  B <= 65535.
+ *
+ * ptmi_tcn_depthwise_forward : v[b,t,h] = prelu(slope_out, bias[h] + sum_k weight[h,k] p[b, t + k dilation - front, h])
+ *   with p = prelu(slope_in, u), p = 0 outside [0, T) (the reference pads behind the first PReLU), front =
+ *   (dilation (K - 1)) / 2 (compute_pad_size(K, dilation, 1, 'both'): an even K pads the end more); weight [H, K] (the
+ *   [H, 1, K] parameter), bias [H] or NULL, slopes [1] in device memory; prelu'(0) = slope.
+ *   stats [B, 2] = (mean, 1 / sqrt(var + eps)) of v per example (biased variance): the gLN statistics, from the same launch's
+ *   partial sums.
+ * ptmi_tcn_depthwise_backward: gz [B, T, H] (scratch: the gradient at the second pre-activation, recomputed from u), gu,
+ *   dparams [H K + H + 2] = d weight [H, K] | d bias [H] | d slope_in | d slope_out.
+ * ptmi_tcn_norm_stats  : stats [G, 2] = (mean, rstd) of x per group: rows == 0 a group is an example (over T C, gLN; needs the
+ *   workspace), else a row (over C, cLN; workspace unused, may be NULL).
+ * ptmi_tcn_norm_apply  : y = gamma[c] (x - mean_g) rstd_g + beta[c].
+ * ptmi_tcn_norm_backward: dx, dparams [2 C] = d gamma | d beta; gsum [G, 2] scratch (the two group means of the gradient). */
+int64_t ptmi_tcn_depthwise_workspace_elems(int64_t B, int64_t T, int32_t H, int32_t K);
+int ptmi_tcn_depthwise_forward(const float* u, const float* slope_in, const float* weight, const float* bias, const float* slope_out,
+                               float* v, float* stats, double* workspace, int64_t B, int64_t T, int32_t H, int32_t K,
+                               int32_t dilation, float eps, ptmi_stream_t stream);
+int ptmi_tcn_depthwise_backward(const float* gv, const float* u, const float* slope_in, const float* weight, const float* bias,
+                                const float* slope_out, float* gz, float* gu, float* dparams, double* workspace, int64_t B,
+                                int64_t T, int32_t H, int32_t K, int32_t dilation, ptmi_stream_t stream);
+int64_t ptmi_tcn_norm_workspace_elems(int64_t B, int64_t T, int32_t C);
+int ptmi_tcn_norm_stats(const float* x, float* stats, double* workspace, int64_t B, int64_t T, int32_t C, int32_t rows, float eps,
+                        ptmi_stream_t stream);
+int ptmi_tcn_norm_apply(const float* x, const float* stats, const float* gamma, const float* beta, float* y, int64_t B, int64_t T,
+                        int32_t C, int32_t rows, ptmi_stream_t stream);
+int ptmi_tcn_norm_backward(const float* gy, const float* x, const float* stats, const float* gamma, float* dx, float* dparams,
+                           float* gsum, double* workspace, int64_t B, int64_t T, int32_t C, int32_t rows, ptmi_stream_t stream);
+
 /* ---- Dense layers: fp32 GEMM on the 16-bit matrix cores (split operands) --------------------------
  * Replaces the library GEMMs behind torch.nn.LSTM's input projections and torch.nn.Linear in
  * padertorch/contrib/examples/source_separation/pit/model.py:60-66,97-104 and contrib/tcl/dc.py:32-40,61-66

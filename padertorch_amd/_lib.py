@@ -73,6 +73,13 @@ SIGNATURES = {
                                                 c_int64, _P]),
     'ptmi_tas_wgrad_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int64]),
     'ptmi_tas_wgrad': (c_int, [_P, _P, _P, _P, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, _P, _P, _P]),
+    'ptmi_tcn_depthwise_workspace_elems': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    'ptmi_tcn_depthwise_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_float, _P]),
+    'ptmi_tcn_depthwise_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P]),
+    'ptmi_tcn_norm_workspace_elems': (c_int64, [c_int64, c_int64, c_int32]),
+    'ptmi_tcn_norm_stats': (c_int, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_float, _P]),
+    'ptmi_tcn_norm_apply': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P]),
+    'ptmi_tcn_norm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P]),
     'ptmi_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_unit_norm_forward': (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),

@@ -243,6 +243,95 @@ def tas_wgrad(g, mask, gate, x, stride, window_length):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ Conv-TasNet block (channels last)
+def _tcn_dims(x, channels_of=None):
+    assert x.dim() == 3 and x.is_contiguous() and x.dtype == torch.float32, (x.shape, x.stride(), x.dtype)
+    B, T, C = x.shape
+    assert channels_of is None or channels_of.shape[0] == C, (x.shape, channels_of.shape)
+    return B, T, C
+
+
+def _doubles(n, device):
+    return torch.empty(int(n), dtype=torch.float64, device=device)
+
+
+@_register('tcn_depthwise_forward(Tensor u, Tensor slope_in, Tensor weight, Tensor? bias, Tensor slope_out, int dilation, float eps) '
+           '-> (Tensor, Tensor)')
+def tcn_depthwise_forward(u, slope_in, weight, bias, slope_out, dilation, eps):
+    """``u [B, T, H]``, ``weight [H, (1,) K]`` -> ``(v [B, T, H], stats [B, 2])``: ``v = prelu(conv(pad(prelu(u))))`` and the per-example
+    ``(mean, rstd)`` of ``v`` (``ptmi_tcn_depthwise_forward``)."""
+    lib = _lib.load()
+    B, T, H = _tcn_dims(u, weight)
+    K = weight.numel() // H
+    assert weight.is_contiguous() and slope_in.numel() == 1 and slope_out.numel() == 1 and (bias is None or bias.is_contiguous())
+    v = torch.empty_like(u)
+    stats = torch.empty((B, 2), dtype=torch.float32, device=u.device)
+    ws = _doubles(lib.ptmi_tcn_depthwise_workspace_elems(B, T, H, K), u.device)
+    _lib.check(_lib.timed('tcn_depthwise_forward', lib.ptmi_tcn_depthwise_forward, u.data_ptr(), slope_in.data_ptr(), weight.data_ptr(),
+                          _lib.ptr(bias), slope_out.data_ptr(), v.data_ptr(), stats.data_ptr(), ws.data_ptr(), B, T, H, K, dilation, eps,
+                          _lib.stream(u.device)), 'ptmi_tcn_depthwise_forward')
+    return v, stats
+
+
+@_register('tcn_depthwise_backward(Tensor gv, Tensor u, Tensor slope_in, Tensor weight, Tensor? bias, Tensor slope_out, int dilation) '
+           '-> (Tensor, Tensor)')
+def tcn_depthwise_backward(gv, u, slope_in, weight, bias, slope_out, dilation):
+    """``(gu [B, T, H], dparams [H K + H + 2])``: ``d weight | d bias | d slope_in | d slope_out`` (``ptmi_tcn_depthwise_backward``)."""
+    lib = _lib.load()
+    B, T, H = _tcn_dims(u, weight)
+    K = weight.numel() // H
+    assert gv.shape == u.shape and gv.is_contiguous() and weight.is_contiguous()
+    gz, gu = torch.empty_like(u), torch.empty_like(u)
+    dparams = torch.empty(H * K + H + 2, dtype=torch.float32, device=u.device)
+    ws = _doubles(lib.ptmi_tcn_depthwise_workspace_elems(B, T, H, K), u.device)
+    _lib.check(_lib.timed('tcn_depthwise_backward', lib.ptmi_tcn_depthwise_backward, gv.data_ptr(), u.data_ptr(), slope_in.data_ptr(),
+                          weight.data_ptr(), _lib.ptr(bias), slope_out.data_ptr(), gz.data_ptr(), gu.data_ptr(), dparams.data_ptr(),
+                          ws.data_ptr(), B, T, H, K, dilation, _lib.stream(u.device)), 'ptmi_tcn_depthwise_backward')
+    return gu, dparams
+
+
+@_register('tcn_norm_stats(Tensor x, bool rows, float eps) -> Tensor')
+def tcn_norm_stats(x, rows, eps):
+    """``(mean, rstd)`` of ``x [B, T, C]`` per example ``[B, 2]`` or, ``rows``, per row ``[B T, 2]`` (``ptmi_tcn_norm_stats``)."""
+    lib = _lib.load()
+    B, T, C = _tcn_dims(x)
+    stats = torch.empty((B * T if rows else B, 2), dtype=torch.float32, device=x.device)
+    ws = None if rows else _doubles(lib.ptmi_tcn_norm_workspace_elems(B, T, C), x.device)
+    _lib.check(_lib.timed('tcn_norm_stats', lib.ptmi_tcn_norm_stats, x.data_ptr(), stats.data_ptr(), _lib.ptr(ws), B, T, C, int(rows), eps,
+                          _lib.stream(x.device)), 'ptmi_tcn_norm_stats')
+    return stats
+
+
+@_register('tcn_norm_apply(Tensor x, Tensor stats, Tensor gamma, Tensor beta, bool rows) -> Tensor')
+def tcn_norm_apply(x, stats, gamma, beta, rows):
+    """``gamma[c] (x - mean_g) rstd_g + beta[c]`` with ``stats [G, 2]`` from ``tcn_norm_stats`` / ``tcn_depthwise_forward``
+    (``ptmi_tcn_norm_apply``)."""
+    B, T, C = _tcn_dims(x)
+    assert stats.shape == (B * T if rows else B, 2) and stats.is_contiguous() and stats.dtype == torch.float32, stats.shape
+    assert gamma.numel() == C and beta.numel() == C and gamma.is_contiguous() and beta.is_contiguous()
+    y = torch.empty_like(x)
+    _lib.check(_lib.timed('tcn_norm_apply', _lib.load().ptmi_tcn_norm_apply, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
+                          beta.data_ptr(), y.data_ptr(), B, T, C, int(rows), _lib.stream(x.device)), 'ptmi_tcn_norm_apply')
+    return y
+
+
+@_register('tcn_norm_backward(Tensor gy, Tensor x, Tensor stats, Tensor gamma, bool rows) -> (Tensor, Tensor)')
+def tcn_norm_backward(gy, x, stats, gamma, rows):
+    """``(dx [B, T, C], dparams [2 C])``: ``d gamma | d beta`` (``ptmi_tcn_norm_backward``)."""
+    lib = _lib.load()
+    B, T, C = _tcn_dims(x)
+    assert gy.shape == x.shape and gy.is_contiguous() and gamma.numel() == C and gamma.is_contiguous()
+    assert stats.shape == (B * T if rows else B, 2) and stats.is_contiguous(), stats.shape
+    dx = torch.empty_like(x)
+    dparams = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+    gsum = torch.empty_like(stats)
+    ws = _doubles(lib.ptmi_tcn_norm_workspace_elems(B, T, C), x.device)
+    _lib.check(_lib.timed('tcn_norm_backward', lib.ptmi_tcn_norm_backward, gy.data_ptr(), x.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
+                          dx.data_ptr(), dparams.data_ptr(), gsum.data_ptr(), ws.data_ptr(), B, T, C, int(rows), _lib.stream(x.device)),
+               'ptmi_tcn_norm_backward')
+    return dx, dparams
+
+
 # ------------------------------------------------------------------------------------------------ dense layers
 _ZERO_WORDS = {}
 
