@@ -396,8 +396,13 @@ __global__ __launch_bounds__(256) void tcn_norm_row_kernel(const TcnNormArgs A, 
 }
 
 // mode 0: y = gamma (x - mean) rstd + beta;  mode 1 (dx): y = rstd (gy gamma - gsum[0] - xhat gsum[1])
+// Contraction is off and the fused multiply-adds are written out: left to the compiler, <4> fused some of its packed lanes and not
+// others, so dx differed in its last bit between <1> and <4> and between neighbouring channels.  gy gamma is rounded before gsum[0] is
+// taken off, as it was rounded before it went into that mean: fused, a group of one element got the product's rounding residual
+// times rstd for its dx instead of 0.
 template <int V>
 __global__ __launch_bounds__(256) void tcn_norm_pointwise_kernel(const TcnNormArgs A, int mode) {
+#pragma clang fp contract(off)
     const int cx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int c0 = (blockIdx.y * 64 + cx) * V;
     if (c0 >= A.C) return;              // no barrier in this kernel
@@ -416,13 +421,13 @@ __global__ __launch_bounds__(256) void tcn_norm_pointwise_kernel(const TcnNormAr
         tcn_load<V>(A.x + row * A.C + c0, x);
         if (mode == 0) {
 #pragma unroll
-            for (int e = 0; e < V; ++e) o[e] = ga[e] * ((x[e] - m) * rs) + be[e];
+            for (int e = 0; e < V; ++e) o[e] = fmaf(ga[e], (x[e] - m) * rs, be[e]);
         } else {
             const float g1 = A.gsum[2 * g], g2 = A.gsum[2 * g + 1];
             float gy[V];
             tcn_load<V>(A.gy + row * A.C + c0, gy);
 #pragma unroll
-            for (int e = 0; e < V; ++e) o[e] = rs * ((gy[e] * ga[e] - g1) - ((x[e] - m) * rs) * g2);
+            for (int e = 0; e < V; ++e) o[e] = rs * fmaf(-((x[e] - m) * rs), g2, gy[e] * ga[e] - g1);
         }
         tcn_store<V>(A.y + row * A.C + c0, o);
     }
