@@ -488,6 +488,45 @@ int ptmi_tcn_norm_apply(const float* x, const float* stats, const float* gamma, 
 int ptmi_tcn_norm_backward(const float* gy, const float* x, const float* stats, const float* gamma, float* dx, float* dparams,
                            float* gsum, double* workspace, int64_t B, int64_t T, int32_t C, int32_t rows, ptmi_stream_t stream);
 
+/* ---- TasNet model: the glue between encoder, separator, output projection and decoder -----------------
+ * Replaces, in TasNet.forward (padertorch/contrib/examples/source_separation/tasnet/model.py:69-152), the examplewise LayerNorm
+ * with its rearranges, the output PReLU, chunk / stack / nonlinearity behind the output projection and the mean subtraction,
+ * forward and backward.  The coders' side is [B, N, E] (channels first, E frames innermost), the separator's [B, E, C]
+ * (channels last); fp32, contiguous.  No atomics; sums are fp64, their per-workgroup partials go to the caller's workspace
+ * (DOUBLES) and are added in ascending order by a second kernel (bit-reproducible); no allocation, no synchronisation
+ * (capturable).  B <= 65535.
+ *
+ * ptmi_tasnet_entry_norm_forward : y[b,e,:] = gamma (w[b,:,e] - mean) rstd + beta over the N channels of frame e (biased variance,
+ *   rstd = 1 / sqrt(var + eps)) for e < lengths[b], 0 (not beta) from there on; lengths [B] in DEVICE memory, int32 or
+ *   (lengths_int64 != 0) int64, clipped to [0, E], NULL: every frame is live.  stats [B E, 2] = (mean, rstd), (0, 0) on dead rows.
+ * ptmi_tasnet_entry_norm_backward: dw [B, N, E] = rstd (gy gamma - mean_n(gy gamma) - xhat mean_n(gy gamma xhat)) on live rows, 0 on
+ *   dead ones; dparams [2 N] = d gamma | d beta over the live rows.
+ * ptmi_tasnet_prelu_forward / _backward: y = x > 0 ? x : a x on n elements, a = slope[0] in device memory; gx = x > 0 ? g : a g,
+ *   dslope [1] = sum over x <= 0 of g x.
+ * ptmi_tasnet_mask_head_forward  : z [B, E, A + K N] -> m [K, B, N, E] = act(z[b, e, A + k N + n]) and, A > 0,
+ *   additional [B, A, E] = z[b, e, :A] (no activation).  activation: 0 sigmoid, 1 relu, 2 leaky_relu (0.01), 3 elu (alpha 1),
+ *   4 tanh, 5 identity.
+ * ptmi_tasnet_mask_head_backward : gz [B, E, A + K N] from gm, the saved OUTPUT m and g_additional (NULL: zeros).
+ * ptmi_tasnet_center : backward == 0: in [K, B, T_in] -> out [B, K, T_out] = in[k, b, t] - mean_{t < T_out} in[k, b, t] (T_out <= T_in);
+ *   backward != 0, its adjoint: in [B, K, T_out] -> out [K, B, T_in] = in - mean(in), zeros from T_out on.  K B <= 65535. */
+int64_t ptmi_tasnet_entry_norm_workspace_elems(int64_t B, int32_t N, int64_t E);
+int ptmi_tasnet_entry_norm_forward(const float* w, const float* gamma, const float* beta, const void* lengths, int32_t lengths_int64,
+                                   float* y, float* stats, int64_t B, int32_t N, int64_t E, float eps, ptmi_stream_t stream);
+int ptmi_tasnet_entry_norm_backward(const float* gy, const float* w, const float* stats, const float* gamma, const void* lengths,
+                                    int32_t lengths_int64, float* dw, float* dparams, double* workspace, int64_t B, int32_t N,
+                                    int64_t E, ptmi_stream_t stream);
+int64_t ptmi_tasnet_prelu_workspace_elems(int64_t n);
+int ptmi_tasnet_prelu_forward(const float* x, const float* slope, float* y, int64_t n, ptmi_stream_t stream);
+int ptmi_tasnet_prelu_backward(const float* g, const float* x, const float* slope, float* gx, float* dslope, double* workspace,
+                               int64_t n, ptmi_stream_t stream);
+int ptmi_tasnet_mask_head_forward(const float* z, float* m, float* additional, int64_t B, int64_t E, int32_t N, int32_t K, int32_t A,
+                                  int32_t activation, ptmi_stream_t stream);
+int ptmi_tasnet_mask_head_backward(const float* gm, const float* m, const float* g_additional, float* gz, int64_t B, int64_t E,
+                                   int32_t N, int32_t K, int32_t A, int32_t activation, ptmi_stream_t stream);
+int64_t ptmi_tasnet_center_workspace_elems(int64_t K, int64_t B, int64_t T_in, int64_t T_out);
+int ptmi_tasnet_center(const float* in, float* out, double* workspace, int64_t K, int64_t B, int64_t T_in, int64_t T_out,
+                       int32_t backward, ptmi_stream_t stream);
+
 /* ---- Dense layers: fp32 GEMM on the 16-bit matrix cores (split operands) --------------------------
  * Replaces the library GEMMs behind torch.nn.LSTM's input projections and torch.nn.Linear in
  * padertorch/contrib/examples/source_separation/pit/model.py:60-66,97-104 and contrib/tcl/dc.py:32-40,61-66

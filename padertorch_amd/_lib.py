@@ -80,6 +80,16 @@ SIGNATURES = {
     'ptmi_tcn_norm_stats': (c_int, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_float, _P]),
     'ptmi_tcn_norm_apply': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P]),
     'ptmi_tcn_norm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P]),
+    'ptmi_tasnet_entry_norm_workspace_elems': (c_int64, [c_int64, c_int32, c_int64]),
+    'ptmi_tasnet_entry_norm_forward': (c_int, [_P, _P, _P, _P, c_int32, _P, _P, c_int64, c_int32, c_int64, c_float, _P]),
+    'ptmi_tasnet_entry_norm_backward': (c_int, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
+    'ptmi_tasnet_prelu_workspace_elems': (c_int64, [c_int64]),
+    'ptmi_tasnet_prelu_forward': (c_int, [_P, _P, _P, c_int64, _P]),
+    'ptmi_tasnet_prelu_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, _P]),
+    'ptmi_tasnet_mask_head_forward': (c_int, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
+    'ptmi_tasnet_mask_head_backward': (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
+    'ptmi_tasnet_center_workspace_elems': (c_int64, [c_int64, c_int64, c_int64, c_int64]),
+    'ptmi_tasnet_center': (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int32, _P]),
     'ptmi_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_unit_norm_forward': (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),

@@ -22,6 +22,9 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.grad_norm, torch.ops.ptmi.adam_flat_  ptmi_grad_norm, ptmi_adam_flat (train/optimizer.py:27-42, trainer.py:512-532)
     torch.ops.ptmi.tas_analysis / tas_synthesis / tas_masked_decode_backward / tas_wgrad   ptmi_tas_*
                                                                               (tasnet/tas_coders.py:9-135, tasnet/model.py:119-129)
+    torch.ops.ptmi.tcn_depthwise_forward / _backward, tcn_norm_stats / _apply / _backward   ptmi_tcn_*   (modules/convnet.py:114-161)
+    torch.ops.ptmi.tasnet_entry_norm_forward / _backward, tasnet_prelu_forward / _backward, tasnet_mask_head_forward / _backward,
+    torch.ops.ptmi.tasnet_center           ptmi_tasnet_*                      (tasnet/model.py:86-142)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -330,6 +333,122 @@ def tcn_norm_backward(gy, x, stats, gamma, rows):
                           dx.data_ptr(), dparams.data_ptr(), gsum.data_ptr(), ws.data_ptr(), B, T, C, int(rows), _lib.stream(x.device)),
                'ptmi_tcn_norm_backward')
     return dx, dparams
+
+
+# ------------------------------------------------------------------------------------------------ TasNet glue (csrc/tasnet.hip)
+#: the activation codes of ptmi_tasnet_mask_head_*
+TASNET_ACTIVATIONS = {'sigmoid': 0, 'relu': 1, 'leaky_relu': 2, 'elu': 3, 'tanh': 4, 'identity': 5}
+
+
+def _f32c(*tensors):
+    for t in tensors:
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32), (t.shape, t.stride(), t.dtype)
+
+
+def _lengths(lengths, B):
+    if lengths is None:
+        return None, 0
+    assert lengths.dtype in (torch.int32, torch.int64) and lengths.shape == (B,) and lengths.is_contiguous() and lengths.is_cuda, \
+        (lengths.dtype, lengths.shape, lengths.device)
+    return lengths, int(lengths.dtype == torch.int64)
+
+
+@_register('tasnet_entry_norm_forward(Tensor w, Tensor gamma, Tensor beta, Tensor? lengths, float eps) -> (Tensor, Tensor)')
+def tasnet_entry_norm_forward(w, gamma, beta, lengths, eps):
+    """``w [B, N, E]`` -> ``(y [B, E, N], stats [B E, 2])``: the layer norm over the channels of every frame below ``lengths[b]``,
+    zeros from there on (``ptmi_tasnet_entry_norm_forward``)."""
+    _f32c(w, gamma, beta)
+    B, N, E = w.shape
+    assert gamma.numel() == N and beta.numel() == N
+    lengths, is64 = _lengths(lengths, B)
+    y = torch.empty((B, E, N), dtype=torch.float32, device=w.device)
+    stats = torch.empty((B * E, 2), dtype=torch.float32, device=w.device)
+    _lib.check(_lib.timed('tasnet_entry_norm_forward', _lib.load().ptmi_tasnet_entry_norm_forward, w.data_ptr(), gamma.data_ptr(),
+                          beta.data_ptr(), _lib.ptr(lengths), is64, y.data_ptr(), stats.data_ptr(), B, N, E, eps, _lib.stream(w.device)),
+               'ptmi_tasnet_entry_norm_forward')
+    return y, stats
+
+
+@_register('tasnet_entry_norm_backward(Tensor gy, Tensor w, Tensor stats, Tensor gamma, Tensor? lengths) -> (Tensor, Tensor)')
+def tasnet_entry_norm_backward(gy, w, stats, gamma, lengths):
+    """``(dw [B, N, E], dparams [2 N])``: ``d gamma | d beta`` (``ptmi_tasnet_entry_norm_backward``)."""
+    lib = _lib.load()
+    _f32c(gy, w, stats, gamma)
+    B, N, E = w.shape
+    assert gy.shape == (B, E, N) and stats.shape == (B * E, 2) and gamma.numel() == N
+    lengths, is64 = _lengths(lengths, B)
+    dw = torch.empty_like(w)
+    dparams = torch.empty(2 * N, dtype=torch.float32, device=w.device)
+    ws = _doubles(lib.ptmi_tasnet_entry_norm_workspace_elems(B, N, E), w.device)
+    _lib.check(_lib.timed('tasnet_entry_norm_backward', lib.ptmi_tasnet_entry_norm_backward, gy.data_ptr(), w.data_ptr(), stats.data_ptr(),
+                          gamma.data_ptr(), _lib.ptr(lengths), is64, dw.data_ptr(), dparams.data_ptr(), ws.data_ptr(), B, N, E,
+                          _lib.stream(w.device)), 'ptmi_tasnet_entry_norm_backward')
+    return dw, dparams
+
+
+@_register('tasnet_prelu_forward(Tensor x, Tensor slope) -> Tensor')
+def tasnet_prelu_forward(x, slope):
+    """``x > 0 ? x : slope x`` with one slope in device memory (``ptmi_tasnet_prelu_forward``)."""
+    _f32c(x, slope)
+    assert slope.numel() == 1
+    y = torch.empty_like(x)
+    _lib.check(_lib.timed('tasnet_prelu_forward', _lib.load().ptmi_tasnet_prelu_forward, x.data_ptr(), slope.data_ptr(), y.data_ptr(),
+                          x.numel(), _lib.stream(x.device)), 'ptmi_tasnet_prelu_forward')
+    return y
+
+
+@_register('tasnet_prelu_backward(Tensor g, Tensor x, Tensor slope) -> (Tensor, Tensor)')
+def tasnet_prelu_backward(g, x, slope):
+    """``(gx, dslope [1])`` (``ptmi_tasnet_prelu_backward``)."""
+    lib = _lib.load()
+    _f32c(g, x, slope)
+    assert g.shape == x.shape and slope.numel() == 1
+    gx = torch.empty_like(x)
+    dslope = torch.empty(1, dtype=torch.float32, device=x.device)
+    ws = _doubles(lib.ptmi_tasnet_prelu_workspace_elems(x.numel()), x.device)
+    _lib.check(_lib.timed('tasnet_prelu_backward', lib.ptmi_tasnet_prelu_backward, g.data_ptr(), x.data_ptr(), slope.data_ptr(),
+                          gx.data_ptr(), dslope.data_ptr(), ws.data_ptr(), x.numel(), _lib.stream(x.device)), 'ptmi_tasnet_prelu_backward')
+    return gx, dslope
+
+
+@_register('tasnet_mask_head_forward(Tensor z, int K, int N, int A, int activation) -> (Tensor, Tensor)')
+def tasnet_mask_head_forward(z, K, N, A, activation):
+    """``z [B, E, A + K N]`` -> ``(m [K, B, N, E], additional [B, A, E])`` (``ptmi_tasnet_mask_head_forward``)."""
+    _f32c(z)
+    B, E, C = z.shape
+    assert C == A + K * N, (z.shape, K, N, A)
+    m = torch.empty((K, B, N, E), dtype=torch.float32, device=z.device)
+    add = torch.empty((B, A, E), dtype=torch.float32, device=z.device)
+    _lib.check(_lib.timed('tasnet_mask_head_forward', _lib.load().ptmi_tasnet_mask_head_forward, z.data_ptr(), m.data_ptr(),
+                          add.data_ptr() if A else None, B, E, N, K, A, activation, _lib.stream(z.device)), 'ptmi_tasnet_mask_head_forward')
+    return m, add
+
+
+@_register('tasnet_mask_head_backward(Tensor gm, Tensor m, Tensor? g_additional, int A, int activation) -> Tensor')
+def tasnet_mask_head_backward(gm, m, g_additional, A, activation):
+    """``gz [B, E, A + K N]`` from the gradients of both outputs and the saved ``m`` (``ptmi_tasnet_mask_head_backward``)."""
+    _f32c(gm, m, g_additional)
+    K, B, N, E = m.shape
+    assert gm.shape == m.shape and (g_additional is None or g_additional.shape == (B, A, E))
+    gz = torch.empty((B, E, A + K * N), dtype=torch.float32, device=m.device)
+    _lib.check(_lib.timed('tasnet_mask_head_backward', _lib.load().ptmi_tasnet_mask_head_backward, gm.data_ptr(), m.data_ptr(),
+                          _lib.ptr(g_additional) if A else None, gz.data_ptr(), B, E, N, K, A, activation, _lib.stream(m.device)),
+               'ptmi_tasnet_mask_head_backward')
+    return gz
+
+
+@_register('tasnet_center(Tensor x, int K, int B, int T_in, int T_out, bool backward) -> Tensor')
+def tasnet_center(x, K, B, T_in, T_out, backward):
+    """``x [K, B, T_in]`` -> ``[B, K, T_out]`` with the mean over ``T_out`` taken off, or (``backward``) the adjoint ``[B, K, T_out]``
+    -> ``[K, B, T_in]`` (``ptmi_tasnet_center``)."""
+    lib = _lib.load()
+    _f32c(x)
+    assert x.shape == ((B, K, T_out) if backward else (K, B, T_in)), (x.shape, K, B, T_in, T_out, backward)
+    out = torch.empty((K, B, T_in) if backward else (B, K, T_out), dtype=torch.float32, device=x.device)
+    ws = _doubles(lib.ptmi_tasnet_center_workspace_elems(K, B, T_in, T_out), x.device)
+    _lib.check(_lib.timed('tasnet_center', lib.ptmi_tasnet_center, x.data_ptr(), out.data_ptr(), ws.data_ptr(), K, B, T_in, T_out,
+                          int(backward), _lib.stream(x.device)), 'ptmi_tasnet_center')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ dense layers

@@ -1,5 +1,5 @@
-"""Image helpers of the review step, same call signatures as the reference
-(``padertorch/summary/tbx_utils.py:61-157,219-271``):
+"""Helpers of the review step, same call signatures as the reference
+(``padertorch/summary/tbx_utils.py:61-157,219-315,400-459``):
 
     mask_to_image(mask, batch_first=False, color=None, origin='lower')
     stft_to_image(signal, batch_first=False, color='viridis', origin='lower', visible_dB=50)
@@ -8,13 +8,17 @@
 All three return ``(channels, features, frames)`` arrays for tensorboard: one uint8 channel when ``color`` is
 ``None``, the RGBA floats of the matplotlib colour map otherwise (grayscale with a warning when matplotlib is
 missing).  They copy their input to the host, so the models only call them when ``create_snapshot`` is set.
+
+    audio(signal, sampling_rate=16000, batch_first=False, normalize=True) -> (samples, sampling_rate)
+    review_dict(*, loss=None, losses=None, scalars=None, histograms=None, audios=None, images=None, figures=None, texts=None)
 """
+import operator
 import warnings
 
 import numpy as np
 import torch
 
-__all__ = ['mask_to_image', 'stft_to_image', 'spectrogram_to_image']
+__all__ = ['mask_to_image', 'stft_to_image', 'spectrogram_to_image', 'audio', 'review_dict']
 
 _CMAPS = {}
 
@@ -83,3 +87,31 @@ def stft_to_image(signal, batch_first=False, color='viridis', origin='lower', vi
     s = _host(signal)
     return spectrogram_to_image(s.real ** 2 + s.imag ** 2, batch_first=batch_first, color=color, origin=origin,
                                 visible_dB=visible_dB)
+
+
+def audio(signal, sampling_rate: int = 16000, batch_first: bool = False, normalize: bool = True):
+    """A time signal ``(samples, batch [optional])`` - ``(batch [optional], samples)`` with ``batch_first`` - as the tuple
+    ``(samples of the first example, sampling_rate)`` tensorboardX takes; ``normalize``: scaled to a maximum amplitude of 0.95."""
+    a = _host(signal)
+    if a.dtype.kind == 'c':
+        raise ValueError(f'Complex datatype ({a.dtype}) is not supported for audio.')
+    if a.ndim == 2:
+        if batch_first is None:
+            raise ValueError(f'The array still has a batch axis but batch_first is None. Shape: {a.shape}')
+        a = a[0] if batch_first else a[:, 0]
+    elif a.ndim != 1:
+        raise ValueError('Either the signal has ndim 1 or 2', a.shape)
+    if normalize:
+        denominator = np.max(np.abs(a))
+        if denominator > 0:
+            a = a / denominator
+            a *= 0.95
+    return a, sampling_rate
+
+
+def review_dict(*, loss=None, losses=None, scalars=None, histograms=None, audios=None, images=None, figures=None, texts=None):
+    """The review dict from its parts: the arguments that are not None, under their names.  Exactly one of ``loss`` (a scalar tensor)
+    and ``losses`` (a dict of them) has to be given."""
+    review = {k: v for k, v in locals().items() if v is not None}
+    assert operator.xor(loss is None, losses is None), (loss, losses)
+    return review
