@@ -527,6 +527,49 @@ int64_t ptmi_tasnet_center_workspace_elems(int64_t K, int64_t B, int64_t T_in, i
 int ptmi_tasnet_center(const float* in, float* out, double* workspace, int64_t K, int64_t B, int64_t T_in, int64_t T_out,
                        int32_t backward, ptmi_stream_t stream);
 
+/* ---- One-and-Rest PIT: loss and flag head ------------------------------------------------------------
+ * Replaces, in padertorch/contrib/examples/source_separation/or_pit/model.py, the loss loop of review (:319-350: B x iterations x K
+ * calls of log_mse_loss on slices through one_and_rest_permutation_invariant_loss, :58-98, with fill_missing_with_zeros=True) and
+ * the flag head (:187-218: rearrange, Linear, (weighted) mean, sigmoid), forward and backward.  fp32 data, fp64 sums of exact
+ * products; no atomics, per-workgroup partials in the caller's workspace (DOUBLES) added in ascending order by a second kernel
+ * (bit-reproducible); no allocation, no synchronisation (capturable).  batch <= 65535.
+ *
+ * ptmi_td_rect_stats  : est [batch, M, T], tgt [batch, K, T] (time contiguous; strides[4] = {est_b, est_m, tgt_b, tgt_k} in
+ *   elements, HOST array) -> stats [batch, M K + M] float64 = C[m][j] = sum e_m t_j | See[m] = sum e_m^2 and, gram != NULL,
+ *   gram [batch, K, K] = sum t_j t_l (it does not depend on est: once per step).  0 <= K <= 8 (tgt may be NULL for K == 0),
+ *   1 <= M <= 8.  workspace: ptmi_td_rect_workspace_elems(batch, M, K, T) float64.
+ * ptmi_orpit_select   : one iteration's loss per example from stats (M = 2) and gram, n = T samples.  alive_in [batch, K] int32
+ *   marks the targets not yet chosen, R their number.  R >= 2: the candidates i (alive) are
+ *   log10(mse(e_0, t_i)) + 1 / (R - 1) log10(mse(e_1, sum_{j alive, j != i} t_j)), mse = (See - 2 Set + Stt) / n; the first minimum
+ *   in ascending i wins (a NaN candidate wins over numbers, as torch.min).  R == 1: log10(mse(e_0, t_alive)) + log10(See_1 / n).
+ *   R == 0: log10(See_0 / n) + log10(See_1 / n).  Outputs: loss [batch] fp32, choice [batch] int32 (-1: none), alive_out (may be
+ *   alive_in) and the coefficients of d loss / d e_m = a[m] e_m + sum_j bmat[m][j] t_j: coef_a [batch, 2], coef_b [batch, 2, K]
+ *   (a_m = 2 w_m / (ln 10 SSE_m), w_0 = 1, w_1 = 1 / (R - 1) or 1; bmat[m][j] = -a_m on row m's target set, else 0).
+ * ptmi_td_rect_lincomb: out[b,m,t] = g[b] (coef_a[b,m] est[b,m,t] + sum_j coef_b[b,m,j] tgt[b,j,t]); g [batch] or NULL (= 1);
+ *   strides[6] = {est_b, est_m, tgt_b, tgt_k, out_b, out_m}.
+ * ptmi_orpit_flag_forward : additional [B, A, E], weight [A], bias [1] -> pre[b,e] = bias + sum_a weight[a] additional[b,a,e] and
+ *   flag[b] = sigmoid(sum_e pre w / sum_e w).  weighted == 0: w = 1 (the mean; mask, encoded, w unused).  weighted != 0:
+ *   w[b,e] = mean_n (mask[k,b,n,e] encoded[b,n,e])^2 with mask [K, B, N, E], encoded [B, N, E] or NULL (the mask IS the
+ *   estimate); w [B, E] is stored for the backward pass.  No epsilon: a silent stream gives 0 / 0.
+ *   stat [B, 2] float64 = (sum pre w / sum w, sum w).  workspace: ptmi_orpit_flag_workspace_elems(B, A, E) float64.
+ * ptmi_orpit_flag_backward: from gflag [B] and gpre [B, E] (or NULL): dadditional [B, A, E], dparams [A + 1] = d weight | d bias
+ *   and, weighted, dmask [K, B, N, E] (zeros on the slices other than k) and dencoded [B, N, E] (encoded given). */
+int64_t ptmi_td_rect_workspace_elems(int64_t batch, int32_t M, int32_t K, int64_t T);
+int ptmi_td_rect_stats(const float* est, const float* tgt, int64_t batch, int32_t M, int32_t K, int64_t T, const int64_t* strides,
+                       double* workspace, double* stats, double* gram, ptmi_stream_t stream);
+int ptmi_orpit_select(const double* stats, const double* gram, const int32_t* alive_in, int32_t* alive_out, float* loss,
+                      int32_t* choice, float* coef_a, float* coef_b, int64_t batch, int32_t K, int64_t n, ptmi_stream_t stream);
+int ptmi_td_rect_lincomb(const float* est, const float* tgt, const float* g, const float* coef_a, const float* coef_b, int64_t batch,
+                         int32_t M, int32_t K, int64_t T, const int64_t* strides, float* out, ptmi_stream_t stream);
+int64_t ptmi_orpit_flag_workspace_elems(int64_t B, int32_t A, int64_t E);
+int ptmi_orpit_flag_forward(const float* additional, const float* weight, const float* bias, const float* mask, const float* encoded,
+                            float* pre, float* w, float* flag, double* stat, double* workspace, int64_t B, int32_t A, int64_t E,
+                            int32_t N, int32_t K, int32_t k, int32_t weighted, ptmi_stream_t stream);
+int ptmi_orpit_flag_backward(const float* gflag, const float* gpre, const float* flag, const double* stat, const float* pre, const float* w,
+                             const float* additional, const float* weight, const float* mask, const float* encoded, float* dadditional,
+                             float* dparams, float* dmask, float* dencoded, double* workspace, int64_t B, int32_t A, int64_t E, int32_t N,
+                             int32_t K, int32_t k, int32_t weighted, ptmi_stream_t stream);
+
 /* ---- Dense layers: fp32 GEMM on the 16-bit matrix cores (split operands) --------------------------
  * Replaces the library GEMMs behind torch.nn.LSTM's input projections and torch.nn.Linear in
  * padertorch/contrib/examples/source_separation/pit/model.py:60-66,97-104 and contrib/tcl/dc.py:32-40,61-66

@@ -90,6 +90,15 @@ SIGNATURES = {
     'ptmi_tasnet_mask_head_backward': (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_tasnet_center_workspace_elems': (c_int64, [c_int64, c_int64, c_int64, c_int64]),
     'ptmi_tasnet_center': (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int32, _P]),
+    'ptmi_td_rect_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int64]),
+    'ptmi_td_rect_stats': (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int64, _I64P, _P, _P, _P, _P]),
+    'ptmi_orpit_select': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
+    'ptmi_td_rect_lincomb': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int64, _I64P, _P, _P]),
+    'ptmi_orpit_flag_workspace_elems': (c_int64, [c_int64, c_int32, c_int64]),
+    'ptmi_orpit_flag_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                        c_int32, _P]),
+    'ptmi_orpit_flag_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32,
+                                         c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_unit_norm_forward': (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),

@@ -36,6 +36,9 @@ class TasNet(Model):
     #: also return ``encoded_out [B, K, E, N]`` (mask * encoded, or the estimate itself with ``mask=False``): the one tensor this path is
     #: built not to form, so it is made - in plain torch, differentiable - only on request (the reference's OR-PIT model reads it)
     return_encoded_out: bool = False
+    #: also return ``mask [K, B, N, E]``, the mask head's output as the decoder reads it (the estimate itself with ``mask=False``): no
+    #: copy.  The OR-PIT flag head's weighted modes read it together with ``encoded`` instead of ``encoded_out``
+    return_mask: bool = False
 
     def __init__(
             self,
@@ -132,6 +135,8 @@ class TasNet(Model):
         if self.return_encoded_out:
             estimate = encoded_raw.unsqueeze(0) * processed if self.mask else processed
             out['encoded_out'] = estimate.permute(1, 0, 3, 2)                                              # [B, K, E, N]
+        if self.return_mask:
+            out['mask'] = processed
         if self.additional_out_size > 0:
             out['additional_out'] = additional_out
         return out

@@ -18,3 +18,4 @@ from .tas import tas_encode, tas_decode, tas_masked_decode  # noqa: F401
 from . import tcn  # noqa: F401
 from .tcn import depthwise_prelu, channel_norm  # noqa: F401
 from . import tasnet  # noqa: F401
+from . import orpit  # noqa: F401

@@ -25,6 +25,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.tcn_depthwise_forward / _backward, tcn_norm_stats / _apply / _backward   ptmi_tcn_*   (modules/convnet.py:114-161)
     torch.ops.ptmi.tasnet_entry_norm_forward / _backward, tasnet_prelu_forward / _backward, tasnet_mask_head_forward / _backward,
     torch.ops.ptmi.tasnet_center           ptmi_tasnet_*                      (tasnet/model.py:86-142)
+    torch.ops.ptmi.td_rect_stats / td_rect_lincomb / orpit_select   ptmi_td_rect_*, ptmi_orpit_select   (or_pit/model.py:58-98,319-350)
+    torch.ops.ptmi.orpit_flag_forward / _backward  ptmi_orpit_flag_*          (or_pit/model.py:187-218)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -449,6 +451,120 @@ def tasnet_center(x, K, B, T_in, T_out, backward):
     _lib.check(_lib.timed('tasnet_center', lib.ptmi_tasnet_center, x.data_ptr(), out.data_ptr(), ws.data_ptr(), K, B, T_in, T_out,
                           int(backward), _lib.stream(x.device)), 'ptmi_tasnet_center')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ One-and-Rest PIT (csrc/orpit.hip)
+def _rows(x):
+    assert x.dim() == 3 and x.dtype == torch.float32 and (x.stride(2) == 1 or x.shape[2] == 1), (x.shape, x.stride(), x.dtype)
+    return x
+
+
+@_register('td_rect_stats(Tensor est, Tensor? tgt, bool want_gram) -> (Tensor, Tensor)')
+def td_rect_stats(est, tgt, want_gram):
+    """``est [B, M, T]``, ``tgt [B, K, T]`` (None: ``K = 0``; time contiguous, any batch / row strides) -> ``(stats [B, M K + M],
+    gram [B, K, K])`` float64: ``sum e_m t_j | sum e_m^2`` and, ``want_gram``, ``sum t_j t_l`` (else empty) (``ptmi_td_rect_stats``)."""
+    lib = _lib.load()
+    B, M, T = _rows(est).shape
+    K = 0 if tgt is None else _rows(tgt).shape[1]
+    assert tgt is None or (tgt.shape[0], tgt.shape[2]) == (B, T), (est.shape, tgt.shape)
+    stats = _doubles(B * (M * K + M), est.device).view(B, M * K + M)
+    gram = _doubles(B * K * K if want_gram else 0, est.device).view(B if want_gram else 0, K, K)
+    ws = _doubles(lib.ptmi_td_rect_workspace_elems(B, M, K, T), est.device)
+    strides = _lib.strides4(est.stride(0), est.stride(1), *((tgt.stride(0), tgt.stride(1)) if K else (0, 0)))
+    _lib.check(_lib.timed('td_rect_stats', lib.ptmi_td_rect_stats, est.data_ptr(), tgt.data_ptr() if K else None, B, M, K, T, strides,
+                          ws.data_ptr(), stats.data_ptr(), gram.data_ptr() if want_gram and K else None, _lib.stream(est.device)),
+               'ptmi_td_rect_stats')
+    return stats, gram
+
+
+@_register('orpit_select(Tensor stats, Tensor gram, Tensor alive, int n) -> (Tensor, Tensor, Tensor, Tensor, Tensor)')
+def orpit_select(stats, gram, alive, n):
+    """One OR-PIT iteration from ``td_rect_stats`` (``M = 2``): ``(loss [B] fp32, choice [B] int32, alive_out [B, K] int32, coef_a [B, 2],
+    coef_b [B, 2, K])`` (``ptmi_orpit_select``)."""
+    B, K = alive.shape
+    assert stats.shape == (B, 2 * K + 2) and stats.dtype == torch.float64 and stats.is_contiguous(), (stats.shape, stats.dtype)
+    assert alive.dtype == torch.int32 and alive.is_contiguous(), (alive.dtype, alive.stride())
+    assert K == 0 or (gram.shape == (B, K, K) and gram.dtype == torch.float64 and gram.is_contiguous()), (gram.shape, gram.dtype)
+    dev = stats.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    choice = torch.empty(B, dtype=torch.int32, device=dev)
+    alive_out = torch.empty_like(alive)
+    coef_a = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    coef_b = torch.empty((B, 2, K), dtype=torch.float32, device=dev)
+    none = (lambda t: t.data_ptr() if K else None)
+    _lib.check(_lib.timed('orpit_select', _lib.load().ptmi_orpit_select, stats.data_ptr(), none(gram), none(alive), none(alive_out),
+                          loss.data_ptr(), choice.data_ptr(), coef_a.data_ptr(), none(coef_b), B, K, n, _lib.stream(dev)), 'ptmi_orpit_select')
+    return loss, choice, alive_out, coef_a, coef_b
+
+
+@_register('td_rect_lincomb(Tensor est, Tensor? tgt, Tensor? g, Tensor coef_a, Tensor coef_b) -> Tensor')
+def td_rect_lincomb(est, tgt, g, coef_a, coef_b):
+    """``out[b, m] = g[b] (coef_a[b, m] est[b, m] + sum_j coef_b[b, m, j] tgt[b, j])`` as a contiguous ``[B, M, T]``
+    (``ptmi_td_rect_lincomb``)."""
+    B, M, T = _rows(est).shape
+    K = 0 if tgt is None else _rows(tgt).shape[1]
+    _f32c(g, coef_a, coef_b)
+    assert coef_a.shape == (B, M) and coef_b.shape == (B, M, K) and (g is None or g.shape == (B,)), (coef_a.shape, coef_b.shape)
+    out = torch.empty((B, M, T), dtype=torch.float32, device=est.device)
+    strides = _lib.strides6(est.stride(0), est.stride(1), *((tgt.stride(0), tgt.stride(1)) if K else (0, 0)), out.stride(0), out.stride(1))
+    _lib.check(_lib.timed('td_rect_lincomb', _lib.load().ptmi_td_rect_lincomb, est.data_ptr(), tgt.data_ptr() if K else None, _lib.ptr(g),
+                          coef_a.data_ptr(), coef_b.data_ptr() if K else None, B, M, K, T, strides, out.data_ptr(),
+                          _lib.stream(est.device)), 'ptmi_td_rect_lincomb')
+    return out
+
+
+def _flag_dims(additional, weight, bias, mask, encoded, k):
+    _f32c(additional, weight, bias, mask, encoded)
+    B, A, E = additional.shape
+    assert weight.numel() == A and (bias is None or bias.numel() == 1) and A >= 1, (additional.shape, weight.shape)
+    K = N = 0
+    if mask is not None:
+        K, _, N, _ = mask.shape
+        assert mask.shape == (K, B, N, E) and 0 <= k < K and (encoded is None or encoded.shape == (B, N, E)), \
+            (mask.shape, additional.shape, k, None if encoded is None else encoded.shape)
+    else:
+        assert encoded is None
+    return B, A, E, N, K
+
+
+@_register('orpit_flag_forward(Tensor additional, Tensor weight, Tensor bias, Tensor? mask, Tensor? encoded, int k) '
+           '-> (Tensor, Tensor, Tensor, Tensor)')
+def orpit_flag_forward(additional, weight, bias, mask, encoded, k):
+    """``(pre [B, E], flag [B], w [B, E] (empty without mask), stat [B, 2] float64)``; a ``mask [K, B, N, E]`` selects the weighted mean
+    with ``w = mean_n (mask[k] encoded)^2`` (``ptmi_orpit_flag_forward``)."""
+    lib = _lib.load()
+    B, A, E, N, K = _flag_dims(additional, weight, bias, mask, encoded, k)
+    dev = additional.device
+    pre = torch.empty((B, E), dtype=torch.float32, device=dev)
+    w = torch.empty((B, E) if K else (0,), dtype=torch.float32, device=dev)
+    flag = torch.empty(B, dtype=torch.float32, device=dev)
+    stat = _doubles(2 * B, dev).view(B, 2)
+    ws = _doubles(lib.ptmi_orpit_flag_workspace_elems(B, A, E), dev)
+    _lib.check(_lib.timed('orpit_flag_forward', lib.ptmi_orpit_flag_forward, additional.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                          _lib.ptr(mask), _lib.ptr(encoded), pre.data_ptr(), w.data_ptr() if K else None, flag.data_ptr(), stat.data_ptr(),
+                          ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev)), 'ptmi_orpit_flag_forward')
+    return pre, flag, w, stat
+
+
+@_register('orpit_flag_backward(Tensor gflag, Tensor? gpre, Tensor flag, Tensor stat, Tensor pre, Tensor w, Tensor additional, '
+           'Tensor weight, Tensor? mask, Tensor? encoded, int k) -> (Tensor, Tensor, Tensor?, Tensor?)')
+def orpit_flag_backward(gflag, gpre, flag, stat, pre, w, additional, weight, mask, encoded, k):
+    """``(d additional, dparams [A + 1] = d weight | d bias, d mask or None, d encoded or None)`` (``ptmi_orpit_flag_backward``)."""
+    lib = _lib.load()
+    B, A, E, N, K = _flag_dims(additional, weight, None, mask, encoded, k)
+    _f32c(gflag, gpre, flag, pre, w)
+    assert gflag.shape == (B,) and (gpre is None or gpre.shape == (B, E)) and pre.shape == (B, E) and stat.shape == (B, 2)
+    dev = additional.device
+    dadd = torch.empty_like(additional)
+    dparams = torch.empty(A + 1, dtype=torch.float32, device=dev)
+    dmask = torch.empty_like(mask) if K else None
+    denc = torch.empty_like(encoded) if encoded is not None else None
+    ws = _doubles(lib.ptmi_orpit_flag_workspace_elems(B, A, E), dev)
+    _lib.check(_lib.timed('orpit_flag_backward', lib.ptmi_orpit_flag_backward, gflag.data_ptr(), _lib.ptr(gpre), flag.data_ptr(),
+                          stat.data_ptr(), pre.data_ptr(), w.data_ptr() if K else None, additional.data_ptr(), weight.data_ptr(),
+                          _lib.ptr(mask), _lib.ptr(encoded), dadd.data_ptr(), dparams.data_ptr(), _lib.ptr(dmask), _lib.ptr(denc),
+                          ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev)), 'ptmi_orpit_flag_backward')
+    return dadd, dparams, dmask, denc
 
 
 # ------------------------------------------------------------------------------------------------ dense layers
