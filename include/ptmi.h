@@ -527,6 +527,61 @@ int64_t ptmi_tasnet_center_workspace_elems(int64_t K, int64_t B, int64_t T_in, i
 int ptmi_tasnet_center(const float* in, float* out, double* workspace, int64_t K, int64_t B, int64_t T_in, int64_t T_out,
                        int32_t backward, ptmi_stream_t stream);
 
+/* ---- Dual-path RNN separator ------------------------------------------------------------------------
+ * padertorch/modules/dual_path_rnn.py between its GEMMs.  The chunked activation is [B, S, K, N] (channels last, chunk-major); a
+ * "position" is a row (b, s, k) of it; fp32, contiguous unless strides are taken.  A sequence is (base row, step stride, step
+ * count): an int32 table [nseq][3] in DEVICE memory.  No atomics; sums over rows are fp64, per-slab partials in the caller's
+ * workspace (DOUBLES) added in ascending order by a second kernel (bit-reproducible); no allocation, no synchronisation (capturable).
+ *
+ * ptmi_dprnn_num_chunks : S of a signal of L frames: the K - P zero frames in front and behind, window K, hop P, end='pad'.
+ * ptmi_dprnn_tables     : chunks [B] = S_b = (len_b + (K - P) - 1) // P + 1 clipped to [0, S] (lengths [B] in DEVICE memory, int32 or
+ *   (lengths_int64 != 0) int64; NULL: S); intra [B S][3] = (row (b, s, 0), 1, s < S_b ? K : 0); inter [B K][3] = (row (b, 0, k), K, S_b).
+ *   B S K < 2^31.
+ * ptmi_chunk_lstm_forward : the time loop of one torch.nn.LSTM layer, ndir = 1 or 2 directions, over the table's sequences.  gates
+ *   [rows, ndir 4H] holds x W_ih^T + b_ih (direction-major, then i | f | g | o) and is OVERWRITTEN by the activated gates; h, c
+ *   [rows, ndir H] are written on the rows of the steps; h is 0 on rows base + t stride, count <= t < cap (cap: the steps a sequence
+ *   has room for); rows of no sequence are not touched.  A reverse direction starts at the sequence's own last step.  One workgroup
+ *   owns ptmi_chunk_lstm_tile() sequences of one direction; W_hh stays in registers for H <= ptmi_chunk_lstm_max_resident_hidden()
+ *   (128) and is streamed from the L2 every step above that, up to H = ptmi_chunk_lstm_max_hidden() (1536: the backward kernel
+ *   keeps d gates, dh and dc of its sequences in LDS, 96 H bytes of the 160 KB of a CU).
+ * ptmi_chunk_lstm_backward: gates holds the forward's output and is OVERWRITTEN by d gates (pre-activation), 0 on the rows between
+ *   count and cap; hprev [rows, ndir H] = h of the step before (0 at a first step and between count and cap): the operand of dW_hh.
+ * ptmi_dprnn_colsum     : out [C] = sum over rows of x [rows, C] (row stride ld); out2 (or NULL) receives the same sums.
+ * ptmi_dprnn_norm_residual_forward : y = (s < chunks[b] ? gamma (z - mean) rstd + beta : 0) + residual per row of z [rows, N],
+ *   rows = B S K, statistics over N (biased variance); chunks NULL: every row is valid.  stats [rows, 2] = (mean, rstd), (0, 0) on
+ *   invalid rows.
+ * ptmi_dprnn_norm_residual_backward: dz (0 on invalid rows), dresidual = gy, dparams [2 N] = d gamma | d beta.
+ * ptmi_dprnn_segment    : x [B, L, N] (strides {b, l, n} in elements, HOST array) -> seg [B, S, K, N],
+ *   seg[b, s, k] = x[b, s P + k - (K - P)] inside [0, L), 0 outside.
+ * ptmi_dprnn_overlap_add: seg [B, S, K, N] (strides {b, s, k, n}, HOST array) -> out [B, L_out, N]: the sum, chunks ascending, of the
+ *   elements of the padded signal's frame l + front (front = K - P: the frames of x, what segment maps frame l to - its adjoint,
+ *   and segment is the adjoint of this; front = 0: the padded signal, L_out up to (S - 1) P + K). */
+int64_t ptmi_dprnn_num_chunks(int64_t L, int32_t K, int32_t P);
+int ptmi_dprnn_tables(const void* lengths, int32_t lengths_int64, int32_t B, int32_t S, int32_t K, int32_t P, int32_t* chunks,
+                      int32_t* intra, int32_t* inter, ptmi_stream_t stream);
+int32_t ptmi_chunk_lstm_max_hidden(void);
+int32_t ptmi_chunk_lstm_max_resident_hidden(void);
+int32_t ptmi_chunk_lstm_tile(void);
+int ptmi_chunk_lstm_forward(float* gates, const float* w_hh, const float* w_hh_reverse, const float* b_hh, const float* b_hh_reverse,
+                            float* h, float* c, const int32_t* table, int32_t nseq, int32_t cap, int32_t H, int32_t ndir,
+                            ptmi_stream_t stream);
+int ptmi_chunk_lstm_backward(float* gates, const float* dh, const float* w_hh, const float* w_hh_reverse, const float* h, const float* c,
+                             float* hprev, const int32_t* table, int32_t nseq, int32_t cap, int32_t H, int32_t ndir,
+                             ptmi_stream_t stream);
+int64_t ptmi_dprnn_colsum_workspace_elems(int64_t rows, int32_t C);
+int ptmi_dprnn_colsum(const float* x, int64_t ld, float* out, float* out2, double* workspace, int64_t rows, int32_t C,
+                      ptmi_stream_t stream);
+int ptmi_dprnn_norm_residual_forward(const float* z, const float* residual, const float* gamma, const float* beta,
+                                     const int32_t* chunks, float* y, float* stats, int64_t rows, int32_t N, int32_t S, int32_t K,
+                                     float eps, ptmi_stream_t stream);
+int ptmi_dprnn_norm_residual_backward(const float* gy, const float* z, const float* stats, const float* gamma, const int32_t* chunks,
+                                      float* dz, float* dresidual, float* dparams, double* workspace, int64_t rows, int32_t N,
+                                      int32_t S, int32_t K, ptmi_stream_t stream);
+int ptmi_dprnn_segment(const float* x, const int64_t* x_strides, float* seg, int64_t B, int64_t L, int32_t N, int32_t S, int32_t K,
+                       int32_t P, ptmi_stream_t stream);
+int ptmi_dprnn_overlap_add(const float* seg, const int64_t* seg_strides, float* out, int64_t B, int64_t L_out, int32_t N, int32_t S,
+                           int32_t K, int32_t P, int32_t front, ptmi_stream_t stream);
+
 /* ---- One-and-Rest PIT: loss and flag head ------------------------------------------------------------
  * Replaces, in padertorch/contrib/examples/source_separation/or_pit/model.py, the loss loop of review (:319-350: B x iterations x K
  * calls of log_mse_loss on slices through one_and_rest_permutation_invariant_loss, :58-98, with fill_missing_with_zeros=True) and

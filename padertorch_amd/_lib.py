@@ -99,6 +99,19 @@ SIGNATURES = {
                                         c_int32, _P]),
     'ptmi_orpit_flag_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32,
                                          c_int32, c_int32, c_int32, _P]),
+    'ptmi_dprnn_num_chunks': (c_int64, [c_int64, c_int32, c_int32]),
+    'ptmi_dprnn_tables': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    'ptmi_chunk_lstm_max_hidden': (c_int32, []),
+    'ptmi_chunk_lstm_max_resident_hidden': (c_int32, []),
+    'ptmi_chunk_lstm_tile': (c_int32, []),
+    'ptmi_chunk_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    'ptmi_chunk_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    'ptmi_dprnn_colsum_workspace_elems': (c_int64, [c_int64, c_int32]),
+    'ptmi_dprnn_colsum': (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int32, _P]),
+    'ptmi_dprnn_norm_residual_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, _P]),
+    'ptmi_dprnn_norm_residual_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P]),
+    'ptmi_dprnn_segment': (c_int, [_P, _I64P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
+    'ptmi_dprnn_overlap_add': (c_int, [_P, _I64P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_unit_norm_forward': (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),

@@ -4,3 +4,5 @@ from .normalization import Normalization, InputNormalization, normalize  # noqa:
 from .recurrent import StatefulLSTM  # noqa: F401
 from . import convnet  # noqa: F401
 from .convnet import ConvNet  # noqa: F401
+from . import dual_path_rnn  # noqa: F401
+from .dual_path_rnn import DPRNN, DPRNNBlock, _ChunkRNN, segment, overlap_add  # noqa: F401

@@ -19,3 +19,4 @@ from . import tcn  # noqa: F401
 from .tcn import depthwise_prelu, channel_norm  # noqa: F401
 from . import tasnet  # noqa: F401
 from . import orpit  # noqa: F401
+from . import dprnn  # noqa: F401

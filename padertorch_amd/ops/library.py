@@ -27,6 +27,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.tasnet_center           ptmi_tasnet_*                      (tasnet/model.py:86-142)
     torch.ops.ptmi.td_rect_stats / td_rect_lincomb / orpit_select   ptmi_td_rect_*, ptmi_orpit_select   (or_pit/model.py:58-98,319-350)
     torch.ops.ptmi.orpit_flag_forward / _backward  ptmi_orpit_flag_*          (or_pit/model.py:187-218)
+    torch.ops.ptmi.dprnn_tables / chunk_lstm_forward / chunk_lstm_backward / dprnn_colsum / dprnn_colsum_pair / dprnn_norm_residual_forward / _backward /
+    torch.ops.ptmi.dprnn_segment / dprnn_overlap_add   ptmi_dprnn_*, ptmi_chunk_lstm_*   (modules/dual_path_rnn.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -923,3 +925,154 @@ def lstm_recurrence_backward(gates, c, c0, dhy, w_hh_t, bs_dev, offs_dev, bs_hos
                               w_hh_t.data_ptr(), dg.data_ptr(), dcs.data_ptr(), ctypes.c_void_p(bs_host), ctypes.c_void_p(offs_host),
                               T, max_batch, H, ndir, st), 'ptmi_lstm_backward')
     return dg, flags
+
+
+# ------------------------------------------------------------------------------------------------ dual-path RNN (csrc/dprnn.hip)
+def _i32c(*tensors):
+    for t in tensors:
+        assert t is None or (t.is_contiguous() and t.dtype == torch.int32 and t.is_cuda), (t.shape, t.stride(), t.dtype, t.device)
+
+
+@_register('dprnn_tables(Tensor like, Tensor? lengths, int B, int S, int K, int P) -> (Tensor, Tensor, Tensor)')
+def dprnn_tables(like, lengths, B, S, K, P):
+    """``(chunks [B], intra [B S, 3], inter [B K, 3])`` (int32) on ``like``'s device: the chunk counts ``S_b`` of ``lengths`` (frames,
+    device memory; None: ``S``) and the sequence tables of both paths (``ptmi_dprnn_tables``)."""
+    lengths, is64 = _lengths(lengths, B)
+    dev = like.device
+    chunks = torch.empty(B, dtype=torch.int32, device=dev)
+    intra = torch.empty((B * S, 3), dtype=torch.int32, device=dev)
+    inter = torch.empty((B * K, 3), dtype=torch.int32, device=dev)
+    _lib.check(_lib.timed('dprnn_tables', _lib.load().ptmi_dprnn_tables, _lib.ptr(lengths), is64, B, S, K, P, chunks.data_ptr(),
+                          intra.data_ptr(), inter.data_ptr(), _lib.stream(dev)), 'ptmi_dprnn_tables')
+    return chunks, intra, inter
+
+
+def _chunk_lstm_dims(gates, table, H):
+    _f32c(gates)
+    _i32c(table)
+    assert gates.dim() == 2 and table.dim() == 2 and table.shape[1] == 3 and gates.shape[1] % (4 * H) == 0, (gates.shape, table.shape, H)
+    ndir = gates.shape[1] // (4 * H)
+    assert ndir in (1, 2), gates.shape
+    return gates.shape[0], ndir
+
+
+@_register('chunk_lstm_forward(Tensor(a!) gates, Tensor w_hh, Tensor? w_hh_reverse, Tensor b_hh, Tensor? b_hh_reverse, Tensor table, '
+           'int cap, int H) -> (Tensor, Tensor)')
+def chunk_lstm_forward(gates, w_hh, w_hh_reverse, b_hh, b_hh_reverse, table, cap, H):
+    """The time loop of one LSTM layer over the sequences of ``table [nseq, 3]`` = (base row, step stride, step count): ``gates [rows,
+    ndir 4H]`` holds ``x W_ih^T + b_ih`` and becomes the activated gates; returns ``(h, c) [rows, ndir H]`` (``ptmi_chunk_lstm_forward``).
+    Every row ``base + t stride``, ``t < cap``, must lie inside ``rows``: the caller's tables guarantee it."""
+    rows, ndir = _chunk_lstm_dims(gates, table, H)
+    _f32c(w_hh, w_hh_reverse, b_hh, b_hh_reverse)
+    assert w_hh.shape == (4 * H, H) and b_hh.shape == (4 * H,) and (ndir == 1 or (w_hh_reverse.shape == (4 * H, H)
+                                                                                  and b_hh_reverse.shape == (4 * H,)))
+    h = torch.empty((rows, ndir * H), dtype=torch.float32, device=gates.device)
+    c = torch.empty((rows, ndir * H), dtype=torch.float32, device=gates.device)
+    _lib.check(_lib.timed(f'chunk_lstm_forward:{table.shape[0]}x{cap}x{H}', _lib.load().ptmi_chunk_lstm_forward, gates.data_ptr(),
+                          w_hh.data_ptr(), _lib.ptr(w_hh_reverse), b_hh.data_ptr(), _lib.ptr(b_hh_reverse), h.data_ptr(), c.data_ptr(),
+                          table.data_ptr(), table.shape[0], cap, H, ndir, _lib.stream(gates.device)), 'ptmi_chunk_lstm_forward')
+    return h, c
+
+
+@_register('chunk_lstm_backward(Tensor(a!) gates, Tensor dh, Tensor w_hh, Tensor? w_hh_reverse, Tensor h, Tensor c, Tensor table, '
+           'int cap, int H) -> Tensor')
+def chunk_lstm_backward(gates, dh, w_hh, w_hh_reverse, h, c, table, cap, H):
+    """``gates`` (the forward's activated gates) becomes ``d gates``; returns ``hprev [rows, ndir H]``, the ``h`` of every row's step
+    before (``ptmi_chunk_lstm_backward``)."""
+    rows, ndir = _chunk_lstm_dims(gates, table, H)
+    _f32c(dh, w_hh, w_hh_reverse, h, c)
+    assert dh.shape == h.shape == c.shape == (rows, ndir * H), (dh.shape, h.shape, c.shape)
+    hprev = torch.empty_like(h)
+    _lib.check(_lib.timed(f'chunk_lstm_backward:{table.shape[0]}x{cap}x{H}', _lib.load().ptmi_chunk_lstm_backward, gates.data_ptr(),
+                          dh.data_ptr(), w_hh.data_ptr(), _lib.ptr(w_hh_reverse), h.data_ptr(), c.data_ptr(), hprev.data_ptr(),
+                          table.data_ptr(), table.shape[0], cap, H, ndir, _lib.stream(gates.device)), 'ptmi_chunk_lstm_backward')
+    return hprev
+
+
+def _dprnn_colsum(x, twice):
+    lib = _lib.load()
+    assert x.dim() == 2 and x.dtype == torch.float32 and (x.stride(1) == 1 or x.shape[1] == 1), (x.shape, x.stride(), x.dtype)
+    rows, C = x.shape
+    out = torch.empty(C, dtype=torch.float32, device=x.device)
+    out2 = torch.empty(C, dtype=torch.float32, device=x.device) if twice else None
+    ws = _doubles(lib.ptmi_dprnn_colsum_workspace_elems(rows, C), x.device)
+    _lib.check(_lib.timed('dprnn_colsum', lib.ptmi_dprnn_colsum, x.data_ptr(), _ld(x), out.data_ptr(), _lib.ptr(out2), ws.data_ptr(), rows,
+                          C, _lib.stream(x.device)), 'ptmi_dprnn_colsum')
+    return out, out2
+
+
+@_register('dprnn_colsum(Tensor x) -> Tensor')
+def dprnn_colsum(x):
+    """``x [rows, C]`` (unit inner stride, any row stride) -> ``[C]``: the column sums, fp64 inside, in a fixed order (``ptmi_dprnn_colsum``)."""
+    return _dprnn_colsum(x, False)[0]
+
+
+@_register('dprnn_colsum_pair(Tensor x) -> (Tensor, Tensor)')
+def dprnn_colsum_pair(x):
+    """:func:`dprnn_colsum` into two tensors of the same content - the gradients of ``b_ih`` and ``b_hh`` - with one pass over the rows."""
+    return _dprnn_colsum(x, True)
+
+
+@_register('dprnn_norm_residual_forward(Tensor z, Tensor residual, Tensor gamma, Tensor beta, Tensor? chunks, int S, int K, float eps) '
+           '-> (Tensor, Tensor)')
+def dprnn_norm_residual_forward(z, residual, gamma, beta, chunks, S, K, eps):
+    """``z [B S K, N]`` -> ``(y, stats [rows, 2])``: the layer norm over ``N`` on the rows ``(b, s, k)`` with ``s < chunks[b]``, zeros on
+    the others, plus ``residual`` (``ptmi_dprnn_norm_residual_forward``)."""
+    _f32c(z, residual, gamma, beta)
+    _i32c(chunks)
+    rows, N = z.shape
+    assert residual.shape == z.shape and gamma.numel() == N and beta.numel() == N and rows % (S * K) == 0
+    assert chunks is None or chunks.numel() == rows // (S * K)
+    y = torch.empty_like(z)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=z.device)
+    _lib.check(_lib.timed('dprnn_norm_residual_forward', _lib.load().ptmi_dprnn_norm_residual_forward, z.data_ptr(), residual.data_ptr(),
+                          gamma.data_ptr(), beta.data_ptr(), _lib.ptr(chunks), y.data_ptr(), stats.data_ptr(), rows, N, S, K, eps,
+                          _lib.stream(z.device)), 'ptmi_dprnn_norm_residual_forward')
+    return y, stats
+
+
+@_register('dprnn_norm_residual_backward(Tensor gy, Tensor z, Tensor stats, Tensor gamma, Tensor? chunks, int S, int K) '
+           '-> (Tensor, Tensor, Tensor)')
+def dprnn_norm_residual_backward(gy, z, stats, gamma, chunks, S, K):
+    """``(dz, dresidual, dparams [2 N])``: ``d gamma | d beta`` over the valid rows (``ptmi_dprnn_norm_residual_backward``)."""
+    lib = _lib.load()
+    _f32c(gy, z, stats, gamma)
+    _i32c(chunks)
+    rows, N = z.shape
+    assert gy.shape == z.shape and stats.shape == (rows, 2) and gamma.numel() == N and rows % (S * K) == 0
+    dz, dres = torch.empty_like(z), torch.empty_like(z)
+    dparams = torch.empty(2 * N, dtype=torch.float32, device=z.device)
+    ws = _doubles(lib.ptmi_dprnn_colsum_workspace_elems(rows, N), z.device)
+    _lib.check(_lib.timed('dprnn_norm_residual_backward', lib.ptmi_dprnn_norm_residual_backward, gy.data_ptr(), z.data_ptr(),
+                          stats.data_ptr(), gamma.data_ptr(), _lib.ptr(chunks), dz.data_ptr(), dres.data_ptr(), dparams.data_ptr(),
+                          ws.data_ptr(), rows, N, S, K, _lib.stream(z.device)), 'ptmi_dprnn_norm_residual_backward')
+    return dz, dres, dparams
+
+
+@_register('dprnn_segment(Tensor x, int K, int P) -> Tensor')
+def dprnn_segment(x, K, P):
+    """``x [B, L, N]`` (any strides) -> ``[B, S, K, N]``: windows of ``K`` frames every ``P`` of the signal with ``K - P`` zero frames in
+    front and behind, the last window padded (``ptmi_dprnn_segment``)."""
+    lib = _lib.load()
+    assert x.dim() == 3 and x.dtype == torch.float32 and 1 <= P <= K, (x.shape, x.dtype, K, P)
+    B, L, N = x.shape
+    S = int(lib.ptmi_dprnn_num_chunks(L, K, P))
+    seg = torch.empty((B, S, K, N), dtype=torch.float32, device=x.device)
+    strides = (ctypes.c_int64 * 3)(*x.stride())
+    _lib.check(_lib.timed('dprnn_segment', lib.ptmi_dprnn_segment, x.data_ptr(), strides, seg.data_ptr(), B, L, N, S, K, P,
+                          _lib.stream(x.device)), 'ptmi_dprnn_segment')
+    return seg
+
+
+@_register('dprnn_overlap_add(Tensor seg, int P, int L_out, int front) -> Tensor')
+def dprnn_overlap_add(seg, P, L_out, front):
+    """``seg [B, S, K, N]`` (any strides) -> ``[B, L_out, N]``: frame ``l`` is the sum of the window elements that hold frame ``l +
+    front`` of the padded signal; ``front = K - P``: those :func:`dprnn_segment` copies frame ``l`` to (``ptmi_dprnn_overlap_add``);
+    ``L_out + front <= (S - 1) P + K``."""
+    assert seg.dim() == 4 and seg.dtype == torch.float32, (seg.shape, seg.dtype)
+    B, S, K, N = seg.shape
+    out = torch.empty((B, L_out, N), dtype=torch.float32, device=seg.device)
+    strides = (ctypes.c_int64 * 4)(*seg.stride())
+    _lib.check(_lib.timed('dprnn_overlap_add', _lib.load().ptmi_dprnn_overlap_add, seg.data_ptr(), strides, out.data_ptr(), B, L_out, N, S,
+                          K, P, front, _lib.stream(seg.device)), 'ptmi_dprnn_overlap_add')
+    return out
