@@ -53,9 +53,9 @@ class TasNet(Model):
     ):
         """
         Args:
-            encoder: ``TasEncoder``
+            encoder: ``TasEncoder`` or ``StftEncoder``
             separator: see the module's docstring
-            decoder: ``TasDecoder``
+            decoder: ``TasDecoder`` or ``IstftDecoder`` (anything with ``feature_size``, ``forward`` and ``masked``)
             mask: If `True`, use the output of the NN as a mask in tas domain for separation. Otherwise, use the output directly as an
                 estimation for the separated signals.
             output_nonlinearity: Nonlinearity applied to the output (right before masking/decoding): 'sigmoid', 'relu', 'leaky_relu',

@@ -15,6 +15,8 @@ from .lstm import packed_lstm  # noqa: F401
 from .unit_norm import unit_norm  # noqa: F401
 from . import tas  # noqa: F401
 from .tas import tas_encode, tas_decode, tas_masked_decode  # noqa: F401
+from . import stft_coders  # noqa: F401
+from .stft_coders import stft_encode, istft_decode, istft_masked_decode  # noqa: F401
 from . import tcn  # noqa: F401
 from .tcn import depthwise_prelu, channel_norm  # noqa: F401
 from . import tasnet  # noqa: F401
