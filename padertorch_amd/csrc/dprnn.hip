@@ -12,12 +12,13 @@
 // sequences.  H > 128 (4 H^2 words fit neither the registers nor the LDS of a workgroup) runs on two kernels of the same decomposition
 // that stream W_hh from the L2 every step, up to H = 1536 (the LDS of a CU).
 //
-// Sums over rows (d gamma, d beta, bias gradients): fp64, per-slab partials in the caller's workspace, added in ascending order by a
-// second kernel: no atomics, bit-reproducible.  No allocation, no synchronisation: every launcher is capturable; chunk counts and
+// Sums over rows (d gamma, d beta, bias gradients): fp64, per-slab partials in the caller's workspace, added by a second kernel in the
+// fixed order that reduce.h defines: no atomics, bit-reproducible.  No allocation, no synchronisation: every launcher is capturable; chunk counts and
 // sequence tables are device data.
 #include <algorithm>
 
 #include "lstm_common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
@@ -450,12 +451,6 @@ __global__ __launch_bounds__(256) void dprnn_lstm_backward_stream_kernel(const D
 }
 
 // ------------------------------------------------------------------------------------------------ c. layer norm + mask + residual
-__device__ __forceinline__ double dp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Row (b, s, k) is valid iff s < sb[b] (sb null: every row).
 __device__ __forceinline__ bool dp_valid(const int* sb, long long row, int S, int K) {
     if (!sb) return true;
@@ -479,13 +474,13 @@ __global__ __launch_bounds__(256) void dprnn_norm_residual_forward_kernel(const 
     if (valid) {
         double s1 = 0.;
         for (int n = lane; n < N; n += 64) s1 += (double)zr[n];
-        const double m = dp_wave_sum(s1) / (double)N;
+        const double m = wave_sum(s1) / (double)N;
         double s2 = 0.;
         for (int n = lane; n < N; n += 64) {
             const double dlt = (double)zr[n] - m;
             s2 += dlt * dlt;
         }
-        const double var = dp_wave_sum(s2) / (double)N;
+        const double var = wave_sum(s2) / (double)N;
         mean = (float)m, rstd = (float)(1. / sqrt(var + (double)eps));
     }
     if (lane == 0) stats[2 * row] = mean, stats[2 * row + 1] = rstd;
@@ -518,7 +513,7 @@ __global__ __launch_bounds__(256) void dprnn_norm_residual_backward_kernel(const
             s1 += (double)g;
             s2 += (double)g * (double)xh;
         }
-        c1 = (float)(dp_wave_sum(s1) / (double)N), c2 = (float)(dp_wave_sum(s2) / (double)N);
+        c1 = (float)(wave_sum(s1) / (double)N), c2 = (float)(wave_sum(s2) / (double)N);
     }
     for (int n = lane; n < N; n += 64) {
         const float g = gr[n];
@@ -560,24 +555,6 @@ __global__ __launch_bounds__(256) void dprnn_colsum_kernel(const float* __restri
         const long long width = mode ? 2LL * C : C;
         ws[blockIdx.y * width + c] = ((red[0][cx][0] + red[1][cx][0]) + red[2][cx][0]) + red[3][cx][0];
         if (mode) ws[blockIdx.y * width + C + c] = ((red[0][cx][1] + red[1][cx][1]) + red[2][cx][1]) + red[3][cx][1];
-    }
-}
-
-// out[j] = sum_s ws[s][j] for j < width: four chains s = g, g + 4, ... (ascending), combined ((0 + 1) + 2) + 3.
-__global__ __launch_bounds__(256) void dprnn_colreduce_kernel(const double* __restrict__ ws, long long slabs, long long width,
-                                                              float* __restrict__ out, float* __restrict__ out2) {
-    __shared__ double red[4][64];
-    const int jx = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const long long j = (long long)blockIdx.x * 64 + jx;
-    double s = 0.;
-    if (j < width)
-        for (long long sl = g; sl < slabs; sl += 4) s += ws[sl * width + j];
-    red[g][jx] = s;
-    __syncthreads();
-    if (g == 0 && j < width) {
-        const float v = (float)(((red[0][jx] + red[1][jx]) + red[2][jx]) + red[3][jx]);
-        out[j] = v;
-        if (out2) out2[j] = v;          // the same sum for a second parameter (b_ih and b_hh), without a second pass over the rows
     }
 }
 
@@ -714,9 +691,7 @@ int ptmi_dprnn_colsum(const float* x, int64_t ld, float* out, float* out2, doubl
                        (const float*)nullptr, (const float*)nullptr, (const int*)nullptr, workspace, (long long)rows, C, 1, 1, 0);
     int rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(dprnn_colreduce_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, st, workspace, slabs, (long long)C, out,
-                       out2);
-    return launch_status();
+    return colreduce(workspace, slabs, (long long)C, StoreTwice{out, out2}, st);          // out2: b_hh beside b_ih
 }
 
 int ptmi_dprnn_norm_residual_forward(const float* z, const float* residual, const float* gamma, const float* beta,
@@ -745,9 +720,7 @@ int ptmi_dprnn_norm_residual_backward(const float* gy, const float* z, const flo
                        chunks, workspace, (long long)rows, N, S, K, 1);
     rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(dprnn_colreduce_kernel, dim3((unsigned)((2LL * N + 63) / 64)), dim3(256), 0, st, workspace, slabs, 2LL * N,
-                       dparams, (float*)nullptr);
-    return launch_status();
+    return colreduce(workspace, slabs, 2LL * N, StoreTwice{dparams, nullptr}, st);
 }
 
 int64_t ptmi_dprnn_num_chunks(int64_t L, int32_t K, int32_t P) {

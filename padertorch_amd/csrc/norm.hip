@@ -7,13 +7,13 @@
 // Three kernels cover forward, backward and the running-statistics mode:
 //   norm_reduce_kernel  masked sums per group over the reduced axes (three integrand sets: statistics,
 //                       backward statistics, gamma/beta gradients), fp64 accumulation, deterministic
-//                       two-stage reduction.  Lanes run along the innermost axis: along the reduction
+//                       two-stage reduction (lanes by reduce.h's wave_sum).  Lanes run along the innermost axis: along the reduction
 //                       when that axis is reduced, along 64 neighbouring groups when it is kept, so
 //                       global reads are coalesced either way;
 //   norm_apply_kernel   y = mask * ((x - mean) * rstd * gamma + beta);
 //   norm_bwd_kernel     dx = mask * (ghat * rstd + c1[g] * xc + c0[g]).
 // All are one pass over the tensor: HBM bound.
-#include "common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
@@ -65,12 +65,6 @@ struct NormRedArgs {
     long long chunk;      // reduced elements per workgroup
     int nchunks;
 };
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // IdxT = unsigned (tensors below 2^31 elements: 32-bit index decode) or long long
 template <typename IdxT>
@@ -140,9 +134,9 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const NormRedArgs A) {
     double* out = A.ws + ((long long)blockIdx.y * g.n_groups) * 3;
     if (gt == 1) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        s0 = wsum(s0);
-        s1 = wsum(s1);
-        s2 = wsum(s2);
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
         if (lane == 0) {
             red[0][wave] = s0;
             red[1][wave] = s1;
@@ -184,7 +178,7 @@ __global__ void norm_reduce2_kernel(const double* __restrict__ ws, double* __res
         if (i >= n) return;
         double v = 0.;
         for (int c = lane; c < nchunks; c += 64) v += ws[(long long)c * n + i];
-        v = wsum(v);
+        v = wave_sum(v);
         if (lane == 0) out[i] = v;
     }
 }

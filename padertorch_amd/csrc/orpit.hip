@@ -12,33 +12,15 @@
 // The flag head reads the separator's additional output [B, A, E] and, in the weighted modes, mask [K, B, N, E] and encoded
 // [B, N, E] directly: mask * encoded (the reference's encoded_out) is never stored.
 //
-// Conventions of td_loss.hip / tasnet.hip: fp32 data, fp64 accumulation of exact products, no atomics, per-workgroup partials in a
-// caller-owned workspace of doubles added in ascending order by a second stage (bit-reproducible), no allocation and no
-// synchronisation (capturable), float4 loads with a scalar path for rows that are not 16-byte aligned.
-#include <initializer_list>
-
-#include "common.h"
+// Conventions of td_loss.hip / tasnet.hip: fp32 data, fp64 accumulation of exact products, no atomics, the order of addition inside a
+// workgroup that reduce.h defines, per-workgroup partials in a caller-owned workspace of doubles added in ascending order by a second
+// stage (bit-reproducible), no allocation and no synchronisation (capturable), float4 loads with a scalar path for rows that are not
+// 16-byte aligned.
+#include "reduce.h"
 
 namespace ptmi {
 
 constexpr int kRectMax = 8;
-
-__device__ __forceinline__ double orpit_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-static long long orpit_pick_chunk(long long batch, long long T) {
-    // as td_loss.hip: ~2048 workgroups per call when the input allows it; 1024..65536 samples each
-    long long chunk = (batch * T + 2047) / 2048;
-    chunk = (chunk + 1023) / 1024 * 1024;
-    if (chunk < 1024) chunk = 1024;
-    if (chunk > 65536) chunk = 65536;
-    return chunk;
-}
-
-static bool orpit_aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 struct RectArgs {
     const float* est;
@@ -137,18 +119,18 @@ __global__ __launch_bounds__(256) void rect_stats_kernel(const RectArgs A) {
         for (int m = 0; m < ME; ++m)
 #pragma unroll
             for (int j = 0; j < K; ++j, ++s) {
-                const double v = orpit_wave_sum(cc[m][j]);
+                const double v = wave_sum(cc[m][j]);
                 if (lane == 0) red[wave][s] = v;
             }
 #pragma unroll
         for (int m = 0; m < ME; ++m, ++s) {
-            const double v = orpit_wave_sum(see[m]);
+            const double v = wave_sum(see[m]);
             if (lane == 0) red[wave][s] = v;
         }
         if (K > 0) {
 #pragma unroll
             for (int x = 0; x < NG; ++x, ++s) {
-                const double v = orpit_wave_sum(g[x]);
+                const double v = wave_sum(g[x]);
                 if (lane == 0) red[wave][s] = v;
             }
         }
@@ -371,25 +353,6 @@ struct FlagArgs {
     int A, N, K, k, weighted, nblk;
 };
 
-// V consecutive floats: one float4 (V == 4, 16-byte aligned) or one float.
-template <int V>
-__device__ __forceinline__ void load(const float* p, float (&v)[V]) {
-    if constexpr (V == 4) {
-        const float4 x = *reinterpret_cast<const float4*>(p);
-        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void store(float* p, const float (&v)[V]) {
-    if constexpr (V == 4)
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else
-        *p = v[0];
-}
-
 // A workgroup is 64 lanes x 4 waves: a lane owns V consecutive frames, the waves share the rows (a, then n) among them and their
 // partial sums are added in wave order.  pre and w are stored; the workgroup's partial (sum pre w, sum w) goes to the workspace.
 template <int V>
@@ -403,7 +366,7 @@ __global__ __launch_bounds__(256) void flag_forward_kernel(const FlagArgs P) {
     if (live) {
         for (int a = wave; a < P.A; a += 4) {
             float x[V];
-            load(P.additional + (b * P.A + a) * P.E + e0, x);
+            load_vec<V>(P.additional + (b * P.A + a) * P.E + e0, x);
             const double wa = (double)P.weight[a];
 #pragma unroll
             for (int q = 0; q < V; ++q) accp[q] = fma(wa, (double)x[q], accp[q]);
@@ -413,8 +376,8 @@ __global__ __launch_bounds__(256) void flag_forward_kernel(const FlagArgs P) {
             const float* en = P.encoded ? P.encoded + b * P.N * P.E + e0 : nullptr;
             for (int n = wave; n < P.N; n += 4) {
                 float mv[V], ev[V];
-                load(m + (long long)n * P.E, mv);
-                if (en) load(en + (long long)n * P.E, ev);
+                load_vec<V>(m + (long long)n * P.E, mv);
+                if (en) load_vec<V>(en + (long long)n * P.E, ev);
 #pragma unroll
                 for (int q = 0; q < V; ++q) {
                     const double p = en ? (double)mv[q] * (double)ev[q] : (double)mv[q];
@@ -445,8 +408,8 @@ __global__ __launch_bounds__(256) void flag_forward_kernel(const FlagArgs P) {
             den += w;
         }
     }
-    num = orpit_wave_sum(num);
-    den = orpit_wave_sum(den);
+    num = wave_sum(num);
+    den = wave_sum(den);
     if (lane == 0) {
         double* o = P.ws + (b * P.nblk + blockIdx.x) * 2;
         o[0] = num;
@@ -500,9 +463,9 @@ __global__ __launch_bounds__(256) void flag_backward_kernel(const FlagBwdArgs P)
     for (int q = 0; q < V; ++q) dpre[q] = dw[q] = 0.f;
     if (live) {
         float pv[V], wv[V], gp[V];
-        load(P.pre + b * P.E + e0, pv);
-        if (P.weighted) load(P.w + b * P.E + e0, wv);
-        if (P.gpre) load(P.gpre + b * P.E + e0, gp);
+        load_vec<V>(P.pre + b * P.E + e0, pv);
+        if (P.weighted) load_vec<V>(P.w + b * P.E + e0, wv);
+        if (P.gpre) load_vec<V>(P.gpre + b * P.E + e0, gp);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
             const double wq = P.weighted ? (double)wv[q] : 1.0;
@@ -515,23 +478,23 @@ __global__ __launch_bounds__(256) void flag_backward_kernel(const FlagBwdArgs P)
         double s = 0.0;
         if (live) {
             float xv[V], o[V];
-            load(P.additional + (b * P.A + a) * P.E + e0, xv);
+            load_vec<V>(P.additional + (b * P.A + a) * P.E + e0, xv);
             const float wa = P.weight[a];
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 o[q] = wa * dpre[q];
                 s = fma((double)xv[q], (double)dpre[q], s);
             }
-            store(P.dadditional + (b * P.A + a) * P.E + e0, o);
+            store_vec<V>(P.dadditional + (b * P.A + a) * P.E + e0, o);
         }
-        s = orpit_wave_sum(s);
+        s = wave_sum(s);
         if (lane == 0) part[a] = s;
     }
     if (wave == 0) {
         double s = 0.0;
 #pragma unroll
         for (int q = 0; q < V; ++q) s += (double)dpre[q];
-        s = orpit_wave_sum(s);
+        s = wave_sum(s);
         if (lane == 0) part[P.A] = s;
     }
     if (!P.weighted || !live) return;
@@ -542,16 +505,16 @@ __global__ __launch_bounds__(256) void flag_backward_kernel(const FlagBwdArgs P)
     for (int n = wave; n < P.N; n += 4) {
         const long long at = row + (long long)n * P.E;
         float mv[V], ev[V], dm[V], de[V];
-        load(P.mask + P.k * slice + at, mv);
-        if (P.encoded) load(P.encoded + at, ev);
+        load_vec<V>(P.mask + P.k * slice + at, mv);
+        if (P.encoded) load_vec<V>(P.encoded + at, ev);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
             const float en = P.encoded ? ev[q] : 1.f;
             dm[q] = dw[q] * mv[q] * en * en;
             de[q] = dw[q] * mv[q] * mv[q] * en;
         }
-        for (int kk = 0; kk < P.K; ++kk) store(P.dmask + kk * slice + at, kk == P.k ? dm : zero);
-        if (P.encoded) store(P.dencoded + at, de);
+        for (int kk = 0; kk < P.K; ++kk) store_vec<V>(P.dmask + kk * slice + at, kk == P.k ? dm : zero);
+        if (P.encoded) store_vec<V>(P.dencoded + at, de);
     }
 }
 
@@ -565,10 +528,7 @@ __global__ void flag_params_kernel(const double* __restrict__ ws, float* __restr
 }
 
 static int flag_vec(long long E, std::initializer_list<const void*> ptrs) {
-    if (E % 4) return 0;
-    for (const void* p : ptrs)
-        if (p && !orpit_aligned16(p)) return 0;
-    return 1;
+    return E % 4 == 0 && aligned16(ptrs);          // (an absent operand is a null pointer and counts as aligned)
 }
 
 }  // namespace ptmi
@@ -579,7 +539,7 @@ extern "C" {
 
 int64_t ptmi_td_rect_workspace_elems(int64_t batch, int32_t M, int32_t K, int64_t T) {
     if (batch < 1 || M < 1 || K < 0 || T < 1) return PTMI_E_INVALID;
-    const long long chunk = orpit_pick_chunk(batch, T);
+    const long long chunk = pick_chunk(batch, T);
     return batch * ((T + chunk - 1) / chunk) * ((int64_t)M * K + M + (int64_t)K * K);
 }
 
@@ -597,12 +557,12 @@ int ptmi_td_rect_stats(const float* est, const float* tgt, int64_t batch, int32_
     A.em = strides[1];
     A.tb = strides[2];
     A.tk = strides[3];
-    A.chunk = orpit_pick_chunk(batch, T);
+    A.chunk = pick_chunk(batch, T);
     A.M = M;
     A.K = K;
     A.nchunks = (int)((T + A.chunk - 1) / A.chunk);
     A.gram = gram != nullptr && K > 0;
-    A.vec = T >= 4 && orpit_aligned16(est) && (K == 0 || orpit_aligned16(tgt)) && A.eb % 4 == 0 && A.em % 4 == 0 &&
+    A.vec = T >= 4 && aligned16({est}) && (K == 0 || aligned16({tgt})) && A.eb % 4 == 0 && A.em % 4 == 0 &&
             (K == 0 || (A.tb % 4 == 0 && A.tk % 4 == 0));
     A.ws = workspace;
     int rc = M % 2 == 0 ? dispatch_rect_stats<2>(A, batch, st) : dispatch_rect_stats<1>(A, batch, st);
@@ -642,9 +602,9 @@ int ptmi_td_rect_lincomb(const float* est, const float* tgt, const float* g, con
     P.tk = strides[3];
     P.ob = strides[4];
     P.om = strides[5];
-    P.chunk = orpit_pick_chunk(batch, T);
+    P.chunk = pick_chunk(batch, T);
     P.M = M;
-    P.vec = orpit_aligned16(est) && orpit_aligned16(out) && (K == 0 || orpit_aligned16(tgt)) && P.eb % 4 == 0 && P.em % 4 == 0 &&
+    P.vec = aligned16({est, out}) && (K == 0 || aligned16({tgt})) && P.eb % 4 == 0 && P.em % 4 == 0 &&
             P.ob % 4 == 0 && P.om % 4 == 0 && (K == 0 || (P.tb % 4 == 0 && P.tk % 4 == 0));
     hipStream_t st = static_cast<hipStream_t>(stream);
     return M % 2 == 0 ? dispatch_rect_lincomb<2>(P, K, batch, st) : dispatch_rect_lincomb<1>(P, K, batch, st);

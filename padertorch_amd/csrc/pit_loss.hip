@@ -5,12 +5,12 @@
 // padertorch/contrib/examples/source_separation/pit/model.py:117-140 with
 //   1. ONE streaming pass over mask / observation / target / cos-phase that accumulates the
 //      K x K pairwise sums of squared errors of every example (HBM-bound: 7196 B per frame at
-//      K=2, F=257; fp32 partials per thread, wave shuffles + LDS across the 4 waves, fp64 from the
+//      K=2, F=257; fp32 partials per thread, wave shuffles (reduce.h's wave_sum) + LDS across the 4 waves, fp64 from the
 //      workgroup partial upwards, fixed reduction order -> bitwise reproducible),
 //   2. a tiny kernel that walks the K! permutations in itertools order on the K x K matrix (first
 //      minimum wins, like torch.min) and forms the batch means,
 //   3. a streaming backward that scatters 2 (est - tgt_perm) / n for the winning permutation.
-#include "common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
@@ -27,12 +27,6 @@ struct PitArgs {
     long long est_bs, est_ts, obs_bs, obs_ts, tgt_bs, tgt_ts;   // element strides of (b, t)
     int K, F, nvar, nchunks;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // partial[b, chunk, v, i, j] (fp64) <- sum over the chunk's (t, f) of (est_i - tgt^v_j)^2
 template <int K>

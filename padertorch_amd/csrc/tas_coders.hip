@@ -17,10 +17,11 @@
 //              gradient) and sum_{b,t} x[b,t] (the decoder's) from one pass: a workgroup owns 256 (n, l) pairs
 //              and one (b, tau range), stages g and the x segment in LDS, and writes its partial sums to the
 //              caller's workspace; a second kernel adds the partials in (b, tau range) order.
-// All sums have a fixed order (l ascending; n, tau ascending; partials ascending): results are bit-reproducible.
+// All sums have a fixed order (l ascending; n, tau ascending; lanes by reduce.h's wave_sum; partials ascending): results are
+// bit-reproducible.
 #include <algorithm>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
@@ -186,12 +187,6 @@ struct TasWgArgs {
     int N, L, s, K, tc, nchunks, xlds;
 };
 
-__device__ __forceinline__ float tas_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Workgroup (pair block, tau chunk, b): thread <-> pair (n, l) = p0 + threadIdx.x; the rows n of the pair block's
 // g tile and the signal segment [tau0 s, (tau0 + tc - 1) s + L) come through LDS (XLDS; a segment that does not
 // fit is read through the caches).
@@ -251,7 +246,7 @@ __global__ __launch_bounds__(256) void tas_wgrad_kernel(const TasWgArgs A) {
         if (l == 0) slab[P + n] = gsum;
     }
     if (blockIdx.x == 0) {
-        const float v = tas_wave_sum(xsum);
+        const float v = wave_sum(xsum);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
         __syncthreads();
         if (threadIdx.x == 0) slab[P + A.N] = ((red[0] + red[1]) + red[2]) + red[3];

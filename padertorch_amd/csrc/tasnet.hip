@@ -13,12 +13,12 @@
 // V = 4 on a side needs that side's innermost extent to be a multiple of 4 and its pointers 16-byte aligned; each side is chosen
 // on its own, per launch, and the arithmetic per element is the same in all four combinations.
 //
-// Sums: fp64 in threads, workgroups and finalize kernels; no atomics; partials go to a caller's workspace and are added in a fixed
-// ascending order (the discipline of tcn.hip / norm.hip): results are bit-reproducible.  No allocation, no synchronisation: capturable.
+// Sums: fp64 in threads, workgroups and finalize kernels; no atomics; partials go to a caller's workspace and are added in the fixed
+// order that reduce.h defines: results are bit-reproducible.  No allocation, no synchronisation: capturable.
 // The lengths of the entry norm are device data.
 #include <algorithm>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
@@ -29,46 +29,6 @@ constexpr int kTnBwdC = 128;              // ... of its backward, which holds tw
 constexpr int kTnHeadC = 64;              // ... of the mask head
 constexpr int kTnChunk = 8192;            // elements per workgroup of the PReLU kernels
 constexpr int kTnCenterChunk = 2048;      // samples per workgroup of the centring kernels
-
-template <int V>
-__device__ __forceinline__ void tn_load(const float* __restrict__ p, float (&o)[V]) {
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = t.w;
-    } else {
-        o[0] = p[0];
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void tn_store(float* __restrict__ p, const float (&o)[V]) {
-    if constexpr (V == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-        p[0] = o[0];
-    }
-}
-
-__device__ __forceinline__ double tn_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Sum of s[n] over the workgroup's 256 threads, returned to every thread: lanes by butterfly, then waves 0..3 in order.
-template <int N>
-__device__ __forceinline__ void tn_block_sums(double (&s)[N]) {
-    __shared__ double red[4][N];
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const double v = tn_wave_sum(s[n]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][n] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < N; ++n) s[n] = ((red[0][n] + red[1][n]) + red[2][n]) + red[3][n];
-}
 
 // ---- the tile's two sides.  f(c, e, v): c < nc the channel inside the tile, e < ne the (first) frame inside it, v the V values.
 // Channels-first side into the tile: f fills v with V consecutive frames of channel c.
@@ -186,7 +146,7 @@ __global__ __launch_bounds__(256) void tasnet_entry_norm_forward_kernel(const Tn
     for (int cb = 0; cb < nblk; ++cb) {
         const int c0 = cb * kTnFwdC, nc = min(kTnFwdC, A.N - c0);
         if (cb) __syncthreads();
-        tn_cf_in<VF>(tile, nc, ne, [&](int c, int e, float (&v)[VF]) { tn_load<VF>(wb + (long long)(c0 + c) * A.E + e, v); });
+        tn_cf_in<VF>(tile, nc, ne, [&](int c, int e, float (&v)[VF]) { load_vec<VF>(wb + (long long)(c0 + c) * A.E + e, v); });
         __syncthreads();
         if (fe < ne)
             for (int c = fp; c < nc; c += 8) {
@@ -217,18 +177,18 @@ __global__ __launch_bounds__(256) void tasnet_entry_norm_forward_kernel(const Tn
         const int c0 = cb * kTnFwdC, nc = min(kTnFwdC, A.N - c0);
         if (nblk > 1) {
             __syncthreads();
-            tn_cf_in<VF>(tile, nc, ne, [&](int c, int e, float (&v)[VF]) { tn_load<VF>(wb + (long long)(c0 + c) * A.E + e, v); });
+            tn_cf_in<VF>(tile, nc, ne, [&](int c, int e, float (&v)[VF]) { load_vec<VF>(wb + (long long)(c0 + c) * A.E + e, v); });
             __syncthreads();
         }
         tn_cl_out<VL, kTnFwdC>(tile, nc, ne, [&](int c, int e, float (&v)[VL]) {
             const bool on = e0 + e < live;
             const float m = smean[e], rs = srstd[e];
             float ga[VL], be[VL];
-            tn_load<VL>(A.gamma + c0 + c, ga);
-            tn_load<VL>(A.beta + c0 + c, be);
+            load_vec<VL>(A.gamma + c0 + c, ga);
+            load_vec<VL>(A.beta + c0 + c, be);
 #pragma unroll
             for (int j = 0; j < VL; ++j) v[j] = on ? fmaf(ga[j], (v[j] - m) * rs, be[j]) : 0.f;
-            tn_store<VL>(yb + (long long)e * A.N + c0 + c, v);
+            store_vec<VL>(yb + (long long)e * A.N + c0 + c, v);
         });
     }
 }
@@ -258,8 +218,8 @@ __global__ __launch_bounds__(256) void tasnet_entry_norm_backward_kernel(const T
     }
     const int nlive = (int)max(0LL, min((long long)ne, live - e0));      // live frames of this tile: frames [0, nlive)
     auto fill = [&](int c0, int nc) {
-        tn_cf_in<VF>(tw, nc, ne, [&](int c, int e, float (&v)[VF]) { tn_load<VF>(wb + (long long)(c0 + c) * A.E + e, v); });
-        tn_cl_in<VL, kTnBwdC>(tg, nc, ne, [&](int c, int e, float (&v)[VL]) { tn_load<VL>(gb + (long long)e * A.N + c0 + c, v); });
+        tn_cf_in<VF>(tw, nc, ne, [&](int c, int e, float (&v)[VF]) { load_vec<VF>(wb + (long long)(c0 + c) * A.E + e, v); });
+        tn_cl_in<VL, kTnBwdC>(tg, nc, ne, [&](int c, int e, float (&v)[VL]) { load_vec<VL>(gb + (long long)e * A.N + c0 + c, v); });
     };
     double* __restrict__ col = A.wcol + (b * gridDim.x + blockIdx.x) * 2 * (long long)A.N;
     double s1 = 0., s2 = 0.;
@@ -318,23 +278,9 @@ __global__ __launch_bounds__(256) void tasnet_entry_norm_backward_kernel(const T
                 const float xh = (v[j] - smean[e + j]) * rs;
                 v[j] = e + j < nlive ? rs * fmaf(-xh, sg2[e + j], tg[c][e + j] * ga - sg1[e + j]) : 0.f;
             }
-            tn_store<VF>(db_ + (long long)(c0 + c) * A.E + e, v);
+            store_vec<VF>(db_ + (long long)(c0 + c) * A.E + e, v);
         });
     }
-}
-
-// out[j] = sum_s ws[s][j] for j < width: four chains s = g, g + 4, ... (ascending), combined ((0 + 1) + 2) + 3.
-__global__ __launch_bounds__(256) void tasnet_colreduce_kernel(const double* __restrict__ ws, long long slabs, long long width,
-                                                               float* __restrict__ out) {
-    __shared__ double red[4][64];
-    const int jx = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const long long j = (long long)blockIdx.x * 64 + jx;
-    double s = 0.;
-    if (j < width)
-        for (long long sl = g; sl < slabs; sl += 4) s += ws[sl * width + j];
-    red[g][jx] = s;
-    __syncthreads();
-    if (g == 0 && j < width) out[j] = (float)(((red[0][jx] + red[1][jx]) + red[2][jx]) + red[3][jx]);
 }
 
 // ------------------------------------------------------------------------------------------------ b. PReLU on rows
@@ -350,23 +296,23 @@ __global__ __launch_bounds__(256) void tasnet_prelu_kernel(const float* __restri
     double s[1] = {0.};
     for (long long i = i0 + (long long)threadIdx.x * V; i < i1; i += 256 * V) {
         float xv[V], o[V];
-        tn_load<V>(x + i, xv);
+        load_vec<V>(x + i, xv);
         if (mode == 0) {
 #pragma unroll
             for (int j = 0; j < V; ++j) o[j] = xv[j] > 0.f ? xv[j] : a * xv[j];
         } else {
             float gv[V];
-            tn_load<V>(g + i, gv);
+            load_vec<V>(g + i, gv);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 s[0] += xv[j] > 0.f ? 0. : (double)gv[j] * (double)xv[j];
                 o[j] = xv[j] > 0.f ? gv[j] : a * gv[j];
             }
         }
-        tn_store<V>(y + i, o);
+        store_vec<V>(y + i, o);
     }
     if (mode == 1) {
-        tn_block_sums<1>(s);
+        block_sums<1>(s);
         if (threadIdx.x == 0) ws[blockIdx.x] = s[0];
     }
 }
@@ -377,7 +323,7 @@ __global__ __launch_bounds__(256) void tasnet_sum_finalize_kernel(const double* 
     const double* __restrict__ p = ws + (long long)blockIdx.x * slabs;
     double s[1] = {0.};
     for (long long i = threadIdx.x; i < slabs; i += 256) s[0] += p[i];
-    tn_block_sums<1>(s);
+    block_sums<1>(s);
     if (threadIdx.x == 0) out[blockIdx.x] = (float)(s[0] * scale);
 }
 
@@ -434,16 +380,16 @@ __global__ __launch_bounds__(256) void tasnet_mask_head_kernel(const TnHeadArgs 
     const int ne = (int)min((long long)kTnE, A.E - e0), nc = min(kTnHeadC, A.C - c0);
     if (!backward) {
         const float* __restrict__ zb = A.z + (b * A.E + e0) * A.C + c0;
-        tn_cl_in<VL, kTnHeadC>(tile, nc, ne, [&](int c, int e, float (&v)[VL]) { tn_load<VL>(zb + (long long)e * A.C + c, v); });
+        tn_cl_in<VL, kTnHeadC>(tile, nc, ne, [&](int c, int e, float (&v)[VL]) { load_vec<VL>(zb + (long long)e * A.C + c, v); });
         __syncthreads();
         tn_cf_out<VF>(tile, nc, ne, [&](int c, int e, float (&v)[VF]) {
             const int cc = c0 + c;
             if (cc < A.A) {
-                tn_store<VF>(A.add + (b * A.A + cc) * A.E + e0 + e, v);
+                store_vec<VF>(A.add + (b * A.A + cc) * A.E + e0 + e, v);
             } else {
 #pragma unroll
                 for (int j = 0; j < VF; ++j) v[j] = tn_act(A.act, v[j]);
-                tn_store<VF>(A.m + tn_head_row(A, b, cc) + e0 + e, v);
+                store_vec<VF>(A.m + tn_head_row(A, b, cc) + e0 + e, v);
             }
         });
     } else {
@@ -451,7 +397,7 @@ __global__ __launch_bounds__(256) void tasnet_mask_head_kernel(const TnHeadArgs 
             const int cc = c0 + c;
             if (cc < A.A) {
                 if (A.gadd) {
-                    tn_load<VF>(A.gadd + (b * A.A + cc) * A.E + e0 + e, v);
+                    load_vec<VF>(A.gadd + (b * A.A + cc) * A.E + e0 + e, v);
                 } else {
 #pragma unroll
                     for (int j = 0; j < VF; ++j) v[j] = 0.f;
@@ -459,15 +405,15 @@ __global__ __launch_bounds__(256) void tasnet_mask_head_kernel(const TnHeadArgs 
             } else {
                 const long long at = tn_head_row(A, b, cc) + e0 + e;
                 float mv[VF];
-                tn_load<VF>(A.gm + at, v);
-                tn_load<VF>(A.m + at, mv);
+                load_vec<VF>(A.gm + at, v);
+                load_vec<VF>(A.m + at, mv);
 #pragma unroll
                 for (int j = 0; j < VF; ++j) v[j] = v[j] * tn_dact(A.act, mv[j]);
             }
         });
         __syncthreads();
         float* __restrict__ gzb = A.gz + (b * A.E + e0) * A.C + c0;
-        tn_cl_out<VL, kTnHeadC>(tile, nc, ne, [&](int c, int e, float (&v)[VL]) { tn_store<VL>(gzb + (long long)e * A.C + c, v); });
+        tn_cl_out<VL, kTnHeadC>(tile, nc, ne, [&](int c, int e, float (&v)[VL]) { store_vec<VL>(gzb + (long long)e * A.C + c, v); });
     }
 }
 
@@ -499,14 +445,14 @@ __global__ __launch_bounds__(256) void tasnet_center_sum_kernel(const TnCenterAr
     for (long long t = t0 + (long long)threadIdx.x * 4; t < t1; t += 1024) {
         if constexpr (V == 4) {
             float v[4];
-            tn_load<4>(src + t, v);
+            load_vec<4>(src + t, v);
 #pragma unroll
             for (int j = 0; j < 4; ++j) s[0] += (double)v[j];
         } else {
             for (int j = 0; j < 4 && t + j < t1; ++j) s[0] += (double)src[t + j];
         }
     }
-    tn_block_sums<1>(s);
+    block_sums<1>(s);
     if (threadIdx.x == 0) A.ws[(long long)blockIdx.y * A.chunks + blockIdx.x] = s[0];
 }
 
@@ -520,27 +466,21 @@ __global__ __launch_bounds__(256) void tasnet_center_apply_kernel(const TnCenter
     const double* __restrict__ p = A.ws + (long long)blockIdx.y * A.chunks;
     double s[1] = {0.};
     for (long long i = threadIdx.x; i < A.chunks; i += 256) s[0] += p[i];
-    tn_block_sums<1>(s);
+    block_sums<1>(s);
     const float mean = (float)(s[0] / (double)A.n);
     const long long t0 = (long long)blockIdx.x * kTnCenterChunk, t1 = min(t0 + kTnCenterChunk, A.out_len);
     for (long long t = t0 + (long long)threadIdx.x * V; t < t1; t += 256 * V) {
         float v[V];
         if (t < A.n) {                      // V == 4: n and out_len are multiples of 4, a quad lies on one side
-            tn_load<V>(src + t, v);
+            load_vec<V>(src + t, v);
 #pragma unroll
             for (int j = 0; j < V; ++j) v[j] = v[j] - mean;
         } else {
 #pragma unroll
             for (int j = 0; j < V; ++j) v[j] = 0.f;
         }
-        tn_store<V>(dst + t, v);
+        store_vec<V>(dst + t, v);
     }
-}
-
-static bool tn_aligned(std::initializer_list<const void*> ptrs) {
-    for (const void* p : ptrs)
-        if (reinterpret_cast<unsigned long long>(p) & 15) return false;
-    return true;
 }
 
 // kernel<VF, VL>: VF the vector width of the channels-first side, VL of the channels-last side
@@ -554,14 +494,6 @@ static bool tn_aligned(std::initializer_list<const void*> ptrs) {
             hipLaunchKernelGGL((kernel<1, 4>), grid, dim3(256), 0, st, __VA_ARGS__);        \
         else                                                                                \
             hipLaunchKernelGGL((kernel<1, 1>), grid, dim3(256), 0, st, __VA_ARGS__);        \
-    } while (0)
-
-#define TN_LAUNCH(kernel, vec, grid, st, ...)                                               \
-    do {                                                                                    \
-        if (vec)                                                                            \
-            hipLaunchKernelGGL((kernel<4>), grid, dim3(256), 0, st, __VA_ARGS__);           \
-        else                                                                                \
-            hipLaunchKernelGGL((kernel<1>), grid, dim3(256), 0, st, __VA_ARGS__);           \
     } while (0)
 
 static long long tn_tiles(int64_t E) { return (E + kTnE - 1) / kTnE; }
@@ -582,8 +514,8 @@ int ptmi_tasnet_entry_norm_forward(const float* w, const float* gamma, const flo
     PTMI_RETURN_IF(!w || !gamma || !beta || !y || !stats || B < 1 || N < 1 || E < 1, PTMI_E_INVALID);
     const long long tiles = tn_tiles(E);
     PTMI_RETURN_IF(tiles > 0x7fffffffLL || B > 65535, PTMI_E_UNSUPPORTED);
-    const bool vf = E % 4 == 0 && tn_aligned({w});
-    const bool vl = N % 4 == 0 && tn_aligned({y, gamma, beta});
+    const bool vf = E % 4 == 0 && aligned16({w});
+    const bool vl = N % 4 == 0 && aligned16({y, gamma, beta});
     TnNormArgs A{};
     A.w = w, A.gamma = gamma, A.beta = beta, A.lengths = lengths, A.is64 = lengths_int64, A.y = y, A.stats = stats;
     A.E = E, A.N = N, A.eps = eps;
@@ -597,8 +529,8 @@ int ptmi_tasnet_entry_norm_backward(const float* gy, const float* w, const float
     PTMI_RETURN_IF(!gy || !w || !stats || !gamma || !dw || !dparams || !workspace || B < 1 || N < 1 || E < 1, PTMI_E_INVALID);
     const long long tiles = tn_tiles(E);
     PTMI_RETURN_IF(tiles > 0x7fffffffLL || B > 65535, PTMI_E_UNSUPPORTED);
-    const bool vf = E % 4 == 0 && tn_aligned({w, dw});
-    const bool vl = N % 4 == 0 && tn_aligned({gy});
+    const bool vf = E % 4 == 0 && aligned16({w, dw});
+    const bool vl = N % 4 == 0 && aligned16({gy});
     TnNormArgs A{};
     A.w = w, A.gy = gy, A.gamma = gamma, A.lengths = lengths, A.is64 = lengths_int64, A.stats_in = stats, A.dw = dw;
     A.wcol = workspace, A.E = E, A.N = N;
@@ -606,9 +538,7 @@ int ptmi_tasnet_entry_norm_backward(const float* gy, const float* w, const float
     TN_LAUNCH2(tasnet_entry_norm_backward_kernel, vf, vl, dim3((unsigned)tiles, (unsigned)B), st, A);
     int rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(tasnet_colreduce_kernel, dim3((unsigned)((2LL * N + 63) / 64)), dim3(256), 0, st, workspace, B * tiles, 2LL * N,
-                       dparams);
-    return launch_status();
+    return colreduce(workspace, B * tiles, 2LL * N, StorePlain{dparams}, st);
 }
 
 int64_t ptmi_tasnet_prelu_workspace_elems(int64_t n) {
@@ -620,8 +550,8 @@ int ptmi_tasnet_prelu_forward(const float* x, const float* slope, float* y, int6
     PTMI_RETURN_IF(!x || !slope || !y || n < 1, PTMI_E_INVALID);
     const long long chunks = (n + kTnChunk - 1) / kTnChunk;
     PTMI_RETURN_IF(chunks > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
-    const bool vec = n % 4 == 0 && tn_aligned({x, y});
-    TN_LAUNCH(tasnet_prelu_kernel, vec, dim3((unsigned)chunks), static_cast<hipStream_t>(stream), x, (const float*)nullptr, slope, y,
+    const bool vec = n % 4 == 0 && aligned16({x, y});
+    PTMI_LAUNCH_VEC(tasnet_prelu_kernel, vec, dim3((unsigned)chunks), static_cast<hipStream_t>(stream), x, (const float*)nullptr, slope, y,
               (long long)n, (double*)nullptr, 0);
     return launch_status();
 }
@@ -631,9 +561,9 @@ int ptmi_tasnet_prelu_backward(const float* g, const float* x, const float* slop
     PTMI_RETURN_IF(!g || !x || !slope || !gx || !dslope || !workspace || n < 1, PTMI_E_INVALID);
     const long long chunks = (n + kTnChunk - 1) / kTnChunk;
     PTMI_RETURN_IF(chunks > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
-    const bool vec = n % 4 == 0 && tn_aligned({g, x, gx});
+    const bool vec = n % 4 == 0 && aligned16({g, x, gx});
     hipStream_t st = static_cast<hipStream_t>(stream);
-    TN_LAUNCH(tasnet_prelu_kernel, vec, dim3((unsigned)chunks), st, x, g, slope, gx, (long long)n, workspace, 1);
+    PTMI_LAUNCH_VEC(tasnet_prelu_kernel, vec, dim3((unsigned)chunks), st, x, g, slope, gx, (long long)n, workspace, 1);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(tasnet_sum_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, chunks, 1., dslope);
@@ -658,7 +588,7 @@ int ptmi_tasnet_mask_head_forward(const float* z, float* m, float* additional, i
     PTMI_RETURN_IF(!z || !m || (A > 0 && !additional), PTMI_E_INVALID);
     TnHeadArgs H{};
     H.z = z, H.m = m, H.add = additional, H.B = B, H.E = E, H.N = N, H.K = K, H.A = A, H.act = activation;
-    return tn_head(H, 0, tn_aligned({m, additional}), tn_aligned({z}), stream);
+    return tn_head(H, 0, aligned16({m, additional}), aligned16({z}), stream);
 }
 
 int ptmi_tasnet_mask_head_backward(const float* gm, const float* m, const float* g_additional, float* gz, int64_t B, int64_t E,
@@ -667,7 +597,7 @@ int ptmi_tasnet_mask_head_backward(const float* gm, const float* m, const float*
     TnHeadArgs H{};
     H.gm = gm, H.m = const_cast<float*>(m), H.gadd = g_additional, H.gz = gz, H.B = B, H.E = E, H.N = N, H.K = K, H.A = A;
     H.act = activation;
-    return tn_head(H, 1, tn_aligned({gm, m, g_additional}), tn_aligned({gz}), stream);
+    return tn_head(H, 1, aligned16({gm, m, g_additional}), aligned16({gz}), stream);
 }
 
 int64_t ptmi_tasnet_center_workspace_elems(int64_t K, int64_t B, int64_t T_in, int64_t T_out) {
@@ -688,12 +618,12 @@ int ptmi_tasnet_center(const float* in, float* out, double* workspace, int64_t K
     }
     const long long out_chunks = (A.out_len + kTnCenterChunk - 1) / kTnCenterChunk;
     PTMI_RETURN_IF(out_chunks > 0x7fffffffLL || K * B > 65535, PTMI_E_UNSUPPORTED);
-    const bool vec = T_in % 4 == 0 && T_out % 4 == 0 && tn_aligned({in, out});
+    const bool vec = T_in % 4 == 0 && T_out % 4 == 0 && aligned16({in, out});
     hipStream_t st = static_cast<hipStream_t>(stream);
-    TN_LAUNCH(tasnet_center_sum_kernel, vec, dim3((unsigned)A.chunks, (unsigned)(K * B)), st, A);
+    PTMI_LAUNCH_VEC(tasnet_center_sum_kernel, vec, dim3((unsigned)A.chunks, (unsigned)(K * B)), st, A);
     int rc = launch_status();
     if (rc) return rc;
-    TN_LAUNCH(tasnet_center_apply_kernel, vec, dim3((unsigned)out_chunks, (unsigned)(K * B)), st, A);
+    PTMI_LAUNCH_VEC(tasnet_center_apply_kernel, vec, dim3((unsigned)out_chunks, (unsigned)(K * B)), st, A);
     return launch_status();
 }
 

@@ -13,58 +13,17 @@
 //                       partial sums of d a1.
 //   channel norm        statistics (per example: partial sums + finalize; per row: one wave per row), apply, and backward (per-channel
 //                       and per-group partial sums, finalize, dx).
-// Sums: per-thread, per-workgroup and final accumulators are fp64 (as csrc/norm.hip); no atomics; partials are added in a fixed
-// order (rows ascending inside a thread, waves 0..3, workgroups ascending in four interleaved chains combined ((0+1)+2)+3):
-// results are bit-reproducible.  No allocation, no synchronisation: capturable.
+// Sums: per-thread, per-workgroup and final accumulators are fp64; no atomics; partials are added in the fixed order that reduce.h
+// defines (rows ascending inside a thread): results are bit-reproducible.  No allocation, no synchronisation: capturable.
 #include <algorithm>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
 constexpr int kTcnRows = 64;              // rows per workgroup
 constexpr int kTcnR = kTcnRows / 4;       // rows per thread
 constexpr int kTcnChunk = 8192;           // elements per workgroup of the per-example statistics pass
-
-template <int V>
-__device__ __forceinline__ void tcn_load(const float* __restrict__ p, float (&o)[V]) {
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = t.w;
-    } else {
-        o[0] = p[0];
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void tcn_store(float* __restrict__ p, const float (&o)[V]) {
-    if constexpr (V == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-        p[0] = o[0];
-    }
-}
-
-__device__ __forceinline__ double tcn_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Sum of s[n] over the workgroup's 256 threads, returned to every thread: lanes by butterfly, then waves 0..3 in order.
-template <int N>
-__device__ __forceinline__ void tcn_block_sums(double (&s)[N]) {
-    __shared__ double red[4][N];
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const double v = tcn_wave_sum(s[n]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][n] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < N; ++n) s[n] = ((red[0][n] + red[1][n]) + red[2][n]) + red[3][n];
-}
 
 // Per-channel sums of the workgroup: the four waves' values of column cx * V + e, added in wave order by wave 0.
 template <int V>
@@ -118,7 +77,7 @@ __device__ __forceinline__ void tcn_preactivation(const TcnDwArgs& A, const floa
             const long long s = t0 + i + off;
             if (t0 + i < A.T && s >= 0 && s < A.T) {
                 float x[V];
-                tcn_load<V>(ub + s * A.H, x);
+                load_vec<V>(ub + s * A.H, x);
 #pragma unroll
                 for (int e = 0; e < V; ++e) z[i][e] = fmaf(wv[e], x[e] > 0.f ? x[e] : a1 * x[e], z[i][e]);
             }
@@ -150,11 +109,11 @@ __global__ __launch_bounds__(256) void tcn_dw_forward_kernel(const TcnDwArgs A) 
                     s[0] += (double)o[e];
                     s[1] += (double)o[e] * (double)o[e];
                 }
-                tcn_store<V>(vb + (t0 + i) * A.H, o);
+                store_vec<V>(vb + (t0 + i) * A.H, o);
             }
         }
     }
-    tcn_block_sums<2>(s);
+    block_sums<2>(s);
     if (threadIdx.x < 2) A.wsca[(((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * 2 + threadIdx.x] = s[threadIdx.x];
 }
 
@@ -180,7 +139,7 @@ __global__ __launch_bounds__(256) void tcn_dw_backward_z_kernel(const TcnDwArgs 
         for (int i = 0; i < kTcnR; ++i) {
             if (t0 + i < A.T) {
                 float g[V];
-                tcn_load<V>(A.gv + (b * A.T + t0 + i) * A.H + c0, g);
+                load_vec<V>(A.gv + (b * A.T + t0 + i) * A.H + c0, g);
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
                     const float zz = z[i][e];
@@ -188,7 +147,7 @@ __global__ __launch_bounds__(256) void tcn_dw_backward_z_kernel(const TcnDwArgs 
                     z[i][e] = zz > 0.f ? g[e] : a2 * g[e];
                     db[e] += (double)z[i][e];
                 }
-                tcn_store<V>(A.gz + (b * A.T + t0 + i) * A.H + c0, z[i]);
+                store_vec<V>(A.gz + (b * A.T + t0 + i) * A.H + c0, z[i]);
             } else {
 #pragma unroll
                 for (int e = 0; e < V; ++e) z[i][e] = 0.f;
@@ -206,7 +165,7 @@ __global__ __launch_bounds__(256) void tcn_dw_backward_z_kernel(const TcnDwArgs 
                 const long long r = t0 + i + off;
                 if (t0 + i < A.T && r >= 0 && r < A.T) {
                     float x[V];
-                    tcn_load<V>(ub + r * A.H, x);
+                    load_vec<V>(ub + r * A.H, x);
 #pragma unroll
                     for (int e = 0; e < V; ++e) acc[e] += (double)z[i][e] * (double)(x[e] > 0.f ? x[e] : a1 * x[e]);
                 }
@@ -215,7 +174,7 @@ __global__ __launch_bounds__(256) void tcn_dw_backward_z_kernel(const TcnDwArgs 
         tcn_wave_columns<V>(acc, live, col + (long long)k * A.H);
     }
     tcn_wave_columns<V>(db, live, col + (long long)A.K * A.H);
-    tcn_block_sums<1>(s);
+    block_sums<1>(s);
     if (threadIdx.x == 0) A.wsca[(((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * 2 + 1] = s[0];
 }
 
@@ -245,7 +204,7 @@ __global__ __launch_bounds__(256) void tcn_dw_backward_u_kernel(const TcnDwArgs 
                 const long long r = t0 + i + off;
                 if (t0 + i < A.T && r >= 0 && r < A.T) {
                     float g[V];
-                    tcn_load<V>(gzb + r * A.H, g);
+                    load_vec<V>(gzb + r * A.H, g);
 #pragma unroll
                     for (int e = 0; e < V; ++e) gp[i][e] = fmaf(wv[e], g[e], gp[i][e]);
                 }
@@ -255,41 +214,18 @@ __global__ __launch_bounds__(256) void tcn_dw_backward_u_kernel(const TcnDwArgs 
         for (int i = 0; i < kTcnR; ++i) {
             if (t0 + i < A.T) {
                 float x[V], o[V];
-                tcn_load<V>(A.u + (b * A.T + t0 + i) * A.H + c0, x);
+                load_vec<V>(A.u + (b * A.T + t0 + i) * A.H + c0, x);
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
                     o[e] = x[e] > 0.f ? gp[i][e] : a1 * gp[i][e];
                     s[0] += x[e] > 0.f ? 0. : (double)gp[i][e] * (double)x[e];
                 }
-                tcn_store<V>(A.gu + (b * A.T + t0 + i) * A.H + c0, o);
+                store_vec<V>(A.gu + (b * A.T + t0 + i) * A.H + c0, o);
             }
         }
     }
-    tcn_block_sums<1>(s);
+    block_sums<1>(s);
     if (threadIdx.x == 0) A.wsca[(((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * 2] = s[0];
-}
-
-// out[map(j)] = sum_s ws[s][j] for j < width: four chains s = g, g + 4, ... (ascending), combined ((0 + 1) + 2) + 3.
-// taps > 0: column j = k C + c of a depthwise slab goes to out[c taps + k] (k < taps: d weight [C, taps]) or out[C taps + c] (d bias).
-__global__ __launch_bounds__(256) void tcn_colreduce_kernel(const double* __restrict__ ws, long long slabs, long long width,
-                                                            float* __restrict__ out, int C, int taps) {
-    __shared__ double red[4][64];
-    const int jx = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const long long j = (long long)blockIdx.x * 64 + jx;
-    double s = 0.;
-    if (j < width)
-        for (long long sl = g; sl < slabs; sl += 4) s += ws[sl * width + j];
-    red[g][jx] = s;
-    __syncthreads();
-    if (g == 0 && j < width) {
-        const double tot = ((red[0][jx] + red[1][jx]) + red[2][jx]) + red[3][jx];
-        long long o = j;
-        if (taps > 0) {
-            const long long k = j / C, c = j % C;
-            o = k < taps ? c * taps + k : (long long)C * taps + c;
-        }
-        out[o] = (float)tot;
-    }
 }
 
 // One workgroup per group g: (s1, s2) = sum of the group's `slabs` partial pairs (thread-strided, ascending, then the workgroup sum).
@@ -302,7 +238,7 @@ __global__ __launch_bounds__(256) void tcn_group_finalize_kernel(const double* _
         s[0] += p[2 * i];
         s[1] += p[2 * i + 1];
     }
-    tcn_block_sums<2>(s);
+    block_sums<2>(s);
     if (threadIdx.x == 0) {
         const double m = s[0] / count;
         if (mode == 0) {
@@ -339,14 +275,14 @@ __global__ __launch_bounds__(256) void tcn_norm_stats_example_kernel(const float
     double s[2] = {0., 0.};
     for (long long i = i0 + (long long)threadIdx.x * V; i < i1; i += 256 * V) {
         float v[V];
-        tcn_load<V>(xb + i, v);
+        load_vec<V>(xb + i, v);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
             s[0] += (double)v[e];
             s[1] += (double)v[e] * (double)v[e];
         }
     }
-    tcn_block_sums<2>(s);
+    block_sums<2>(s);
     if (threadIdx.x < 2) ws[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = s[threadIdx.x];
 }
 
@@ -361,7 +297,7 @@ __global__ __launch_bounds__(256) void tcn_norm_row_kernel(const TcnNormArgs A, 
     double s1 = 0., s2 = 0.;
     for (int c = lane * V; c < A.C; c += 64 * V) {
         float v[V];
-        tcn_load<V>(A.x + row * A.C + c, v);
+        load_vec<V>(A.x + row * A.C + c, v);
         if (mode == 0) {
 #pragma unroll
             for (int e = 0; e < V; ++e) {
@@ -370,8 +306,8 @@ __global__ __launch_bounds__(256) void tcn_norm_row_kernel(const TcnNormArgs A, 
             }
         } else {
             float g[V], ga[V];
-            tcn_load<V>(A.gy + row * A.C + c, g);
-            tcn_load<V>(A.gamma + c, ga);
+            load_vec<V>(A.gy + row * A.C + c, g);
+            load_vec<V>(A.gamma + c, ga);
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 const float gx = g[e] * ga[e];
@@ -380,8 +316,8 @@ __global__ __launch_bounds__(256) void tcn_norm_row_kernel(const TcnNormArgs A, 
             }
         }
     }
-    s1 = tcn_wave_sum(s1);
-    s2 = tcn_wave_sum(s2);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
     if (lane == 0) {
         const double mean = s1 / A.C;
         if (mode == 0) {
@@ -409,8 +345,8 @@ __global__ __launch_bounds__(256) void tcn_norm_pointwise_kernel(const TcnNormAr
     const long long b = blockIdx.z;
     const long long t0 = (long long)blockIdx.x * kTcnRows + ty * kTcnR;
     float ga[V], be[V];
-    tcn_load<V>(A.gamma + c0, ga);
-    if (mode == 0) tcn_load<V>(A.beta + c0, be);
+    load_vec<V>(A.gamma + c0, ga);
+    if (mode == 0) load_vec<V>(A.beta + c0, be);
 #pragma unroll 4
     for (int i = 0; i < kTcnR; ++i) {
         if (t0 + i >= A.T) break;
@@ -418,18 +354,18 @@ __global__ __launch_bounds__(256) void tcn_norm_pointwise_kernel(const TcnNormAr
         const long long g = A.rows ? row : b;
         const float m = A.stats[2 * g], rs = A.stats[2 * g + 1];
         float x[V], o[V];
-        tcn_load<V>(A.x + row * A.C + c0, x);
+        load_vec<V>(A.x + row * A.C + c0, x);
         if (mode == 0) {
 #pragma unroll
             for (int e = 0; e < V; ++e) o[e] = fmaf(ga[e], (x[e] - m) * rs, be[e]);
         } else {
             const float g1 = A.gsum[2 * g], g2 = A.gsum[2 * g + 1];
             float gy[V];
-            tcn_load<V>(A.gy + row * A.C + c0, gy);
+            load_vec<V>(A.gy + row * A.C + c0, gy);
 #pragma unroll
             for (int e = 0; e < V; ++e) o[e] = rs * fmaf(-((x[e] - m) * rs), g2, gy[e] * ga[e] - g1);
         }
-        tcn_store<V>(A.y + row * A.C + c0, o);
+        store_vec<V>(A.y + row * A.C + c0, o);
     }
 }
 
@@ -447,7 +383,7 @@ __global__ __launch_bounds__(256) void tcn_norm_backward_reduce_kernel(const Tcn
     for (int e = 0; e < V; ++e) dg[e] = db[e] = 0.;
     if (live) {
         float ga[V];
-        tcn_load<V>(A.gamma + c0, ga);
+        load_vec<V>(A.gamma + c0, ga);
 #pragma unroll 4
         for (int i = 0; i < kTcnR; ++i) {
             if (t0 + i >= A.T) break;
@@ -455,8 +391,8 @@ __global__ __launch_bounds__(256) void tcn_norm_backward_reduce_kernel(const Tcn
             const long long g = A.rows ? row : b;
             const float m = A.stats[2 * g], rs = A.stats[2 * g + 1];
             float x[V], gy[V];
-            tcn_load<V>(A.x + row * A.C + c0, x);
-            tcn_load<V>(A.gy + row * A.C + c0, gy);
+            load_vec<V>(A.x + row * A.C + c0, x);
+            load_vec<V>(A.gy + row * A.C + c0, gy);
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 const float xh = (x[e] - m) * rs;
@@ -471,14 +407,8 @@ __global__ __launch_bounds__(256) void tcn_norm_backward_reduce_kernel(const Tcn
     double* __restrict__ col = A.wcol + ((long long)b * gridDim.x + blockIdx.x) * 2 * (long long)A.C + c0;
     tcn_wave_columns<V>(dg, live, col);
     tcn_wave_columns<V>(db, live, col + A.C);
-    tcn_block_sums<2>(s);
+    block_sums<2>(s);
     if (threadIdx.x < 2) A.wsca[(((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * 2 + threadIdx.x] = s[threadIdx.x];
-}
-
-static bool tcn_aligned(std::initializer_list<const void*> ptrs) {
-    for (const void* p : ptrs)
-        if (reinterpret_cast<unsigned long long>(p) & 15) return false;
-    return true;
 }
 
 struct TcnGrid {
@@ -500,14 +430,6 @@ static long long tcn_scalar_slabs(int64_t B, int64_t T, int32_t C) {
     return B * ((T + kTcnRows - 1) / kTcnRows) * ((C + 63) / 64);          // V = 1: the most channel blocks a launch can have
 }
 
-#define TCN_LAUNCH(kernel, vec, grid, st, ...)                                          \
-    do {                                                                                \
-        if (vec)                                                                        \
-            hipLaunchKernelGGL((kernel<4>), grid, dim3(256), 0, st, __VA_ARGS__);       \
-        else                                                                            \
-            hipLaunchKernelGGL((kernel<1>), grid, dim3(256), 0, st, __VA_ARGS__);       \
-    } while (0)
-
 }  // namespace ptmi
 
 using namespace ptmi;
@@ -525,7 +447,7 @@ int ptmi_tcn_depthwise_forward(const float* u, const float* slope_in, const floa
                                int32_t dilation, float eps, ptmi_stream_t stream) {
     PTMI_RETURN_IF(!u || !slope_in || !weight || !slope_out || !v || !stats || !workspace, PTMI_E_INVALID);
     PTMI_RETURN_IF(B < 1 || T < 1 || H < 1 || K < 1 || dilation < 1, PTMI_E_INVALID);
-    const bool vec = H % 4 == 0 && tcn_aligned({u, v});
+    const bool vec = H % 4 == 0 && aligned16({u, v});
     const TcnGrid g = tcn_grid(B, T, H, vec ? 4 : 1);
     PTMI_RETURN_IF(!g.ok, PTMI_E_UNSUPPORTED);
     TcnDwArgs A{};
@@ -534,7 +456,7 @@ int ptmi_tcn_depthwise_forward(const float* u, const float* slope_in, const floa
     A.T = T, A.H = H, A.K = K, A.d = dilation;
     A.front = (int)(((long long)dilation * (K - 1)) / 2);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    TCN_LAUNCH(tcn_dw_forward_kernel, vec, g.grid, st, A);
+    PTMI_LAUNCH_VEC(tcn_dw_forward_kernel, vec, g.grid, st, A);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(tcn_group_finalize_kernel, dim3((unsigned)B), dim3(256), 0, st, workspace, g.tiles * g.cblocks,
@@ -548,7 +470,7 @@ int ptmi_tcn_depthwise_backward(const float* gv, const float* u, const float* sl
     PTMI_RETURN_IF(!gv || !u || !slope_in || !weight || !slope_out || !gz || !gu || !dparams || !workspace, PTMI_E_INVALID);
     PTMI_RETURN_IF(B < 1 || T < 1 || H < 1 || K < 1 || dilation < 1, PTMI_E_INVALID);
     PTMI_RETURN_IF((long long)(K + 1) * H > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
-    const bool vec = H % 4 == 0 && tcn_aligned({gv, u, gz, gu});
+    const bool vec = H % 4 == 0 && aligned16({gv, u, gz, gu});
     const TcnGrid g = tcn_grid(B, T, H, vec ? 4 : 1);
     PTMI_RETURN_IF(!g.ok, PTMI_E_UNSUPPORTED);
     const long long width = (long long)(K + 1) * H;
@@ -560,14 +482,12 @@ int ptmi_tcn_depthwise_backward(const float* gv, const float* u, const float* sl
     A.front = (int)(((long long)dilation * (K - 1)) / 2);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
-    TCN_LAUNCH(tcn_dw_backward_z_kernel, vec, g.grid, st, A);
+    PTMI_LAUNCH_VEC(tcn_dw_backward_z_kernel, vec, g.grid, st, A);
     if ((rc = launch_status())) return rc;
-    TCN_LAUNCH(tcn_dw_backward_u_kernel, vec, g.grid, st, A);
+    PTMI_LAUNCH_VEC(tcn_dw_backward_u_kernel, vec, g.grid, st, A);
     if ((rc = launch_status())) return rc;
-    hipLaunchKernelGGL(tcn_colreduce_kernel, dim3((unsigned)((width + 63) / 64)), dim3(256), 0, st, A.wcol, B * g.tiles, width, dparams, H, K);
-    if ((rc = launch_status())) return rc;
-    hipLaunchKernelGGL(tcn_colreduce_kernel, dim3(1), dim3(256), 0, st, A.wsca, B * g.tiles * g.cblocks, 2LL, dparams + width, 0, 0);
-    return launch_status();
+    if ((rc = colreduce(A.wcol, B * g.tiles, width, StoreDepthwise{dparams, H, K}, st))) return rc;
+    return colreduce(A.wsca, B * g.tiles * g.cblocks, 2LL, StoreDepthwise{dparams + width, 0, 0}, st);
 }
 
 int64_t ptmi_tcn_norm_workspace_elems(int64_t B, int64_t T, int32_t C) {
@@ -581,20 +501,20 @@ int ptmi_tcn_norm_stats(const float* x, float* stats, double* workspace, int64_t
                         ptmi_stream_t stream) {
     PTMI_RETURN_IF(!x || !stats || B < 1 || T < 1 || C < 1, PTMI_E_INVALID);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool vec = C % 4 == 0 && tcn_aligned({x});
+    const bool vec = C % 4 == 0 && aligned16({x});
     if (rows) {
         const long long nrows = B * T;
         PTMI_RETURN_IF((nrows + 3) / 4 > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
         TcnNormArgs A{};
         A.x = x, A.T = T, A.C = C, A.rows = 1;
-        TCN_LAUNCH(tcn_norm_row_kernel, vec, dim3((unsigned)((nrows + 3) / 4)), st, A, nrows, eps, 0, stats);
+        PTMI_LAUNCH_VEC(tcn_norm_row_kernel, vec, dim3((unsigned)((nrows + 3) / 4)), st, A, nrows, eps, 0, stats);
         return launch_status();
     }
     PTMI_RETURN_IF(!workspace, PTMI_E_INVALID);
     const long long n = T * C;
     const long long chunks = (n + kTcnChunk - 1) / kTcnChunk;
     PTMI_RETURN_IF(chunks > 0x7fffffffLL || B > 65535, PTMI_E_UNSUPPORTED);
-    TCN_LAUNCH(tcn_norm_stats_example_kernel, vec, dim3((unsigned)chunks, (unsigned)B), st, x, n, workspace);
+    PTMI_LAUNCH_VEC(tcn_norm_stats_example_kernel, vec, dim3((unsigned)chunks, (unsigned)B), st, x, n, workspace);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(tcn_group_finalize_kernel, dim3((unsigned)B), dim3(256), 0, st, workspace, chunks, (double)n, eps, 0, stats);
@@ -604,12 +524,12 @@ int ptmi_tcn_norm_stats(const float* x, float* stats, double* workspace, int64_t
 int ptmi_tcn_norm_apply(const float* x, const float* stats, const float* gamma, const float* beta, float* y, int64_t B, int64_t T,
                         int32_t C, int32_t rows, ptmi_stream_t stream) {
     PTMI_RETURN_IF(!x || !stats || !gamma || !beta || !y || B < 1 || T < 1 || C < 1, PTMI_E_INVALID);
-    const bool vec = C % 4 == 0 && tcn_aligned({x, y, gamma, beta});
+    const bool vec = C % 4 == 0 && aligned16({x, y, gamma, beta});
     const TcnGrid g = tcn_grid(B, T, C, vec ? 4 : 1);
     PTMI_RETURN_IF(!g.ok, PTMI_E_UNSUPPORTED);
     TcnNormArgs A{};
     A.x = x, A.stats = stats, A.gamma = gamma, A.beta = beta, A.y = y, A.T = T, A.C = C, A.rows = rows ? 1 : 0;
-    TCN_LAUNCH(tcn_norm_pointwise_kernel, vec, g.grid, static_cast<hipStream_t>(stream), A, 0);
+    PTMI_LAUNCH_VEC(tcn_norm_pointwise_kernel, vec, g.grid, static_cast<hipStream_t>(stream), A, 0);
     return launch_status();
 }
 
@@ -617,7 +537,7 @@ int ptmi_tcn_norm_backward(const float* gy, const float* x, const float* stats, 
                            float* gsum, double* workspace, int64_t B, int64_t T, int32_t C, int32_t rows, ptmi_stream_t stream) {
     PTMI_RETURN_IF(!gy || !x || !stats || !gamma || !dx || !dparams || !gsum || !workspace, PTMI_E_INVALID);
     PTMI_RETURN_IF(B < 1 || T < 1 || C < 1, PTMI_E_INVALID);
-    const bool vec = C % 4 == 0 && tcn_aligned({gy, x, dx, gamma});
+    const bool vec = C % 4 == 0 && aligned16({gy, x, dx, gamma});
     const TcnGrid g = tcn_grid(B, T, C, vec ? 4 : 1);
     const long long nrows = B * T;
     PTMI_RETURN_IF(!g.ok || (nrows + 3) / 4 > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
@@ -627,17 +547,16 @@ int ptmi_tcn_norm_backward(const float* gy, const float* x, const float* stats, 
     A.wsca = workspace + B * g.tiles * 2 * C;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
-    TCN_LAUNCH(tcn_norm_backward_reduce_kernel, vec, g.grid, st, A);
+    PTMI_LAUNCH_VEC(tcn_norm_backward_reduce_kernel, vec, g.grid, st, A);
     if ((rc = launch_status())) return rc;
-    hipLaunchKernelGGL(tcn_colreduce_kernel, dim3((unsigned)((2LL * C + 63) / 64)), dim3(256), 0, st, A.wcol, B * g.tiles, 2LL * C, dparams, 0, 0);
-    if ((rc = launch_status())) return rc;
+    if ((rc = colreduce(A.wcol, B * g.tiles, 2LL * C, StoreDepthwise{dparams, 0, 0}, st))) return rc;
     if (rows)
-        TCN_LAUNCH(tcn_norm_row_kernel, vec, dim3((unsigned)((nrows + 3) / 4)), st, A, nrows, 0.f, 1, gsum);
+        PTMI_LAUNCH_VEC(tcn_norm_row_kernel, vec, dim3((unsigned)((nrows + 3) / 4)), st, A, nrows, 0.f, 1, gsum);
     else
         hipLaunchKernelGGL(tcn_group_finalize_kernel, dim3((unsigned)B), dim3(256), 0, st, A.wsca, g.tiles * g.cblocks,
                            (double)T * (double)C, 0.f, 1, gsum);
     if ((rc = launch_status())) return rc;
-    TCN_LAUNCH(tcn_norm_pointwise_kernel, vec, g.grid, st, A, 1);
+    PTMI_LAUNCH_VEC(tcn_norm_pointwise_kernel, vec, g.grid, st, A, 1);
     return launch_status();
 }
 

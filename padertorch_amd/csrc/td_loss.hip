@@ -11,10 +11,10 @@
 // the closed forms (done on the host side on [B, K*K+4K] tensors).
 //
 // Products of two fp32 values are exact in fp64 and the sums are kept in fp64 (per thread -> wave ->
-// workgroup -> fixed-order reduction over chunks: bitwise reproducible), so cancellation in
+// workgroup in the order reduce.h defines -> sequential reduction over chunks: bitwise reproducible), so cancellation in
 // See - Set^2/Stt (high SI-SDR) costs nothing; the fp64 vector rate is far above what 8 TB/s of
 // fp32 input needs (K^2 + 4K fused multiply-adds per 2K loaded values).
-#include "common.h"
+#include "reduce.h"
 
 namespace ptmi {
 
@@ -30,12 +30,6 @@ struct TdArgs {
     int K, nchunks, vec;        // vec: every row start is 16-byte aligned
     double* ws;                 // [B][nchunks][NS]
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // stats layout per example: Set[K][K] | See[K] | Stt[K] | Se[K] | St[K]
 template <int K>
@@ -275,17 +269,6 @@ __global__ __launch_bounds__(256) void td_lincomb_kernel(const TdLinArgs P) {
     }
 }
 
-static long long pick_chunk(long long batch, long long T) {
-    // ~2048 workgroups per call when the input allows it; 1024..65536 samples each
-    long long chunk = (batch * T + 2047) / 2048;
-    chunk = (chunk + 1023) / 1024 * 1024;
-    if (chunk < 1024) chunk = 1024;
-    if (chunk > 65536) chunk = 65536;
-    return chunk;
-}
-
-static bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 template <int K>
 static int launch_lincomb(const TdLinArgs& P, long long batch, hipStream_t st) {
     const unsigned nchunks = (unsigned)((P.T + P.chunk - 1) / P.chunk);
@@ -326,7 +309,7 @@ int ptmi_td_pair_stats(const float* est, const float* tgt, const int32_t* length
     A.chunk = pick_chunk(batch, T);
     A.K = K;
     A.nchunks = (int)((T + A.chunk - 1) / A.chunk);
-    A.vec = T >= 4 && aligned16(est) && aligned16(tgt) && A.eb % 4 == 0 && A.ek % 4 == 0 && A.tb % 4 == 0 &&
+    A.vec = T >= 4 && aligned16({est, tgt}) && A.eb % 4 == 0 && A.ek % 4 == 0 && A.tb % 4 == 0 &&
             A.tk % 4 == 0;
     A.ws = workspace;
     const dim3 grid((unsigned)A.nchunks, (unsigned)batch);
@@ -368,7 +351,7 @@ int ptmi_td_lincomb(const float* x, const float* y, const int32_t* lengths, cons
     P.ob = strides[4];
     P.ok = strides[5];
     P.chunk = pick_chunk(batch, T);
-    P.vec = aligned16(x) && aligned16(y) && aligned16(out) && P.xb % 4 == 0 && P.xk % 4 == 0 && P.yb % 4 == 0 &&
+    P.vec = aligned16({x, y, out}) && P.xb % 4 == 0 && P.xk % 4 == 0 && P.yb % 4 == 0 &&
             P.yk % 4 == 0 && P.ob % 4 == 0 && P.ok % 4 == 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (K) {

@@ -15,12 +15,13 @@ same two throughout:
   DEPTHWISE_PATHS   <4> kernels with blockIdx.y = 1 (H = 512) and with a last channel block of one live lane group (H = 260); T on a tile
                     boundary (64, 128) and one row past it (65); every off-centre tap in the padding (d = 128 > T = 5) on the vector and
                     the scalar path; T = 1; even K with front != end and B > 1; K = 5; more than 256 (tile, channel block) partials, so
-                    that tcn_group_finalize_kernel and the scalar tcn_colreduce chains take a second trip (325 scalar, 257 vector);
+                    that tcn_group_finalize_kernel and the scalar chains of colreduce_kernel (csrc/reduce.h) take a second trip (325
+                    scalar, 257 vector);
                     bias = None; needs_input_grad of one input alone
   NORM_PATHS        the same block shapes for apply / backward; the second trip of tcn_norm_row_kernel<4>'s c += 64 V loop (C = 512, 516);
                     259 chunks of the per-example statistics pass and 325 backward partials through the finalize loop; T = C = 1;
                     eps = 1e-3 / 1e-8 through tcn_norm_stats, tcn_norm_row_kernel and the fused finalize of the depthwise launch
-  alignment         contiguous views one float into their storage (data_ptr % 16 == 4) at H = C = 128, 512: tcn_aligned() picks <1>
+  alignment         contiguous views one float into their storage (data_ptr % 16 == 4) at H = C = 128, 512: aligned16() picks <1>
                     although C % 4 == 0, per launch: forward on (u, v), backward on (gv, u, gz, gu), norm on (x, y, gamma, beta) /
                     (gy, x, dx, gamma); v, gu, y, dx must equal the <4> results bit for bit, the sentinels around the views stay
   statistics        var = 0 behind fmax(., 0) (constant example, constant row): y = beta exactly, rstd = eps^-1/2; mean 1e3 spreads away

@@ -370,6 +370,24 @@ def test_norm_residual_against_fp64(N):
     close('y without lengths', free, torch.nn.functional.layer_norm(z.double(), (N,), gamma.double(), beta.double(), 1e-5) + res.double(), VALUE)
 
 
+SLAB_ROWS = 128             # kDpSlabRows of csrc/dprnn.hip: rows per partial of the column sums
+
+
+@pytest.mark.parametrize('C', [5, 70])
+def test_colsum_over_many_slabs_against_fp64(C):
+    """5 1/4 slabs of rows and a width that is no multiple of 64: every one of the four chains of colreduce_kernel (csrc/reduce.h) adds
+    more than one partial, the last slab and the last column block are ragged.  Both store forms: one output (the fc bias) and the pair
+    (b_ih and b_hh), from a contiguous tensor and from columns of a wider one.  The sums are fp64 inside and rounded once: VALUE."""
+    rows = 5 * SLAB_ROWS + SLAB_ROWS // 4 + 5
+    torch.manual_seed(C)
+    wide = torch.randn(rows, C + 3).cuda()
+    for name, x in (('contiguous', wide[:, :C].contiguous()), ('strided', wide[:, 2:2 + C])):
+        one = torch.ops.ptmi.dprnn_colsum(x)
+        a, b = torch.ops.ptmi.dprnn_colsum_pair(x)
+        close(f'colsum {name} C={C}', one, x.cpu().double().sum(0), VALUE)
+        assert a.data_ptr() != b.data_ptr() and torch.equal(a, one) and torch.equal(b, one)
+
+
 # ---------------------------------------------------------------------------------------------------- full width
 def _block_fp64(block, x, S_b, K, P):
     """One DPRNN block on ``x [B, S, K, N]`` in fp64 on the CPU from torch.nn.LSTM / Linear / LayerNorm with the block's parameters;

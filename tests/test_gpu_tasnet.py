@@ -221,8 +221,10 @@ def _lengths_of(mode, B, E):
 
 
 @pytest.mark.parametrize('mode', ['none', 'full', 'partial32', 'partial64'])
-@pytest.mark.parametrize('shape', [(2, 256, 70), (1, 5, 65), (3, 64, 1), (2, 260, 64)], ids=_id)
+@pytest.mark.parametrize('shape', [(2, 256, 70), (1, 5, 65), (3, 64, 1), (2, 260, 64), (2, 37, 201)], ids=_id)
 def test_entry_norm_against_fp64(shape, mode):
+    """(2, 37, 201): 14 partials (B x tiles of 32 frames) of width 2 N = 74 through colreduce_kernel (csrc/reduce.h): every one of its four
+    chains adds more than one partial, and its second column block ends inside the block."""
     from padertorch_amd.ops import tasnet as glue
     B, N, E = shape
     gen = torch.Generator().manual_seed(151)
