@@ -206,20 +206,26 @@ int ptmi_lstm_backward(const float* gates, const float* c, const float* c0, cons
                        float* dc_state, const int32_t* batch_sizes, const int64_t* offsets, int32_t T,
                        int32_t max_batch, int32_t H, int32_t ndir, ptmi_stream_t stream);
 
-/* Persistent forward recurrence: ONE launch for all T steps; W_hh stays in registers and the steps
- * are chained by write-through stores + per-step arrival counters (see csrc/lstm.hip).  Same
- * results as ptmi_lstm_forward.  batch_sizes_dev / offsets_dev are DEVICE copies here; flags is a
- * device scratch of ptmi_lstm_scratch_elems(T, ndir, max_batch, H, 0) uint32: the tile-major copy of hy the
- * workgroups hand to each other, ptmi_lstm_flags_elems(T, ndir, max_batch) arrival counters (zeroed by
- * the call) and, as the LAST 8 words, the error words (non-zero after the call = a bounded spin ran
- * out).  KP must be H rounded up to 16.  Returns PTMI_E_UNSUPPORTED when the configuration cannot be
- * kept resident (caller falls back to ptmi_lstm_forward).
- * The default kernels (csrc/lstm_split.hip; ptmi_lstm_split_enabled() != 0) evaluate h W_hh^T as three fp16 MFMA
- * products of (hi, lo) operand halves with fp32 accumulation (fp32-equivalent result); w_hh_amax = device word
- * from ptmi_absmax over w_hh_pad (NULL: |W_hh| within fp16's range as it is).  The backward kernel splits into
- * bf16 halves (no scale) and leaves max |dgates| (float bits) in the word right behind the bias gradient.
- * PTMI_LSTM_F32=1 in the environment selects the exact-fp32 MFMA kernels of round 1. */
+/* ---- Persistent recurrence: ONE launch per layer and pass (host side csrc/lstm.hip, kernels csrc/lstm_split.hip) ----
+ * A workgroup's slice of W_hh stays in registers for all T steps.  The per-step product is evaluated as three 16-bit MFMA
+ * products of (hi, lo) operand halves with fp32 accumulation (fp32-equivalent result): forward fp16 halves of 2^10 h and of the
+ * scaled weights (w_hh_amax = device word from ptmi_absmax over w_hh_pad; NULL: |W_hh| within fp16's range as it is), backward
+ * bf16 halves (no scale).  The steps are chained through 16-bit hand-off planes at the START of the scratch, synchronised by
+ * their data (data-as-flag): every 16-bit value of the planes starts out as 0xFFFF - a pattern no conversion to fp16 / bf16
+ * produces -, producers only store, consumers re-request an operand tile until none of the values they are going to use is the
+ * pattern.  Every poll is bounded.  Same results as ptmi_lstm_forward / ptmi_lstm_backward.  With PTMI_LSTM_F32 in the
+ * environment (ptmi_lstm_split_enabled() == 0) the persistent entries refuse every configuration, and the callers run the
+ * exact-fp32 step-per-launch kernels above.
+ *
+ * batch_sizes_dev / offsets_dev are DEVICE copies here.  `flags` is the launch's device scratch of
+ * ptmi_lstm_scratch_elems(T, ndir, max_batch, H, backward) uint32:
+ *   forward    [ hand-off planes of hy | ptmi_lstm_flags_elems(T, ndir, max_batch) words ]
+ *   backward   [ hand-off planes of dgates | BIAS GRADIENT [ndir][4H] floats (sum of dgates over all rows, out) | 8 words, word 0:
+ *                float bits of max |dgates| (out) | ptmi_lstm_flags_elems(T, ndir, max_batch) words ]
+ * The LAST 8 words are the error words in both (non-zero after the call = a bounded poll ran out; ptmi_lstm_set_error_sink
+ * counts such launches per device).  The words in front of them are reserved and zeroed (the slots of the former flag protocol). */
 int64_t ptmi_lstm_flags_elems(int32_t T, int32_t ndir, int32_t max_batch);
+int64_t ptmi_lstm_scratch_elems(int32_t T, int32_t ndir, int32_t max_batch, int32_t H, int32_t backward);
 /* ptmi_lstm_weight_prep (csrc/lstm_prep.hip): the operand forms of ONE (bi)directional LSTM layer's parameters
  * (torch.nn.LSTM layout, padertorch/contrib/examples/source_separation/pit/model.py:60-66) in one launch:
  *   w_ih / w_hh / b_ih / b_hh  HOST arrays of ndir device pointers: [4H, I], [4H, H], [4H], [4H] per direction
@@ -237,102 +243,91 @@ int ptmi_lstm_weight_prep(const float* const* w_ih, const float* const* w_hh, co
  * launch's own error word in its scratch): ONE word for the host to watch instead of one per call. */
 int ptmi_lstm_set_error_sink(uint32_t* word);
 int ptmi_lstm_split_enabled(void);
-/* ptmi_lstm_handoff_cols: columns per direction (H resp. 4H rounded up to 32) of the 16-bit hand-off planes the persistent
- * split kernels leave at the START of their scratch - forward (backward = 0): fp16 (hi, lo) halves of 2^10 h, backward: bf16
- * halves of dgates -, as [T][16-row tile][direction][cols / 32][hi | lo][64 chunks of 8 values] in the fragment order of
- * ptmi_gemm_planes: for a batch of equal-length sequences whose size is a multiple of 16 this IS the A operand
- * (rows = packed rows, k = direction-major columns) of the dense GEMM that follows.  0: these kernels do not run for this H
- * (PTMI_LSTM_F32, or a layer too wide for their register budget). */
+/* Queries: what the persistent launches of a configuration do (CU count of the current device).
+ * ptmi_lstm_handoff_cols: columns per direction (H resp. 4H rounded up to 32) of the hand-off planes - forward (backward = 0):
+ *   fp16 (hi, lo) halves of 2^10 h, backward: bf16 halves of dgates -, laid out as [T][16-row tile][direction][cols / 32][hi | lo]
+ *   [64 chunks of 8 values] in the fragment order of ptmi_gemm_planes: for a batch of equal-length sequences whose size is a multiple of
+ *   16 this IS the A operand (rows = packed rows, k = direction-major columns) of the dense GEMM that follows.  0: no persistent
+ *   kernel for this H (PTMI_LSTM_F32, or a layer too wide for the kernels' register budget).
+ * ptmi_lstm_backward_planes_ok: != 0 when the backward launch can emit dgates^T planes (dgates_t below): a configuration it runs
+ *   at all, equal-length sequences (rows == T * max_batch), max_batch a multiple of 16.
+ * ptmi_lstm_forward_fills: the value to pass as `prefilled` to the backward call of a layer whose forward call got that backward
+ *   call's scratch as `backward_scratch` - 2: the forward launch writes the pattern into the backward planes and zeros into the
+ *   words behind them (an otherwise idle wavefront of every workgroup, a slice per time step, i.e. for free), the backward call
+ *   enqueues nothing in front of its recurrence kernel; 0: it does not, `backward_scratch` is ignored. */
 int32_t ptmi_lstm_handoff_cols(int32_t H, int32_t backward);
+int32_t ptmi_lstm_backward_planes_ok(int32_t T, int32_t ndir, int32_t max_batch, int64_t rows, int32_t H);
+int ptmi_lstm_forward_fills(int32_t T, int32_t ndir, int32_t max_batch, int32_t H);
+
+/* Persistent forward recurrence.  Arguments as ptmi_lstm_forward, and
+ *   step_masks        NULL, or a ROW-SLOT batch: several sequences lie END TO END in one row slot, so that every one of the (at most
+ *                     64) slots works in (nearly) every time step - a recurrence costs its number of steps, whatever the number of rows
+ *                     up to 32 (64) per step, so a ragged batch packed this way takes total frames / slots steps instead of the longest
+ *                     sequence's.  Layout: uniform, row(t, slot) = t * max_batch + slot, every such row exists in all buffers;
+ *                     step_masks [T][3] uint64 (device): rows alive at time index t, rows whose sequence STARTS at t, rows whose
+ *                     sequence ENDS at t (bit b = slot b).  A sequence start resets (h, c) to zero in the forward direction, a
+ *                     sequence end in the reverse direction; idle rows are neither computed nor handed on (hy / c of idle rows are
+ *                     not written: hand in zeroed buffers; their gate gradients come out as zeros, and their rows of the hand-off
+ *                     planes as zeros too, so that for max_batch % 16 == 0 the planes are the GEMM operands they are for
+ *                     equal-length batches).  Same results per sequence as one sequence per row (torch.nn.LSTM on a
+ *                     PackedSequence, pit/model.py:60-66,97).
+ *   prefilled         != 0: the caller has filled the planes with the pattern (32-bit words 0xFFFFFFFF) on a stream ordered before
+ *                     this one; the call then only zeroes the words behind them
+ *   backward_scratch  NULL, or the scratch of this layer's backward call (ptmi_lstm_forward_fills)
+ * Refused, with NOTHING enqueued:
+ *   PTMI_E_INVALID      gates, hy, c, w_hh_pad, batch_sizes_dev, offsets_dev or flags NULL; T, max_batch, H or rows < 1; ndir not 1 or 2
+ *   PTMI_E_UNSUPPORTED  step_masks with c0, with rows != T * max_batch or with max_batch > 64; H % 4 != 0; KP != H rounded up to 16;
+ *                       a configuration the kernels cannot keep resident (the caller falls back to ptmi_lstm_forward);
+ *                       rows * ndir * H * 4 bytes >= 2^31 */
 int ptmi_lstm_forward_persistent(float* gates, float* hy, float* c, const float* c0, const float* w_hh_pad,
                                  const uint32_t* w_hh_amax, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                 uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows, int32_t H, int32_t KP,
-                                 int32_t ndir, int32_t prefilled, uint32_t* backward_scratch, ptmi_stream_t stream);
+                                 const uint64_t* step_masks, uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows,
+                                 int32_t H, int32_t KP, int32_t ndir, int32_t prefilled, uint32_t* backward_scratch,
+                                 ptmi_stream_t stream);
 
-/* Persistent backward-through-time (mirror of ptmi_lstm_forward_persistent; same results as
- * ptmi_lstm_backward; no dc_state scratch: the cell-state gradient stays in registers).  `flags` is a device
- * scratch of ptmi_lstm_scratch_elems(T, ndir, max_batch, H, 1) uint32: a tile-major copy of dgates that the
- * workgroups hand to each other (16 x 16 tiles, one contiguous KB per load), then [ndir][4H] floats that
- * receive the BIAS GRADIENT (sum of dgates over all rows, out), then the ptmi_lstm_flags_elems arrival
- * counters (both zeroed by the call), then the 8 error words (still the LAST 8 words). */
-int64_t ptmi_lstm_scratch_elems(int32_t T, int32_t ndir, int32_t max_batch, int32_t H, int32_t backward);
-int ptmi_lstm_backward_persistent(const float* gates, const float* c, const float* c0, const float* dhy, const float* w_hh_t,
-                                  float* dgates, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                  uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows, int32_t H,
-                                  int32_t ndir, int32_t prefilled, ptmi_stream_t stream);
-/* The same recurrence cut in time: processes the steps [s_begin, s_end) of the T processing steps (step s handles
- * time index T-1-s in direction 0, s in direction 1).  Ranges must be launched in order on one stream with the same
- * scratch; the first (s_begin == 0) zeroes it, dc_carry (device fp32 [ndir, max_batch, H]) takes the cell-state
- * gradient across a cut.  After the range [0, s) the gate gradients of direction 0 are complete for time indices
- * >= T - s and of direction 1 for time indices < s: their weight-gradient GEMMs can run under the next range.
- * Split kernels only (PTMI_E_UNSUPPORTED otherwise). */
-int ptmi_lstm_backward_persistent_range(const float* gates, const float* c, const float* c0, const float* dhy,
-                                        const float* w_hh_t, float* dgates, const int32_t* batch_sizes_dev,
-                                        const int64_t* offsets_dev, uint32_t* flags, float* dc_carry, int32_t T,
-                                        int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin,
-                                        int32_t s_end, int32_t prefilled, ptmi_stream_t stream);
-/* The same launch with the gate gradients ALSO (or only) leaving the kernel as the operand of the weight-gradient GEMMs
- * dW_ih = dgates^T x, dW_hh = dgates^T h_prev (torch.nn.LSTM backward inside pit/model.py:60-66,97): bf16 (hi, lo) planes of
- * dgates^T per direction, [ndir][4H / 16 column tiles][ceil(rows / 32) k blocks][hi | lo][64 chunks of 8 values] = exactly what
- * ptmi_pack_planes_t_bf16 makes of one direction's [rows, 4H] block, i.e. operand A of ptmi_gemm_planes_bf16(m = 4H, k = rows)
- * at byte offset direction * ptmi_planes_elems(4H, rows) * 2.  No row-major fp32 store, no transposing pack pass.
- *   dgates_t   ndir * ptmi_planes_elems(4H, range_rows) uint16 (16-byte aligned) or NULL, range_rows = (s_end - s_begin) *
- *              max_batch: the rows of THIS launch's step range (all rows for [0, T)) - for the forward direction the time
- *              indices T - s_end .. T - s_begin - 1, for the reverse direction s_begin .. s_end - 1 -; the call writes every value
- *   dgates     may be NULL when dgates_t is given (the hand-off copy in `flags` still serves dx = dgates W_ih)
- * Only for batches of equal-length sequences whose size is a multiple of 16 on the split kernels:
- * ptmi_lstm_backward_planes_ok(...) != 0; PTMI_E_UNSUPPORTED otherwise. */
-/* The whole backward recurrence with gradients through BOTH ends of the state (torch.nn.LSTM returns (h_n, c_n) with their graph,
- * padertorch/modules/recurrent.py:42 carries them): dc_n [ndir][max_batch][H] (or NULL) = gradient w.r.t. the final cell state, added
- * to the cell-state gradient at every sequence's last step; dc_0 [ndir][max_batch][H] (or NULL) receives the gradient w.r.t. the
- * initial cell state.  (The final / initial HIDDEN states' gradients travel through dhy resp. dgates W_hh on the caller's side.)
- * Split kernels only. */
-int ptmi_lstm_backward_persistent_states(const float* gates, const float* c, const float* c0, const float* dhy, const float* dc_n,
-                                         const float* w_hh_t, float* dgates, const int32_t* batch_sizes_dev,
-                                         const int64_t* offsets_dev, uint32_t* flags, float* dc_0, int32_t T, int32_t max_batch,
-                                         int64_t rows, int32_t H, int32_t ndir, int32_t prefilled, ptmi_stream_t stream);
-/* Row-slot batches: several sequences lie END TO END in one row slot, so that every one of the (at most 64) row slots works in
- * (nearly) every time step - a recurrence costs its number of steps, whatever the number of rows up to 32 (64) per step, so a ragged
- * batch packed this way takes total frames / slots steps instead of the longest sequence's.  Layout: uniform, row(t, slot) = t *
- * max_batch + slot, every such row exists in all buffers; step_masks [T][3] uint64 (device): rows alive at time index t, rows whose
- * sequence STARTS at t, rows whose sequence ENDS at t (bit b = slot b).  A sequence start resets (h, c) to zero in the forward
- * direction, a sequence end in the reverse direction; idle rows are neither computed nor handed on (hy / c of idle rows are not
- * written: hand in zeroed buffers; their gate gradients come out as zeros, and their rows of the hand-off planes as zeros too, so
- * that for max_batch % 16 == 0 the planes are the GEMM operands they are for equal-length batches: ptmi_lstm_handoff_cols; the
- * backward call takes dgates_t like ptmi_lstm_backward_persistent_planes, dgates may then be NULL).  Same results per sequence as one sequence per row
- * (torch.nn.LSTM on a PackedSequence, pit/model.py:60-66,97).  Data-as-flag split kernels only (PTMI_E_UNSUPPORTED otherwise); no
- * initial states. */
-int ptmi_lstm_forward_persistent_slots(float* gates, float* hy, float* c, const float* c0, const float* w_hh_pad,
-                                       const uint32_t* w_hh_amax, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                       const uint64_t* step_masks, uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows,
-                                       int32_t H, int32_t KP, int32_t ndir, int32_t prefilled, uint32_t* backward_scratch,
-                                       ptmi_stream_t stream);
-int ptmi_lstm_backward_persistent_slots(const float* gates, const float* c, const float* dhy, const float* w_hh_t, float* dgates,
-                                        uint16_t* dgates_t, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                        const uint64_t* step_masks, uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows,
-                                        int32_t H, int32_t ndir, int32_t prefilled, ptmi_stream_t stream);
-int32_t ptmi_lstm_backward_planes_ok(int32_t T, int32_t ndir, int32_t max_batch, int64_t rows, int32_t H);
-int ptmi_lstm_backward_persistent_planes(const float* gates, const float* c, const float* c0, const float* dhy,
-                                         const float* w_hh_t, float* dgates, uint16_t* dgates_t, const int32_t* batch_sizes_dev,
-                                         const int64_t* offsets_dev, uint32_t* flags, float* dc_carry, int32_t T,
-                                         int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin, int32_t s_end,
-                                         int32_t prefilled, ptmi_stream_t stream);
-/* Data-as-flag hand-off (the split kernels' protocol wherever their tile shapes allow it): the planes at the
- * start of the scratch start out as 0xFFFF in every 16-bit value - a pattern no conversion to fp16 / bf16 produces -, producers
- * only store, consumers re-request an operand tile until none of the values they are going to use is the pattern.  The
- * persistent calls fill the planes themselves (prefilled = 0) unless the caller has done it with ptmi_lstm_scratch_prefill
- * on any stream it orders before the launch (prefilled = 1: the fill then runs next to earlier work instead of in front of
- * the recurrence).  ptmi_lstm_scratch_prefill returns 1 when it has filled, 0 when the launch for this configuration does
- * not use the pattern (nothing done; pass prefilled = 0), < 0 on error. */
-int ptmi_lstm_scratch_prefill(uint32_t* scratch, int32_t T, int32_t ndir, int32_t max_batch, int32_t H, int32_t backward,
-                              ptmi_stream_t stream);
-/* backward_scratch of ptmi_lstm_forward_persistent (NULL: none): the scratch the caller will hand to this layer's
- * ptmi_lstm_backward_persistent.  When ptmi_lstm_forward_fills(T, ndir, max_batch, H) != 0 the forward launch writes the
- * pattern into its planes itself - an otherwise idle wavefront of every workgroup, a slice per time step, i.e. for free -
- * and the caller passes the returned value as `prefilled` to the backward launch: 2 = the planes AND the words behind them
- * (bias sums, maximum word, arrival slots, error words: zeroed) are ready, the backward call enqueues nothing in front of its
- * recurrence kernel (round 6; 1, until then: the planes only).  Otherwise the pointer is ignored. */
-int ptmi_lstm_forward_fills(int32_t T, int32_t ndir, int32_t max_batch, int32_t H);
+/* Persistent backward-through-time.  Arguments as ptmi_lstm_backward (no dc_state scratch: the cell-state gradient stays in
+ * registers), step_masks as above, and
+ *   s_begin, s_end    the launch processes the steps [s_begin, s_end) of the T processing steps (step s handles time index T-1-s in
+ *                     direction 0, s in direction 1); [0, T) is the whole recurrence.  Ranges must be launched in order on one stream
+ *                     with the same scratch; the first (s_begin == 0) sets the scratch up.  After the range [0, s) the gate gradients
+ *                     of direction 0 are complete for time indices >= T - s and of direction 1 for time indices < s: their
+ *                     weight-gradient GEMMs can run under the next range.
+ *   dc_carry          NULL, or device fp32 [ndir, max_batch, H]: takes the cell-state gradient across a cut between ranges; after
+ *                     the last range it is the gradient w.r.t. the initial cell state c0
+ *   dc_n              NULL, or device fp32 [ndir, max_batch, H]: gradient w.r.t. the FINAL cell state, added to the cell-state
+ *                     gradient at every sequence's last step (torch.nn.LSTM returns (h_n, c_n) with their graph,
+ *                     padertorch/modules/recurrent.py:42 carries them; the final / initial HIDDEN states' gradients travel through
+ *                     dhy resp. dgates W_hh on the caller's side)
+ *   dgates_t          NULL, or ndir * ptmi_planes_elems(4H, range_rows) uint16, range_rows = (s_end - s_begin) * max_batch: the gate
+ *                     gradients of THIS launch's step range - for the forward direction the time indices T - s_end .. T - s_begin - 1,
+ *                     for the reverse direction s_begin .. s_end - 1 - as the operand of the weight-gradient GEMMs dW_ih = dgates^T x,
+ *                     dW_hh = dgates^T h_prev (torch.nn.LSTM backward inside pit/model.py:60-66,97): bf16 (hi, lo) planes of dgates^T
+ *                     per direction, [ndir][4H / 16 column tiles][ceil(range_rows / 32) k blocks][hi | lo][64 chunks of 8 values] =
+ *                     exactly what ptmi_pack_planes_t_bf16 makes of one direction's [rows, 4H] block, i.e. operand A of
+ *                     ptmi_gemm_planes_bf16(m = 4H, k = rows) at byte offset direction * ptmi_planes_elems(4H, rows) * 2.  The call
+ *                     writes every value.  No transposing pack pass.
+ *   dgates            may be NULL when dgates_t is given (the hand-off copy in `flags` still serves dx = dgates W_ih): no row-major
+ *                     fp32 store then
+ *   prefilled         0: the call sets its scratch up itself (one launch in front of the recurrence); 1: the caller has filled the
+ *                     planes with the pattern, the call zeroes the words behind them; 2: those are zero as well
+ *                     (ptmi_lstm_forward_fills), the call enqueues its recurrence only.  Read by the first range.
+ * Refused, with NOTHING enqueued (a "partial range" is any [s_begin, s_end) other than [0, T)):
+ *   PTMI_E_INVALID      gates, c, dhy, w_hh_t, batch_sizes_dev, offsets_dev or flags NULL; T, max_batch, H or rows < 1; ndir not 1 or 2
+ *   PTMI_E_INVALID      dgates and dgates_t both NULL
+ *   PTMI_E_INVALID      dgates_t not 16-byte aligned
+ *   PTMI_E_INVALID      s_begin < 0, s_end > T or s_begin >= s_end
+ *   PTMI_E_INVALID      a partial range without dc_carry
+ *   PTMI_E_INVALID      dc_n with a partial range
+ *   PTMI_E_UNSUPPORTED  dc_n with step_masks
+ *   PTMI_E_UNSUPPORTED  step_masks with c0, with rows != T * max_batch, with max_batch > 64 or with a partial range
+ *   PTMI_E_UNSUPPORTED  dgates_t where ptmi_lstm_backward_planes_ok(...) == 0
+ *   PTMI_E_UNSUPPORTED  H % 4 != 0; a configuration the kernels cannot keep resident (the caller falls back to
+ *                       ptmi_lstm_backward); rows * ndir * 4H * 4 bytes >= 2^31 */
+int ptmi_lstm_backward_persistent(const float* gates, const float* c, const float* c0, const float* dhy, const float* dc_n,
+                                  const float* w_hh_t, float* dgates, uint16_t* dgates_t, const int32_t* batch_sizes_dev,
+                                  const int64_t* offsets_dev, const uint64_t* step_masks, uint32_t* flags, float* dc_carry,
+                                  int32_t T, int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin,
+                                  int32_t s_end, int32_t prefilled, ptmi_stream_t stream);
 
 /* ---- (log-)mel features ----------------------------------------------------------------------------
  * Replaces MelTransform.forward (padertorch/contrib/je/modules/features.py:297-330: spectrogram @

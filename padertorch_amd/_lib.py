@@ -122,23 +122,12 @@ SIGNATURES = {
     'ptmi_lstm_set_error_sink': (c_int, [_P]),
     'ptmi_lstm_split_enabled': (c_int, []),
     'ptmi_lstm_handoff_cols': (c_int32, [c_int32, c_int32]),
-    'ptmi_lstm_forward_persistent': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32, c_int32,
+    'ptmi_lstm_forward_persistent': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32, c_int32,
                                              c_int32, c_int32, _P, _P]),
     'ptmi_lstm_forward_fills': (c_int, [c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_lstm_backward_persistent': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32,
-                                              c_int32, c_int32, _P]),
-    'ptmi_lstm_backward_persistent_range': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32,
-                                                    c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_lstm_forward_persistent_slots': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32, c_int32,
-                                                   c_int32, c_int32, _P, _P]),
-    'ptmi_lstm_backward_persistent_slots': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32, c_int32,
-                                                    c_int32, _P]),
-    'ptmi_lstm_backward_persistent_states': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32,
-                                                     c_int32, c_int32, _P]),
     'ptmi_lstm_backward_planes_ok': (c_int32, [c_int32, c_int32, c_int32, c_int64, c_int32]),
-    'ptmi_lstm_backward_persistent_planes': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32,
-                                                     c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_lstm_scratch_prefill': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    'ptmi_lstm_backward_persistent': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32,
+                                              c_int32, c_int32, c_int32, c_int32, _P]),
     'ptmi_absmax': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
     'ptmi_absmax_accumulate': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
     'ptmi_planes_elems': (c_int64, [c_int64, c_int64]),

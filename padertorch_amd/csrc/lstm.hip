@@ -5,22 +5,25 @@
 // (PyTorch semantics: gate order i,f,g,o; two bias vectors; zero initial state).
 //
 // The input projections X W_ih^T + b (60 % of the LSTM FLOPs) are ONE dense GEMM per layer for
-// both directions and stay on the BLAS library.  What is hand-written here is the part that is
+// both directions and stay on the BLAS library.  What is hand-written is the part that is
 // sequential in time:
-//     gates = gx[t] + h_{t-1} W_hh^T   (exact fp32 on the matrix cores: v_mfma_f32_16x16x4_f32,
-//                                        K split over the wavefronts of a workgroup, LDS reduce)
+//     gates = gx[t] + h_{t-1} W_hh^T
 //     i,f,o = sigmoid, g = tanh, c_t = f c_{t-1} + i g, h_t = o tanh(c_t)      (fused epilogue)
 // and the mirrored step of the backward pass (dh_rec = dgates_{t+1} W_hh, then the gate
 // derivatives), both directions in one launch.  Two execution forms with the same results:
-//   * lstm_{fwd,bwd}_step_kernel: one launch per timestep (MIOpen spends 4 launches, 2 GEMMs + 2
-//     pointwise, per step and direction here); no residency requirement, also captured as hipGraphs;
-//   * lstm_{fwd,bwd}_persistent_kernel (default): ONE launch per layer and pass.  The workgroup's slice
-//     of W_hh lives in registers for all T steps; steps are chained by write-through stores into a
-//     tile-major hand-off copy (one contiguous KB per operand load), a drain, and per-chain arrival
-//     counters.  All workgroups must be co-resident (host-checked); every spin is bounded.
-// Environment: PTMI_LSTM_F32 (these exact-fp32 kernels instead of csrc/lstm_split.hip: the A/B reference),
-// PTMI_LSTM_DBG (timing ablations - 16 no poll, 32 no drain, 64 no MFMA, 128 no operand loads, 256 no look-ahead loads:
-// results void), PTMI_LSTM_MAX_POLLS (watchdog budget).  Round 2's tile / placement knobs are gone with round 3's prune.
+//   * lstm_{fwd,bwd}_step_kernel (this file): one launch per timestep, the product in exact fp32 on the matrix
+//     cores (v_mfma_f32_16x16x4_f32, K split over the wavefronts of a workgroup, LDS reduce; MIOpen spends 4
+//     launches, 2 GEMMs + 2 pointwise, per step and direction here); no residency requirement;
+//   * the persistent kernels of csrc/lstm_split.hip (default): ONE launch per layer and pass, split 16-bit MFMA
+//     products, the steps chained through hand-off planes that carry their own "ready" (data-as-flag).  All
+//     workgroups of a launch must be co-resident.  This file holds their host side: fwd_plan / bwd_plan decide per
+//     configuration whether they run and with which tile and grid - every geometry rule is written there, once -,
+//     and ptmi_lstm_{forward,backward}_persistent check their contract (include/ptmi.h) in full before they
+//     enqueue anything.
+// Environment: PTMI_LSTM_F32 (the persistent entries refuse, so that the callers run the exact-fp32
+// step-per-launch kernels: the A/B reference), PTMI_LSTM_DBG (timing ablations; the persistent kernels' bits are listed in
+// csrc/lstm_split.hip, the step kernels': 1 no recurrent product, 2 no MFMA, 4 the other tile, 8 both row tiles: results
+// void), PTMI_LSTM_MAX_POLLS (watchdog budget of the persistent kernels).
 //
 // Layouts (rows = packed time-major rows of the PackedSequence, row(t, b) = offs[t] + b):
 //   gx / gates / dgates  [rows][ndir][4][H]   (pre-activations in, activations out: in place)
@@ -32,17 +35,6 @@
 
 #include "common.h"
 #include "lstm_common.h"
-
-// fragments of the backward K slice in flight per wavefront (8-wavefront kernel, see HALF there)
-#ifndef PTMI_BWD_CA
-#define PTMI_BWD_CA 5
-#endif
-
-// fragments of the forward K slice in flight per wavefront (us per step at B = 32 / 16 / 1: 5: 4.45 / 3.72 / 3.45,
-// 3: 4.44 / 3.62 / 3.54, 2: 4.32 / 3.54 / 3.43, 1: 4.41 / 3.59 / 3.37)
-#ifndef PTMI_FWD_CA
-#define PTMI_FWD_CA 2
-#endif
 
 namespace ptmi {
 
@@ -308,10 +300,6 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_step_kernel(const LstmBwdArg
     }
 }
 
-// (Rounds 1-4 kept a persistent EXACT-fp32 pair of kernels here - lstm_fwd_persistent_kernel / lstm_bwd_persistent_kernel, the flag
-//  protocol on v_mfma_f32_16x16x4_f32 - reachable only through PTMI_LSTM_F32=1 once the split kernels of lstm_split.hip covered every
-//  resident configuration.  Removed in round 5: PTMI_LSTM_F32=1 now selects the step-per-launch kernels above, which are exact fp32 too.)
-
 static void neighbour(const int32_t* bs, const int64_t* offs, int T, int t, int tn, int* n, long long* row) {
     *n = 0;
     *row = 0;
@@ -392,12 +380,6 @@ static unsigned* error_sink() {
     return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) ? g_error_sink[dev] : nullptr;
 }
 
-static int lstm_backward_persistent_impl(const float* gates, const float* c, const float* c0, const float* dhy,
-                                         const float* w_hh_t, float* dgates, uint16_t* dgates_t, const int32_t* batch_sizes_dev,
-                                         const int64_t* offsets_dev, const uint64_t* step_masks, uint32_t* flags, float* dc_carry,
-                                         int32_t T, int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin,
-                                         int32_t s_end, int32_t prefilled, ptmi_stream_t stream, const float* dc_n = nullptr);
-
 extern "C" {
 
 int ptmi_lstm_forward(float* gates, float* hy, float* c, const float* c0, const float* w_hh_pad, const int32_t* batch_sizes,
@@ -421,21 +403,29 @@ int ptmi_lstm_backward(const float* gates, const float* c, const float* c0, cons
                             static_cast<hipStream_t>(stream));
 }
 
+// ---- host side of the persistent recurrence (kernels: csrc/lstm_split.hip) -----------------------------------------------
+
 int64_t ptmi_lstm_flags_elems(int32_t T, int32_t ndir, int32_t max_batch) {
     (void)T;
-    return (int64_t)ndir * ((max_batch + 15) / 16) * kSlots + 8;   // one chain per 16-row tile + error words
+    return (int64_t)ndir * ((max_batch + 15) / 16) * kSlots + 8;   // kSlots reserved words per chain of 16 rows + error words
 }
+
+static int round32(int n) { return (n + 31) / 32 * 32; }
 
 // tile-major hand-off copy: [T][16-row tiles][ndir][cols / 16] tiles of 16 x 16 floats
 static int64_t lstm_tile_elems(int32_t T, int32_t ndir, int32_t max_batch, int32_t cols) {
     return (int64_t)T * ((max_batch + 15) / 16) * ndir * cols * 16;
 }
 
+// the words behind the backward planes: [ndir][4H] bias sums, 8 words (word 0: max |dgates|), reserved + error words
+static int64_t bwd_tail_elems(int32_t T, int32_t ndir, int32_t max_batch, int32_t H) {
+    return (int64_t)ndir * 4 * H + 8 + ptmi_lstm_flags_elems(T, ndir, max_batch);
+}
+
 int64_t ptmi_lstm_scratch_elems(int32_t T, int32_t ndir, int32_t max_batch, int32_t H, int32_t backward) {
-    // [tile-major hand-off copy (columns rounded up to 32) | backward: bias gradient [ndir][4H] + 8 words (word 0: max
-    // |dgates| as float bits) | hand-off slots | 8 error words]
-    return lstm_tile_elems(T, ndir, max_batch, backward ? (4 * H + 31) / 32 * 32 : (H + 31) / 32 * 32) +
-           (backward ? (int64_t)ndir * 4 * H + 8 : 0) + ptmi_lstm_flags_elems(T, ndir, max_batch);
+    // [tile-major hand-off copy (columns rounded up to 32) | backward: bias gradient [ndir][4H] + 8 words | reserved words | 8 error words]
+    return backward ? lstm_tile_elems(T, ndir, max_batch, round32(4 * H)) + bwd_tail_elems(T, ndir, max_batch, H)
+                    : lstm_tile_elems(T, ndir, max_batch, round32(H)) + ptmi_lstm_flags_elems(T, ndir, max_batch);
 }
 
 int ptmi_lstm_set_error_sink(uint32_t* word) {
@@ -449,193 +439,165 @@ int ptmi_lstm_set_error_sink(uint32_t* word) {
 
 int ptmi_lstm_split_enabled(void) { return getenv("PTMI_LSTM_F32") ? 0 : 1; }
 
-static bool fwd_uses_daf(int max_batch, int H, int ndir);
-static void fwd_tile_shape(int max_batch, int H, int ndir, bool split, int* jt_out, int* mtl_out);
-
-int ptmi_lstm_forward_fills(int32_t T, int32_t ndir, int32_t max_batch, int32_t H) {
-    if (T < 1 || max_batch < 1 || H < 1 || H % 4 != 0 || (ndir != 1 && ndir != 2) || !ptmi_lstm_split_enabled()) return 0;
-    const int G32 = (4 * H + 31) / 32 * 32;
-    if ((G32 / 32 + 7) / 8 > 10 || !bwd_daf_applies() || !fwd_uses_daf(max_batch, H, ndir)) return 0;
-    // one forward launch (all row tiles resident at once), a wavefront without elements in its workgroups
-    int jt, mtl;
-    fwd_tile_shape(max_batch, H, ndir, true, &jt, &mtl);
-    const int ntiles = (max_batch + 16 * mtl - 1) / (16 * mtl);
-    const int jx = (H + jt - 1) / jt;
-    return ((long long)jx * ndir * ntiles <= cu_count() && 16 * mtl * jt <= 7 * 64) ? 2 : 0;      // 2: planes AND the words behind them
+// What a plan can be made for at all (the queries answer 0 for everything else; the entries refuse it with a code of their own).
+static bool plannable(int T, int ndir, int max_batch, int64_t rows, int H) {
+    return T >= 1 && max_batch >= 1 && rows >= 1 && H >= 1 && H % 4 == 0 && (ndir == 1 || ndir == 2) && ptmi_lstm_split_enabled();
 }
 
-int ptmi_lstm_scratch_prefill(uint32_t* scratch, int32_t T, int32_t ndir, int32_t max_batch, int32_t H, int32_t backward,
-                              ptmi_stream_t stream) {
-    PTMI_RETURN_IF(!scratch || T < 1 || max_batch < 1 || H < 1 || (ndir != 1 && ndir != 2), PTMI_E_INVALID);
-    if (H % 4 != 0 || !ptmi_lstm_split_enabled()) return 0;
-    int cols;
-    if (backward) {
-        const int G32 = (4 * H + 31) / 32 * 32;
-        if ((G32 / 32 + 7) / 8 > 10 || !bwd_daf_applies()) return 0;
-        cols = G32;
-    } else {
-        if (!fwd_uses_daf(max_batch, H, ndir)) return 0;
-        cols = (H + 31) / 32 * 32;
-    }
-    const int rc = daf_prefill(scratch, (size_t)lstm_tile_elems(T, ndir, max_batch, cols), static_cast<hipStream_t>(stream));
-    return rc ? rc : 1;
+// The persistent BACKWARD launch of one configuration.  Everything the launcher and the queries know about its geometry is here.
+struct BwdPlan {
+    bool ok;           // the persistent kernels run this configuration (else: the step-per-launch kernels)
+    int G32;           // hand-off columns per direction, 4H rounded up to 32; 0: no persistent kernel for a layer of this width
+    int mtl;           // 16-row tiles per workgroup
+    int ntiles;        // row tiles (16 mtl rows) of the whole batch
+    int nx;            // unit tiles (16 hidden units) = workgroups of a chain (direction x row tile)
+    int per_launch;    // row tiles per launch
+    bool planes;       // the launch can emit dgates^T as bf16 planes
+};
+
+static BwdPlan bwd_plan(int T, int ndir, int max_batch, int64_t rows, int H) {
+    BwdPlan p{};
+    if (!plannable(T, ndir, max_batch, rows, H)) return p;
+    constexpr int NW = 8, CB = 10;            // lstm_bwd_split_kernel: wavefronts, resident k blocks of 32 per wavefront
+    const int G32 = round32(4 * H);
+    if ((G32 / 32 + NW - 1) / NW > CB) return p;
+    p.G32 = G32;
+    // One workgroup per CU must be resident (at most 240 per launch: a margin of 16).  Row tiles are independent recurrences,
+    // so a batch whose tiles do not fit at once runs as several launches over groups of tiles; before that,
+    // 16-row chains become 32-row chains (MTL = 2: one launch up to batch 64 at H = 600; 7.5 us per step instead of 2 x 5.0).
+    const int resident = cu_count() - 16;
+    p.nx = (H + 15) / 16;
+    if ((long long)p.nx * ndir > resident || p.nx > kSlots) return p;
+    const int nt16 = (max_batch + 15) / 16, fit = resident / (p.nx * ndir);
+    p.mtl = nt16 > fit ? 2 : 1;
+    p.ntiles = (nt16 + p.mtl - 1) / p.mtl;
+    p.per_launch = std::min(p.ntiles, fit);
+    p.planes = rows == (int64_t)T * max_batch && max_batch % 16 == 0;          // equal lengths, whole 16-row tiles
+    p.ok = true;
+    return p;
 }
 
-int32_t ptmi_lstm_handoff_cols(int32_t H, int32_t backward) {
-    if (H < 1 || H % 4 != 0 || !ptmi_lstm_split_enabled()) return 0;
-    if (backward) {
-        const int G32 = (4 * H + 31) / 32 * 32;
-        return (G32 / 32 + 7) / 8 <= 10 ? G32 : 0;           // the rule of ptmi_lstm_backward_persistent_range
-    }
-    const int KP32 = (H + 31) / 32 * 32;
-    return (KP32 / 32 + 7) / 8 <= 3 ? KP32 : 0;              // the rule of ptmi_lstm_forward_persistent
-}
+// The persistent FORWARD launch of one configuration.
+struct FwdPlan {
+    bool ok;           // as in BwdPlan
+    int KP32;          // hand-off columns per direction, H rounded up to 32; 0: no persistent kernel for a layer of this width
+    int jt, mtl;       // workgroup tile: jt hidden units x 16 mtl rows
+    int ntiles;        // row tiles (16 mtl rows) of the whole batch
+    int jx;            // unit tiles = workgroups of a chain
+    int per_launch;    // row tiles per launch
+    int fills;         // what the launch writes into this layer's BACKWARD scratch on the side (the `prefilled` of the backward
+                       // call): 2 = the pattern into its planes and zeros into the words behind them, 0 = nothing
+};
 
-// Workgroup tile of the persistent forward launch (jt hidden units x 16 mtl rows) for a batch / layer size.
-static void fwd_tile_shape(int max_batch, int H, int ndir, bool split, int* jt_out, int* mtl_out) {
-    int jt = max_batch <= 16 ? 8 : 12, mtl = max_batch <= 32 ? 1 : 2;
-    // split kernels, one 16-row tile per workgroup: 16 units (38 instead of 50 workgroups per chain at H = 600) measured
-    // 3.19 against 3.27 us per step with the fragment-order hand-off copy, and leaves 48 more CUs to other queues
-    // (flag-protocol kernels only; with the data-as-flag hand-off 12 units measure 2.48 against 2.55)
-    if (jt == 12 && (long long)((H + 11) / 12) * ndir > cu_count()) jt = 16;      // wide tiles: one workgroup per CU
-    if (jt == 16 && (long long)((H + 15) / 16) * ndir > cu_count()) jt = 8;
-    *jt_out = jt;
-    *mtl_out = mtl;
-}
-
-// Does the persistent forward launch of this configuration hand its rows on by the data-as-flag protocol (planes pre-filled
-// with the pattern)?  One answer for all launches of a call (later launches have at most as many row tiles as the first).
-static bool fwd_uses_daf(int max_batch, int H, int ndir) {
-    const int KP32 = (H + 31) / 32 * 32;
-    const bool split = ptmi_lstm_split_enabled() && (KP32 / 32 + 7) / 8 <= 3;
-    if (!split) return false;
-    int jt, mtl;
-    fwd_tile_shape(max_batch, H, ndir, split, &jt, &mtl);
-    const bool wide = jt >= 12;
-    const int ntiles = (max_batch + 16 * mtl - 1) / (16 * mtl);
-    const int jx = wide ? (H + jt - 1) / jt : (H + 7) / 8;
+static FwdPlan fwd_plan(int T, int ndir, int max_batch, int64_t rows, int H) {
+    FwdPlan p{};
+    if (!plannable(T, ndir, max_batch, rows, H)) return p;
+    constexpr int NW = 8, CB = 3;             // lstm_fwd_daf_kernel: wavefronts, resident k blocks of 32 per wavefront
+    const int KP32 = round32(H);
+    if ((KP32 / 32 + NW - 1) / NW > CB) return p;
+    p.KP32 = KP32;
     const int cus = cu_count();
-    const int cap = wide ? cus : cus * 7 / 4;
-    if ((long long)jx * ndir > cap) return false;
-    const int per_launch = std::min(ntiles, cap / (jx * ndir));
-    return fwd_daf_applies(jt, mtl == 1, (long long)jx * ndir * per_launch <= cus);
-}
-
-int ptmi_lstm_forward_persistent(float* gates, float* hy, float* c, const float* c0, const float* w_hh_pad,
-                                 const uint32_t* w_hh_amax, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                 uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows, int32_t H, int32_t KP,
-                                 int32_t ndir, int32_t prefilled, uint32_t* backward_scratch, ptmi_stream_t stream) {
-    return ptmi_lstm_forward_persistent_slots(gates, hy, c, c0, w_hh_pad, w_hh_amax, batch_sizes_dev, offsets_dev, nullptr, flags, T,
-                                              max_batch, rows, H, KP, ndir, prefilled, backward_scratch, stream);
-}
-
-int ptmi_lstm_forward_persistent_slots(float* gates, float* hy, float* c, const float* c0, const float* w_hh_pad,
-                                       const uint32_t* w_hh_amax, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                       const uint64_t* step_masks, uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows,
-                                       int32_t H, int32_t KP, int32_t ndir, int32_t prefilled, uint32_t* backward_scratch,
-                                       ptmi_stream_t stream) {
-    PTMI_RETURN_IF(!gates || !hy || !c || !w_hh_pad || !batch_sizes_dev || !offsets_dev || !flags, PTMI_E_INVALID);
-    // row slots: every (time index, slot) row exists in the buffers; at most 64 slots (one mask word per step and kind)
-    PTMI_RETURN_IF(step_masks && (rows != (int64_t)T * max_batch || max_batch > 64 || c0), PTMI_E_UNSUPPORTED);
-    PTMI_RETURN_IF(T < 1 || max_batch < 1 || H < 1 || (ndir != 1 && ndir != 2) || rows < 1, PTMI_E_INVALID);
-    PTMI_RETURN_IF(H % 4 != 0 || KP % 16 != 0 || KP < H, PTMI_E_UNSUPPORTED);
-    constexpr int NW = 8;
-    // the resident W slice must fit 3 k blocks of 32 per wavefront; all workgroups must be co-resident
-    const int KP32 = (H + 31) / 32 * 32;
-    const bool split = ptmi_lstm_split_enabled() && (KP32 / 32 + NW - 1) / NW <= 3;      // split kernels: <= 3 k blocks of 32 per wavefront
-    PTMI_RETURN_IF(!split, PTMI_E_UNSUPPORTED);                     // the caller falls back to the step-per-launch kernels
-    // 16-row workgroups (two interleaved chains per 32 rows) while all of them stay co-resident
-    // (512 threads at <= 128 VGPRs: 2 per CU; keep a margin below 256 x 2), else 32-row workgroups
-    const int jx8 = (H + 7) / 8;
-    const long long hy_bytes = rows * ndir * H * 4;
-    PTMI_RETURN_IF(hy_bytes > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
     // Workgroup tile (rows x hidden units), measured forward us per step at H = 600, T = 253:
     //   B <= 16: 16 x 8 (4.9);  B <= 32: two independent chains of 16 x 12 on separate CUs (200 workgroups:
     //   5.4; 16 x 16 on 152: 5.8; 32 x 8: 6.6; 16 x 8 with 300 workgroups sharing CUs: 8.3);
     //   B > 32: 32 x 12 (B = 64: 32 x 16 8.8, 32 x 8 11.6).
-    int jt, mtl;
-    fwd_tile_shape(max_batch, H, ndir, split, &jt, &mtl);
-    const bool small = mtl == 1, wide = jt >= 12;
-    const int ntiles = (max_batch + 16 * mtl - 1) / (16 * mtl);
-    const int jx = wide ? (H + jt - 1) / jt : jx8;
-    const int cus = cu_count();
-    const int cap = wide ? cus : cus * 7 / 4;     // 12/16-unit tiles need the whole register file: one workgroup per CU
-    PTMI_RETURN_IF((long long)jx * ndir > cap || jx > kSlots, PTMI_E_UNSUPPORTED);
+    // One 16-row tile per workgroup: 16 units (38 instead of 50 workgroups per chain at H = 600) measured 2.55 against 2.48 us
+    // per step for 12 - they only step in where 12-unit tiles do not fit one workgroup per CU, 8 where those do not either.
+    p.jt = max_batch <= 16 ? 8 : 12;
+    p.mtl = max_batch <= 32 ? 1 : 2;
+    if (p.jt == 12 && (long long)((H + 11) / 12) * ndir > cus) p.jt = 16;
+    if (p.jt == 16 && (long long)((H + 15) / 16) * ndir > cus) p.jt = 8;
+    p.ntiles = (max_batch + 16 * p.mtl - 1) / (16 * p.mtl);
+    p.jx = (H + p.jt - 1) / p.jt;
+    // 8-unit tiles (512 threads at <= 128 VGPRs) fit 2 per CU, with a margin below 2 x; 12 / 16-unit tiles need the whole
+    // register file: one workgroup per CU
+    const int cap = p.jt >= 12 ? cus : cus * 7 / 4;
+    if ((long long)p.jx * ndir > cap || p.jx > kSlots) return p;
     // row tiles are independent recurrences: a batch whose tiles do not all fit runs as several launches
-    const int per_launch = std::min(ntiles, cap / (jx * ndir));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // scratch = [tile-major hy | arrival counters | 8 error words]; only the counters need zeroing
-    PTMI_RETURN_IF(KP != (H + 15) / 16 * 16, PTMI_E_UNSUPPORTED);
-    float* const hyt = reinterpret_cast<float*>(flags);
-    flags += lstm_tile_elems(T, ndir, max_batch, KP32);
-    const bool daf = split && fwd_uses_daf(max_batch, H, ndir);
-    PTMI_RETURN_IF(!daf, PTMI_E_UNSUPPORTED);          // no data-as-flag instantiation for this tile shape: the step-per-launch kernels
-    PTMI_RETURN_IF(step_masks && !daf, PTMI_E_UNSUPPORTED);          // the data-as-flag kernels carry the row masks
-    if (daf && !prefilled) {        // every 16-bit value of the planes = 0xFFFF (no value can be), the counters behind them zero: one launch
-        int fe = daf_prefill_and_zero(hyt, (size_t)lstm_tile_elems(T, ndir, max_batch, KP32), flags, (size_t)ptmi_lstm_flags_elems(T, ndir, max_batch), st);
-        if (fe) return fe;
-    } else {
-        hipError_t e = zero_words_async(flags, (size_t)ptmi_lstm_flags_elems(T, ndir, max_batch), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    LstmPersistArgs A{gates, hy, c, w_hh_pad, batch_sizes_dev, offsets_dev, flags, T, H, KP, ndir,
-                      (unsigned)jx, getenv("PTMI_LSTM_MAX_POLLS") ? (unsigned)atoi(getenv("PTMI_LSTM_MAX_POLLS")) : 1u << 22, (int)hy_bytes,
-                      (unsigned)(ptmi_lstm_flags_elems(T, ndir, max_batch) - 8),
-                      getenv("PTMI_LSTM_DBG") ? atoi(getenv("PTMI_LSTM_DBG")) : 0, 0, ntiles, c0, max_batch, hyt, (max_batch + 15) / 16,
-                      w_hh_amax, KP32};
-    A.err_sink = error_sink();
-    A.uniform = (rows == (int64_t)T * max_batch) ? 1 : 0;      // batch sizes never grow: equal lengths
-    A.masks = reinterpret_cast<const unsigned long long*>(step_masks);
-    if (backward_scratch && ptmi_lstm_forward_fills(T, ndir, max_batch, H)) {     // this layer's backward planes get their pattern here
-        const int G32 = (4 * H + 31) / 32 * 32;
-        A.fill_ptr = reinterpret_cast<uint4*>(backward_scratch);
-        A.fill_n16 = (unsigned long long)lstm_tile_elems(T, ndir, max_batch, G32) / 4;
-        // the words behind the planes: [ndir][4H] bias sums, 8 words, arrival slots + error words - a multiple of 4 words (kSlots is)
-        A.zero_n16 = (unsigned long long)((long long)ndir * 4 * H + 8 + ptmi_lstm_flags_elems(T, ndir, max_batch)) / 4;
-    }
-    for (int t0 = 0; t0 < ntiles; t0 += per_launch) {
-        A.tile0 = t0;
-        const int nt = std::min(per_launch, ntiles - t0);
-        const dim3 grid((unsigned)jx, (unsigned)ndir, (unsigned)nt);
-        const bool one_per_cu = (long long)jx * ndir * nt <= cus;
-        // one workgroup per CU: the workgroups of a chain (direction x row tile) on 8 / chains neighbouring XCDs, as in the
-        // backward kernel (a chain's hand-off rows and slots then live in the L2s of those XCDs only)
-        const int chains = ndir * nt;
-        A.span = (one_per_cu && chains <= 8 && 8 % chains == 0 && (jx + 8 / chains - 1) / (8 / chains) * 8 <= cus) ? 8 / chains : 0;
-        A.nx = jx;
-        A.nt = nt;
-        const dim3 grid1(A.span ? (unsigned)((jx + A.span - 1) / A.span * 8) : 0u);
-        int rc = launch_fwd_split(A, jt, small, one_per_cu, A.span ? grid1 : grid, st, daf);
-        if (rc) return rc;
-    }
-    return PTMI_OK;
+    p.per_launch = std::min(p.ntiles, cap / (p.jx * ndir));
+    // the data-as-flag kernels exist for these tiles, and run one workgroup per CU
+    if (!fwd_split_instantiated(p.jt, p.mtl) || (long long)p.jx * ndir * p.per_launch > cus) return p;
+    p.ok = true;
+    // the fill of the backward planes: ONE forward launch (all row tiles resident at once) whose workgroups have a wavefront
+    // without elements, and a backward kernel that reads the pattern for this width
+    if ((long long)p.jx * ndir * p.ntiles <= cus && 16 * p.mtl * p.jt <= 7 * 64 && bwd_plan(T, ndir, max_batch, rows, H).G32) p.fills = 2;
+    return p;
 }
 
-int ptmi_lstm_backward_persistent(const float* gates, const float* c, const float* c0, const float* dhy, const float* w_hh_t,
-                                  float* dgates, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                  uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows, int32_t H,
-                                  int32_t ndir, int32_t prefilled, ptmi_stream_t stream) {
-    return ptmi_lstm_backward_persistent_range(gates, c, c0, dhy, w_hh_t, dgates, batch_sizes_dev, offsets_dev, flags, nullptr, T,
-                                               max_batch, rows, H, ndir, 0, T, prefilled, stream);
+int32_t ptmi_lstm_handoff_cols(int32_t H, int32_t backward) {        // (a rule of the layer's width alone)
+    return backward ? bwd_plan(1, 1, 1, 1, H).G32 : fwd_plan(1, 1, 1, 1, H).KP32;
 }
 
-int ptmi_lstm_backward_persistent_range(const float* gates, const float* c, const float* c0, const float* dhy,
-                                        const float* w_hh_t, float* dgates, const int32_t* batch_sizes_dev,
-                                        const int64_t* offsets_dev, uint32_t* flags, float* dc_carry, int32_t T,
-                                        int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin, int32_t s_end,
-                                        int32_t prefilled, ptmi_stream_t stream) {
-    PTMI_RETURN_IF(!dgates, PTMI_E_INVALID);
-    return ptmi_lstm_backward_persistent_planes(gates, c, c0, dhy, w_hh_t, dgates, nullptr, batch_sizes_dev, offsets_dev, flags, dc_carry,
-                                                T, max_batch, rows, H, ndir, s_begin, s_end, prefilled, stream);
+int ptmi_lstm_forward_fills(int32_t T, int32_t ndir, int32_t max_batch, int32_t H) {
+    return fwd_plan(T, ndir, max_batch, (int64_t)T * max_batch, H).fills;
 }
 
 int32_t ptmi_lstm_backward_planes_ok(int32_t T, int32_t ndir, int32_t max_batch, int64_t rows, int32_t H) {
-    if (T < 1 || max_batch < 1 || H < 1 || H % 4 != 0 || (ndir != 1 && ndir != 2) || !ptmi_lstm_split_enabled()) return 0;
-    if (rows != (int64_t)T * max_batch || max_batch % 16 != 0) return 0;             // equal lengths, whole 16-row tiles
-    const int G32 = (4 * H + 31) / 32 * 32;
-    if ((G32 / 32 + 7) / 8 > 10 || !bwd_daf_applies()) return 0;                     // the data-as-flag split kernels run
-    const int nx = (H + 15) / 16;
-    return ((long long)nx * ndir <= cu_count() - 16 && nx <= kSlots) ? 1 : 0;
+    const BwdPlan p = bwd_plan(T, ndir, max_batch, rows, H);
+    return p.ok && p.planes ? 1 : 0;
+}
+
+static int env_int(const char* name, int fallback) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : fallback;
+}
+
+int ptmi_lstm_forward_persistent(float* gates, float* hy, float* c, const float* c0, const float* w_hh_pad,
+                                 const uint32_t* w_hh_amax, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
+                                 const uint64_t* step_masks, uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows,
+                                 int32_t H, int32_t KP, int32_t ndir, int32_t prefilled, uint32_t* backward_scratch,
+                                 ptmi_stream_t stream) {
+    // the contract (include/ptmi.h), in full before the first enqueue
+    PTMI_RETURN_IF(!gates || !hy || !c || !w_hh_pad || !batch_sizes_dev || !offsets_dev || !flags, PTMI_E_INVALID);
+    PTMI_RETURN_IF(T < 1 || max_batch < 1 || H < 1 || (ndir != 1 && ndir != 2) || rows < 1, PTMI_E_INVALID);
+    const bool uniform = rows == (int64_t)T * max_batch;         // batch sizes never grow: equal lengths
+    // row slots: every (time index, slot) row exists in the buffers; at most 64 slots (one mask word per step and kind)
+    PTMI_RETURN_IF(step_masks && (c0 || !uniform || max_batch > 64), PTMI_E_UNSUPPORTED);
+    PTMI_RETURN_IF(H % 4 != 0 || KP != (H + 15) / 16 * 16, PTMI_E_UNSUPPORTED);
+    const FwdPlan P = fwd_plan(T, ndir, max_batch, rows, H);
+    PTMI_RETURN_IF(!P.ok, PTMI_E_UNSUPPORTED);                      // the caller falls back to the step-per-launch kernels
+    const long long hy_bytes = rows * ndir * H * 4;
+    PTMI_RETURN_IF(hy_bytes > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // scratch = [hand-off planes of hy | reserved words | 8 error words]: every 16-bit value of the planes starts as 0xFFFF (no value can
+    // be), the words behind them as zero - one launch, unless the caller has filled the planes
+    const int64_t plane_elems = lstm_tile_elems(T, ndir, max_batch, P.KP32), flag_elems = ptmi_lstm_flags_elems(T, ndir, max_batch);
+    float* const hyt = reinterpret_cast<float*>(flags);
+    flags += plane_elems;
+    if (!prefilled) {
+        int fe = daf_fill_and_zero(hyt, (size_t)plane_elems, flags, (size_t)flag_elems, st);
+        if (fe) return fe;
+    } else {
+        hipError_t e = zero_words_async(flags, (size_t)flag_elems, st);
+        if (e != hipSuccess) return (int)e;
+    }
+    LstmPersistArgs A{gates, hy, c, w_hh_pad, batch_sizes_dev, offsets_dev, flags, T, H, KP, ndir,
+                      (unsigned)P.jx, (unsigned)env_int("PTMI_LSTM_MAX_POLLS", 1 << 22), (int)hy_bytes, (unsigned)(flag_elems - 8),
+                      env_int("PTMI_LSTM_DBG", 0), 0, P.ntiles, c0, max_batch, hyt, (max_batch + 15) / 16, w_hh_amax, P.KP32};
+    A.err_sink = error_sink();
+    A.uniform = uniform ? 1 : 0;
+    A.masks = reinterpret_cast<const unsigned long long*>(step_masks);
+    if (backward_scratch && P.fills) {     // this layer's backward planes get their pattern here, the words behind them zeros
+        A.fill_ptr = reinterpret_cast<uint4*>(backward_scratch);
+        A.fill_n16 = (unsigned long long)lstm_tile_elems(T, ndir, max_batch, bwd_plan(T, ndir, max_batch, rows, H).G32) / 4;
+        A.zero_n16 = (unsigned long long)bwd_tail_elems(T, ndir, max_batch, H) / 4;          // a multiple of 4 words (kSlots is)
+    }
+    const int cus = cu_count();
+    for (int t0 = 0; t0 < P.ntiles; t0 += P.per_launch) {
+        A.tile0 = t0;
+        A.nx = P.jx;
+        A.nt = std::min(P.per_launch, P.ntiles - t0);
+        // the workgroups of a chain (direction x row tile) on 8 / chains neighbouring XCDs, as in the backward kernel (a chain's
+        // hand-off rows then live in the L2s of those XCDs only): a 1-D grid; else (unit tile, direction, row tile)
+        const int chains = ndir * A.nt;
+        A.span = (chains <= 8 && 8 % chains == 0 && (P.jx + 8 / chains - 1) / (8 / chains) * 8 <= cus) ? 8 / chains : 0;
+        const dim3 grid = A.span ? dim3((unsigned)((P.jx + A.span - 1) / A.span * 8))
+                                 : dim3((unsigned)P.jx, (unsigned)ndir, (unsigned)A.nt);
+        int rc = launch_fwd_split(A, P.jt, P.mtl, grid, st);
+        if (rc) return rc;
+    }
+    return PTMI_OK;
 }
 
 // the half k block behind the last packed row (rows % 32 == 16) of every column tile and plane: zero
@@ -647,99 +609,61 @@ __global__ void zero_tp_tail_kernel(uint4* planes, long long tiles, int kb_total
     planes[((tile * kb_total + kb_total - 1) * 2 + plane) * 64 + ch] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-int ptmi_lstm_backward_persistent_planes(const float* gates, const float* c, const float* c0, const float* dhy,
-                                         const float* w_hh_t, float* dgates, uint16_t* dgates_t, const int32_t* batch_sizes_dev,
-                                         const int64_t* offsets_dev, uint32_t* flags, float* dc_carry, int32_t T,
-                                         int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin, int32_t s_end,
-                                         int32_t prefilled, ptmi_stream_t stream) {
-    return lstm_backward_persistent_impl(gates, c, c0, dhy, w_hh_t, dgates, dgates_t, batch_sizes_dev, offsets_dev, nullptr, flags, dc_carry,
-                                         T, max_batch, rows, H, ndir, s_begin, s_end, prefilled, stream);
-}
-
-int ptmi_lstm_backward_persistent_states(const float* gates, const float* c, const float* c0, const float* dhy, const float* dc_n,
-                                         const float* w_hh_t, float* dgates, const int32_t* batch_sizes_dev,
-                                         const int64_t* offsets_dev, uint32_t* flags, float* dc_0, int32_t T, int32_t max_batch,
-                                         int64_t rows, int32_t H, int32_t ndir, int32_t prefilled, ptmi_stream_t stream) {
-    PTMI_RETURN_IF(!dgates, PTMI_E_INVALID);
-    return lstm_backward_persistent_impl(gates, c, c0, dhy, w_hh_t, dgates, nullptr, batch_sizes_dev, offsets_dev, nullptr, flags, dc_0, T,
-                                         max_batch, rows, H, ndir, 0, T, prefilled, stream, dc_n);
-}
-
-int ptmi_lstm_backward_persistent_slots(const float* gates, const float* c, const float* dhy, const float* w_hh_t, float* dgates,
-                                        uint16_t* dgates_t, const int32_t* batch_sizes_dev, const int64_t* offsets_dev,
-                                        const uint64_t* step_masks, uint32_t* flags, int32_t T, int32_t max_batch, int64_t rows,
-                                        int32_t H, int32_t ndir, int32_t prefilled, ptmi_stream_t stream) {
-    PTMI_RETURN_IF(!step_masks || (!dgates && !dgates_t), PTMI_E_INVALID);
-    PTMI_RETURN_IF(rows != (int64_t)T * max_batch || max_batch > 64, PTMI_E_UNSUPPORTED);
-    return lstm_backward_persistent_impl(gates, c, nullptr, dhy, w_hh_t, dgates, dgates_t, batch_sizes_dev, offsets_dev, step_masks, flags,
-                                         nullptr, T, max_batch, rows, H, ndir, 0, T, prefilled, stream);
-}
-
-}  // extern "C"
-
-static int lstm_backward_persistent_impl(const float* gates, const float* c, const float* c0, const float* dhy,
-                                         const float* w_hh_t, float* dgates, uint16_t* dgates_t, const int32_t* batch_sizes_dev,
-                                         const int64_t* offsets_dev, const uint64_t* step_masks, uint32_t* flags, float* dc_carry,
-                                         int32_t T, int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin,
-                                         int32_t s_end, int32_t prefilled, ptmi_stream_t stream, const float* dc_n) {
-    PTMI_RETURN_IF(!gates || !c || !dhy || !w_hh_t || (!dgates && !dgates_t) || !batch_sizes_dev || !offsets_dev || !flags,
-                   PTMI_E_INVALID);
-    PTMI_RETURN_IF(dgates_t && (reinterpret_cast<uintptr_t>(dgates_t) & 15) != 0, PTMI_E_INVALID);
+int ptmi_lstm_backward_persistent(const float* gates, const float* c, const float* c0, const float* dhy, const float* dc_n,
+                                  const float* w_hh_t, float* dgates, uint16_t* dgates_t, const int32_t* batch_sizes_dev,
+                                  const int64_t* offsets_dev, const uint64_t* step_masks, uint32_t* flags, float* dc_carry,
+                                  int32_t T, int32_t max_batch, int64_t rows, int32_t H, int32_t ndir, int32_t s_begin,
+                                  int32_t s_end, int32_t prefilled, ptmi_stream_t stream) {
+    // the contract (include/ptmi.h), in full before the first enqueue
+    PTMI_RETURN_IF(!gates || !c || !dhy || !w_hh_t || !batch_sizes_dev || !offsets_dev || !flags, PTMI_E_INVALID);
     PTMI_RETURN_IF(T < 1 || max_batch < 1 || H < 1 || (ndir != 1 && ndir != 2) || rows < 1, PTMI_E_INVALID);
+    PTMI_RETURN_IF(!dgates && !dgates_t, PTMI_E_INVALID);
+    PTMI_RETURN_IF(dgates_t && (reinterpret_cast<uintptr_t>(dgates_t) & 15) != 0, PTMI_E_INVALID);
     PTMI_RETURN_IF(s_begin < 0 || s_end > T || s_begin >= s_end, PTMI_E_INVALID);
     const bool whole = s_begin == 0 && s_end == T;
-    PTMI_RETURN_IF(!whole && !dc_carry, PTMI_E_INVALID);
+    PTMI_RETURN_IF(!whole && (!dc_carry || dc_n), PTMI_E_INVALID);
+    const bool uniform = rows == (int64_t)T * max_batch;
+    PTMI_RETURN_IF(dc_n && step_masks, PTMI_E_UNSUPPORTED);
+    PTMI_RETURN_IF(step_masks && (c0 || !uniform || max_batch > 64 || !whole), PTMI_E_UNSUPPORTED);
     PTMI_RETURN_IF(H % 4 != 0, PTMI_E_UNSUPPORTED);
-    const int G32 = (4 * H + 31) / 32 * 32;
-    const bool split = ptmi_lstm_split_enabled() && (G32 / 32 + 7) / 8 <= 10;           // split kernel: <= 10 k blocks of 32 per wavefront
-    PTMI_RETURN_IF(!split, PTMI_E_UNSUPPORTED);                     // the caller falls back to the step-per-launch kernels
-    const int resident = cu_count() - 16;     // one workgroup per CU, with a margin
-    // One workgroup per CU must be resident (at most 240 per launch).  Row tiles are independent recurrences,
-    // so a batch whose tiles do not fit at once runs as several launches over groups of tiles; before that,
-    // 16-row chains become 32-row chains (8-wavefront workgroups, MTL = 2: one launch up to batch 64 at
-    // H = 600; 7.5 us per step instead of 2 x 5.0).
-    const int nx = (H + 15) / 16, nt16 = (max_batch + 15) / 16;
-    PTMI_RETURN_IF((long long)nx * ndir > resident || nx > kSlots, PTMI_E_UNSUPPORTED);
-    int mtl = nt16 > resident / (nx * ndir) ? 2 : 1;
-    const int ntiles = (nt16 + mtl - 1) / mtl;
-    const int per_launch = std::min(ntiles, resident / (nx * ndir));
+    const BwdPlan P = bwd_plan(T, ndir, max_batch, rows, H);
+    PTMI_RETURN_IF(!P.ok, PTMI_E_UNSUPPORTED);                      // the caller falls back to the step-per-launch kernels
+    PTMI_RETURN_IF(dgates_t && !P.planes, PTMI_E_UNSUPPORTED);
     const long long dg_bytes = rows * ndir * 4 * H * 4;
     PTMI_RETURN_IF(dg_bytes > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
+
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // scratch = [tile-major dgates | bias gradient [ndir][4H] | arrival counters | 8 error words];
-    // the bias gradient and the counters are zeroed here (one memset)
+    // scratch = [hand-off planes of dgates | bias gradient [ndir][4H] | 8 words, word 0: max |dgates| | reserved words | 8 error words].
+    // The first range sets it up in one launch - the planes start as the fill pattern, the words behind them as zero -, unless the
+    // caller (prefilled = 1: planes) or the forward launch (2: the words too, FwdPlan::fills) has; a later range continues on the
+    // first one's bias sums and maximum.
+    const int64_t plane_elems = lstm_tile_elems(T, ndir, max_batch, P.G32), tail_elems = bwd_tail_elems(T, ndir, max_batch, H);
     float* const dgt = reinterpret_cast<float*>(flags);
-    flags += lstm_tile_elems(T, ndir, max_batch, G32);
+    flags += plane_elems;
     float* const dbias = reinterpret_cast<float*>(flags);
-    if (s_begin == 0) {         // a later range continues on the first one's counters, bias sums and maximum
-        const size_t nz = (size_t)(ndir * 4 * H + 8 + ptmi_lstm_flags_elems(T, ndir, max_batch));
-        if (split && bwd_daf_applies() && !prefilled) {       // data-as-flag hand-off: the planes start as the fill pattern (same launch)
-            int fe = daf_prefill_and_zero(dgt, (size_t)lstm_tile_elems(T, ndir, max_batch, G32), flags, nz, st);
-            if (fe) return fe;
-        } else if (prefilled != 2) {       // (2: the forward launch has zeroed these words with the pattern fill - ptmi_lstm_forward_fills)
-            hipError_t e = zero_words_async(flags, nz, st);
-            if (e != hipSuccess) return (int)e;
-        }
+    if (s_begin == 0 && !prefilled) {
+        int fe = daf_fill_and_zero(dgt, (size_t)plane_elems, flags, (size_t)tail_elems, st);
+        if (fe) return fe;
+    } else if (s_begin == 0 && prefilled != 2) {
+        hipError_t e = zero_words_async(flags, (size_t)tail_elems, st);
+        if (e != hipSuccess) return (int)e;
     }
     flags += ndir * 4 * H;
     uint32_t* const dg_amax = flags;
     flags += 8;
+    const int nt16 = (max_batch + 15) / 16;
     LstmPersistBwdArgs A{gates, c, dhy, w_hh_t, dgates, batch_sizes_dev, offsets_dev, flags, T, H, ndir,
-                         (unsigned)nx, getenv("PTMI_LSTM_MAX_POLLS") ? (unsigned)atoi(getenv("PTMI_LSTM_MAX_POLLS")) : 1u << 22, (int)dg_bytes,
-                         (unsigned)(ptmi_lstm_flags_elems(T, ndir, max_batch) - 8), 0, ntiles,
-                         getenv("PTMI_LSTM_DBG") ? atoi(getenv("PTMI_LSTM_DBG")) : 0, c0, max_batch, 0, 0, 0, dgt, nt16, dbias,
-                         split ? dg_amax : nullptr, G32};
+                         (unsigned)P.nx, (unsigned)env_int("PTMI_LSTM_MAX_POLLS", 1 << 22), (int)dg_bytes,
+                         (unsigned)(ptmi_lstm_flags_elems(T, ndir, max_batch) - 8), 0, P.ntiles, env_int("PTMI_LSTM_DBG", 0), c0, max_batch,
+                         0, 0, 0, dgt, nt16, dbias, dg_amax, P.G32};
     A.err_sink = error_sink();
-    A.uniform = (rows == (int64_t)T * max_batch) ? 1 : 0;
+    A.uniform = uniform ? 1 : 0;
     A.masks = reinterpret_cast<const unsigned long long*>(step_masks);
-    PTMI_RETURN_IF(step_masks && !(split && bwd_daf_applies()), PTMI_E_UNSUPPORTED);
-    PTMI_RETURN_IF(dc_n && (!split || step_masks), PTMI_E_UNSUPPORTED);
     A.dcn = dc_n;
     A.s_begin = s_begin;
     A.s_end = s_end;
     A.dc_carry = dc_carry;
     if (dgates_t) {
-        PTMI_RETURN_IF(!split || !ptmi_lstm_backward_planes_ok(T, ndir, max_batch, rows, H), PTMI_E_UNSUPPORTED);
         // the planes hold the rows of THIS launch's step range: (s_end - s_begin) * max_batch packed rows per direction, from
         // time index T - s_end on (forward direction: processed last to first) / s_begin on (reverse direction)
         const int64_t range_rows = (int64_t)(s_end - s_begin) * max_batch;
@@ -755,16 +679,17 @@ static int lstm_backward_persistent_impl(const float* gates, const float* c, con
             if (rc) return rc;
         }
     }
-    for (int t0 = 0; t0 < ntiles; t0 += per_launch) {
+    for (int t0 = 0; t0 < P.ntiles; t0 += P.per_launch) {
         A.tile0 = t0;
-        const int nt = std::min(per_launch, ntiles - t0);
-        const int chains = nt * ndir;
-        A.nx = nx;
-        A.nt = nt;
-        A.span = (chains <= 8 && 8 % chains == 0) ? 8 / chains : 0;
-        const unsigned nwg = A.span ? (unsigned)((nx + A.span - 1) / A.span * 8) : (unsigned)(nx * chains);
-        int rc = launch_bwd_split(A, mtl, nwg, st);
+        A.nx = P.nx;
+        A.nt = std::min(P.per_launch, P.ntiles - t0);
+        const int chains = A.nt * ndir;
+        A.span = (chains <= 8 && 8 % chains == 0) ? 8 / chains : 0;        // XCDs per chain (chain_tile)
+        const unsigned nwg = A.span ? (unsigned)((P.nx + A.span - 1) / A.span * 8) : (unsigned)(P.nx * chains);
+        int rc = launch_bwd_split(A, P.mtl, nwg, st);
         if (rc) return rc;
     }
     return PTMI_OK;
 }
+
+}  // extern "C"

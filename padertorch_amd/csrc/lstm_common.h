@@ -1,5 +1,6 @@
-// Shared pieces of the persistent (B)LSTM recurrence kernels (csrc/lstm.hip: exact fp32 MFMA; csrc/lstm_split.hip:
-// split 16-bit MFMA products).
+// Shared pieces of the (B)LSTM recurrence: the gate non-linearities (csrc/lstm.hip: step-per-launch kernels, csrc/lstm_split.hip:
+// persistent kernels) and the argument blocks / launch interface between the host side of the persistent recurrence (csrc/lstm.hip)
+// and its kernels (csrc/lstm_split.hip).
 #pragma once
 #include "common.h"
 
@@ -18,6 +19,8 @@ __device__ __forceinline__ float tanhf_(float x) {
     return copysignf((1.f - t) * __builtin_amdgcn_rcpf(1.f + t), x);
 }
 
+// (expected, hy_bytes / dg_bytes and ntiles of the two blocks are read by no kernel any more.  They keep their places: without them
+//  the compiler schedules the argument loads, and with them registers, differently in every persistent kernel.)
 struct LstmPersistArgs {
     float* gx;
     float* hy;
@@ -25,13 +28,13 @@ struct LstmPersistArgs {
     const float* w;
     const int32_t* bs;       // device [T]
     const int64_t* offs;     // device [T]
-    unsigned* flags;         // device [ndir][row tiles][kSlots] hand-off slots + 8 error words, zeroed per call
+    unsigned* flags;         // device: the words behind the hand-off planes (zeroed per call), the last 8 of them the error words
     int T, H, KP, ndir;
     unsigned expected;       // producer workgroups per chain (direction x row tile)
     unsigned max_polls;
     int hy_bytes;
     unsigned err_off;        // index of the error words in flags
-    int dbg;                 // PTMI_LSTM_DBG timing ablations (16: no poll, 32: no drain, 64: no MFMA, 128: no operand loads)
+    int dbg;                 // PTMI_LSTM_DBG timing ablations (bits: csrc/lstm_split.hip)
     int tile0, ntiles;       // first row tile of this launch / row tiles of the whole batch
     const float* c0;         // [ndir, max_batch, H] initial cell state or null
     int max_batch;
@@ -48,7 +51,7 @@ struct LstmPersistArgs {
     // scratch) get the fill pattern from an otherwise idle wavefront, a slice per workgroup and step
     uint4* fill_ptr = nullptr;
     unsigned long long fill_n16 = 0;
-    // ... and the `zero_n16` 16-byte units BEHIND them (the backward scratch's bias sums, maximum word, arrival slots and error words)
+    // ... and the `zero_n16` 16-byte units BEHIND them (the backward scratch's bias sums, maximum word, reserved words and error words)
     // get zeros the same way (round 6): the backward launch then has nothing to enqueue in front of its recurrence kernel
     unsigned long long zero_n16 = 0;
     // Row-slot batches (data-as-flag kernels; layout = uniform [T][max_batch] rows, max_batch <= 64 slots): several sequences lie END TO
@@ -58,36 +61,9 @@ struct LstmPersistArgs {
     const unsigned long long* masks = nullptr;
 };
 
-// Hand-off flags: every workgroup of a chain owns ONE slot and stores the number of steps it has
-// finished (a plain write-through store: no read-modify-write, no two producers on one address); a
-// consumer reads all slots of its chain with one or two loads per lane and goes on when every one of them
-// has reached the step it needs.  (First form: 8 sharded arrival counters per step; the ~6 atomic adds
-// queueing on each shard were part of every step's chain.)
-constexpr int kSlots = 128;          // slots per chain = most producer workgroups a chain may have
-
-// `dead`: set once a wait of this workgroup has run out (or another workgroup's has: the error word is sticky and
-// re-read every 256 polls); every later wait then returns at once, so a launch whose workgroups are not all
-// resident ends after ONE bounded spin per workgroup instead of one per time step.
-__device__ __forceinline__ bool wait_arrivals(const unsigned* slots, unsigned producers, unsigned step,
-                                              unsigned max_polls, unsigned* err, unsigned* sink = nullptr) {
-    const unsigned lane = threadIdx.x & 63;
-    for (unsigned it = 0; it < max_polls; ++it) {
-        unsigned v = lane < producers ? __hip_atomic_load(slots + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0u;
-        if (producers > 64) {
-            const unsigned w = lane + 64 < producers
-                                   ? __hip_atomic_load(slots + lane + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0u;
-            v = min(v, w);
-        }
-        if (__all(v >= step)) return true;
-        if ((it & 255u) == 255u && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    if (lane == 0) {
-        __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sink) atomicAdd(sink, 1u);          // the failure path only: what the host polls instead of every call's own word
-    }
-    return false;
-}
+// Most workgroups a chain (direction x row tile) may have.  The scratch still reserves this many words per chain behind the
+// planes (ptmi_lstm_flags_elems: the slots of the former flag protocol, unread by today's kernels) in front of its 8 error words.
+constexpr int kSlots = 128;
 
 struct LstmPersistBwdArgs {
     const float* gates;
@@ -158,12 +134,9 @@ __device__ __forceinline__ bool chain_tile(int nx, int nt, int span, int* x, int
 // registers serve both tiles, the second tile's operands are requested while the first one multiplies).
 
 // csrc/lstm_split.hip
-// data-as-flag kernels (csrc/lstm_split.hip): the caller pre-fills the hand-off planes with daf_prefill
-bool fwd_daf_applies(int jt, bool small, bool one_per_cu);
-bool bwd_daf_applies();
-int daf_prefill(void* p, size_t words, hipStream_t st);
-int daf_prefill_and_zero(void* p, size_t words, void* z, size_t zero_words, hipStream_t st);      // + `zero_words` zeroed words at z, one launch
-int launch_fwd_split(const LstmPersistArgs& A, int jt, bool small, bool one_per_cu, dim3 grid, hipStream_t st, bool daf);
+bool fwd_split_instantiated(int jt, int mtl);       // is there a forward kernel for this workgroup tile (jt hidden units x 16 mtl rows)?
+int daf_fill_and_zero(void* p, size_t words, void* z, size_t zero_words, hipStream_t st);      // pattern into `words` words at p, zeros into `zero_words` at z: one launch
+int launch_fwd_split(const LstmPersistArgs& A, int jt, int mtl, dim3 grid, hipStream_t st);
 int launch_bwd_split(const LstmPersistBwdArgs& A, int mtl, unsigned nwg, hipStream_t st);
 
 }  // namespace ptmi

@@ -1,9 +1,11 @@
 // Persistent (B)LSTM recurrence kernels with split 16-bit MFMA products (gfx950).
 //
-// Same launches, hand-off protocol (write-through tile-major copy, one slot per producer workgroup, bounded polls),
-// layouts and results as lstm_{fwd,bwd}_persistent_kernel in lstm.hip (the recurrence of torch.nn.LSTM on a
-// PackedSequence: padertorch/contrib/examples/source_separation/pit/model.py:60-66,97, contrib/tcl/dc.py:32-34,61).
-// What changes is how the per-step matrix product is evaluated.  fp32 MFMA (v_mfma_f32_16x16x4_f32) runs at 1/16 of the
+// ONE launch per layer and pass: a workgroup's slice of W_hh lives in registers for all T steps, the steps are chained by
+// write-through stores into a tile-major hand-off copy that the consumers poll by value (data-as-flag, below; every poll is
+// bounded).  Same layouts and results as the step-per-launch kernels of lstm.hip (the recurrence of torch.nn.LSTM on a
+// PackedSequence: padertorch/contrib/examples/source_separation/pit/model.py:60-66,97, contrib/tcl/dc.py:32-34,61); the host
+// side - which configurations run, their tiles and grids - is csrc/lstm.hip.
+// What differs from those kernels is how the per-step matrix product is evaluated.  fp32 MFMA (v_mfma_f32_16x16x4_f32) runs at 1/16 of the
 // 16-bit rate; the product h_{t-1} W_hh^T (dgates_{t+1} W_hh in the backward pass) is the longest single item of
 // every step's serial chain (60 / 76 MFMAs of 32 cycles per wavefront).  Here
 //   forward   h in (-1, 1) is handed on as fp16 (hi, lo) halves of 2^10 h, W_hh lives in registers as fp16 halves of
@@ -92,21 +94,8 @@ struct DafHold {
     }
 };
 
-__global__ void fill_words_kernel(uint4* p, size_t n16, unsigned word) {
-    const uint4 v = make_uint4(word, word, word, word);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
-// host: fill `words` 32-bit words (a multiple of 4, 16-byte aligned) with the pattern
-int daf_prefill(void* p, size_t words, hipStream_t st) {
-    const size_t n16 = words / 4;
-    const unsigned grid = (unsigned)std::min<size_t>((n16 + 255) / 256, 8192);
-    hipLaunchKernelGGL(fill_words_kernel, dim3(grid), dim3(256), 0, st, static_cast<uint4*>(p), n16, kFill);
-    return launch_status();
-}
-
-// The set-up of a persistent launch in ONE kernel: the planes start as the pattern, the words behind them (bias sums, arrival
-// slots, error words) as zero.  (Two launches before: ~5 us of queue time each in front of every recurrence of the step.)
+// The set-up of a persistent launch in ONE kernel: the planes start as the pattern, the words behind them (bias sums, maximum
+// word, reserved words, error words) as zero.  (Two launches before: ~5 us of queue time each in front of every recurrence of the step.)
 __global__ void fill_and_zero_kernel(uint4* p, size_t n16, unsigned word, unsigned* z, size_t nz) {
     const uint4 v = make_uint4(word, word, word, word);
     const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
@@ -114,7 +103,7 @@ __global__ void fill_and_zero_kernel(uint4* p, size_t n16, unsigned word, unsign
     for (size_t i = i0; i < nz; i += step) z[i] = 0u;
 }
 
-int daf_prefill_and_zero(void* p, size_t words, void* z, size_t zero_words, hipStream_t st) {
+int daf_fill_and_zero(void* p, size_t words, void* z, size_t zero_words, hipStream_t st) {
     const size_t n16 = words / 4;
     const unsigned grid = (unsigned)std::min<size_t>((std::max(n16, zero_words) + 255) / 256, 8192);
     hipLaunchKernelGGL(fill_and_zero_kernel, dim3(grid), dim3(256), 0, st, static_cast<uint4*>(p), n16, kFill, static_cast<unsigned*>(z), zero_words);
@@ -180,8 +169,8 @@ __device__ __forceinline__ unsigned pair_word(float v, int lane, int* plane) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Forward, data-as-flag hand-off (the default wherever fwd_daf_applies; one workgroup per CU).
-// The protocol above costs every step two store round trips in series (the write-through drain, then the flag) and two
+// Forward, data-as-flag hand-off (one workgroup per CU: fwd_plan in csrc/lstm.hip).
+// A flag protocol (rounds 1-2) costs every step two store round trips in series (the write-through drain, then the flag) and two
 // load round trips (the poll, then the operands).  Here the scratch planes are pre-filled with a pattern no value can
 // have (0xFFFF: a NaN in fp16), producers only issue their write-through stores, and a consumer wavefront requests its
 // operand tiles at once and again until none of their 16-bit values is the pattern: one store and one load round trip.
@@ -478,7 +467,7 @@ __global__ __launch_bounds__(NW * 64, 2) void lstm_fwd_daf_kernel(const LstmPers
 
 // ---------------------------------------------------------------------------------------------------------------
 // Backward-through-time.  8 wavefronts, CB = 32-wide k blocks of K = 4H per wavefront (even split), CAB blocks in
-// flight per wavefront (re-requested as soon as their MFMAs have consumed them, as in lstm_bwd_persistent_kernel).
+// flight per wavefront (re-requested as soon as their MFMAs have consumed them).
 //
 // TP (equal-length batches whose size is a multiple of 16): the gate gradients leave the kernel a second time as bf16 (hi, lo)
 // planes of dgates^T - the operand [4H gate columns][packed rows] of the weight-gradient GEMMs dW = dgates^T [x | h_prev]
@@ -489,9 +478,8 @@ __global__ __launch_bounds__(NW * 64, 2) void lstm_fwd_daf_kernel(const LstmPers
 // stores one 16-byte chunk.  With the planes, the hand-off copy (the LSTM input gradient's operand) and the in-kernel bias sums,
 // nobody reads the row-major fp32 gate gradients any more: A.dg may be null, and the 155 MB store + two transposing pack
 // passes per layer of the B = 32 step go away.
-template <int NW, int CB, int MTL, int CABW, int CP = 16, bool UNI = false, bool DAF = false, bool TP = false, bool MSK = false>
+template <int NW, int CB, int MTL, int CABW, int CP = 16, bool UNI = false, bool TP = false, bool MSK = false>
 __global__ __launch_bounds__(NW * 64, 2) void lstm_bwd_split_kernel(const LstmPersistBwdArgs A) {
-    static_assert(DAF, "the flag-protocol form of this kernel (rounds 1-2) is gone: data-as-flag instantiations only");
     int bx, by, dir;
     if (!chain_tile(A.nx, A.nt, A.span, &bx, &by, &dir)) return;
     const int n0 = bx * 16;
@@ -876,40 +864,27 @@ __global__ __launch_bounds__(NW * 64, 2) void lstm_bwd_split_kernel(const LstmPe
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-bool fwd_daf_applies(int jt, bool small, bool one_per_cu) {
-    return one_per_cu && ((small && (jt == 8 || jt == 12 || jt == 16)) || (!small && jt == 12));
-}
+bool fwd_split_instantiated(int jt, int mtl) { return mtl == 1 ? (jt == 8 || jt == 12 || jt == 16) : (mtl == 2 && jt == 12); }
 
-bool bwd_daf_applies() { return true; }
-
-int launch_fwd_split(const LstmPersistArgs& A, int jt, bool small, bool one_per_cu, dim3 grid, hipStream_t st, bool daf) {
+int launch_fwd_split(const LstmPersistArgs& A, int jt, int mtl, dim3 grid, hipStream_t st) {
     constexpr int NW = 8, CB = 3;
     const dim3 block(NW * 64);
-    if (daf) {
-        if (jt == 16 && small)
-            hipLaunchKernelGGL((lstm_fwd_daf_kernel<16, NW, CB, 1>), grid, block, 0, st, A);
-        else if (jt == 12 && small)
-            hipLaunchKernelGGL((lstm_fwd_daf_kernel<12, NW, CB, 1>), grid, block, 0, st, A);
-        else if (jt == 8 && small)
-            hipLaunchKernelGGL((lstm_fwd_daf_kernel<8, NW, CB, 1>), grid, block, 0, st, A);
-        else
-            hipLaunchKernelGGL((lstm_fwd_daf_kernel<12, NW, CB, 2>), grid, block, 0, st, A);
-        return launch_status();
-    }
-    return PTMI_E_UNSUPPORTED;        // (a tile shape without a data-as-flag instantiation: the caller has checked fwd_daf_applies)
+    if (!fwd_split_instantiated(jt, mtl)) return PTMI_E_UNSUPPORTED;
+    if (mtl == 2)
+        hipLaunchKernelGGL((lstm_fwd_daf_kernel<12, NW, CB, 2>), grid, block, 0, st, A);
+    else if (jt == 16)
+        hipLaunchKernelGGL((lstm_fwd_daf_kernel<16, NW, CB, 1>), grid, block, 0, st, A);
+    else if (jt == 12)
+        hipLaunchKernelGGL((lstm_fwd_daf_kernel<12, NW, CB, 1>), grid, block, 0, st, A);
+    else
+        hipLaunchKernelGGL((lstm_fwd_daf_kernel<8, NW, CB, 1>), grid, block, 0, st, A);
+    return launch_status();
 }
 
 int launch_bwd_split(const LstmPersistBwdArgs& A, int mtl, unsigned nwg, hipStream_t st) {
     // equal-length batches: an instantiation without the PackedSequence tables (no loads at the loop head)
     const bool uni = A.uniform != 0 && !A.masks;         // (row-slot batches: the instantiation that reads the per-step masks)
-    if (A.dgtp && A.masks && A.uniform) {          // row slots (rows = [T, slots]) + dgates^T planes
-        if (mtl == 2)
-            hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, false, true, true, true>), dim3(nwg), dim3(512), 0, st, A);
-        else
-            hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, false, true, true, true>), dim3(nwg), dim3(512), 0, st, A);
-        return launch_status();
-    }
-    if (A.dgtp && A.masks) {
+    if (A.dgtp && A.masks) {          // row slots + dgates^T planes (the entry has checked that masks come with rows = [T, slots])
         if (mtl == 2)
             hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, false, true, true>), dim3(nwg), dim3(512), 0, st, A);
         else
@@ -918,19 +893,19 @@ int launch_bwd_split(const LstmPersistBwdArgs& A, int mtl, unsigned nwg, hipStre
     }
     if (A.dgtp) {          // + dgates^T as bf16 planes (host checked: equal lengths, batch a multiple of 16)
         if (mtl == 2)
-            hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, true, true, true>), dim3(nwg), dim3(512), 0, st, A);
+            hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, true, true>), dim3(nwg), dim3(512), 0, st, A);
         else
-            hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, true, true, true>), dim3(nwg), dim3(512), 0, st, A);
+            hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, true, true>), dim3(nwg), dim3(512), 0, st, A);
         return launch_status();
     }
     if (mtl == 2 && uni)
-        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, true, true>), dim3(nwg), dim3(512), 0, st, A);
+        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, true>), dim3(nwg), dim3(512), 0, st, A);
     else if (mtl == 2)
-        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, false, true>), dim3(nwg), dim3(512), 0, st, A);
+        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 2, 3, 16, false>), dim3(nwg), dim3(512), 0, st, A);
     else if (uni)
-        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, true, true>), dim3(nwg), dim3(512), 0, st, A);
+        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, true>), dim3(nwg), dim3(512), 0, st, A);
     else
-        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, false, true>), dim3(nwg), dim3(512), 0, st, A);
+        hipLaunchKernelGGL((lstm_bwd_split_kernel<8, 10, 1, 3, 16, false>), dim3(nwg), dim3(512), 0, st, A);
     return launch_status();
 }
 

@@ -4,7 +4,7 @@ Same constructor; the parameters live in a ``torch.nn.LSTM`` (same ``state_dict`
 ``lstm.weight_ih_l0`` ...).  The time loop runs in ``csrc/lstm.hip`` (``ops.lstm.packed_lstm``); ``(h_n, c_n)`` of a call is
 carried into the next one like the reference does - WITH their graph (``modules/recurrent.py:42-43`` stores what ``torch.nn.LSTM``
 returns): a loss on a later chunk reaches the earlier chunks' inputs and the parameters through the carried states (the persistent
-kernels' state gradients, ``ptmi_lstm_backward_persistent_states``), and - as with the reference - a second ``backward`` through a chunk
+kernels' state gradients, ``dc_n`` of ``ptmi_lstm_backward_persistent``), and - as with the reference - a second ``backward`` through a chunk
 whose graph has been freed raises torch's error: truncated backpropagation is the caller's ``states = tuple(s.detach() ...)``.
 """
 import torch

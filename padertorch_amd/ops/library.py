@@ -596,26 +596,32 @@ def absmax(x, rows, cols, ld):
     return out
 
 
+def _lstm_backward_persistent(gates, c, c0, dhy, w_hh_t, dg, dg_t, scratch, dc_carry, bs_dev, offs_dev, T, max_batch, rows, H, ndir,
+                              s_begin, s_end, prefilled, step_masks=None, dc_n=None):
+    """The one call of ``ptmi_lstm_backward_persistent`` (include/ptmi.h has its contract).  False: the configuration cannot be kept
+    resident, or the call does not support the combination of arguments - nothing was enqueued, the caller takes another route;
+    every other refusal raises."""
+    rc = _lib.timed('lstm_backward', _lib.load().ptmi_lstm_backward_persistent, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0),
+                    dhy.data_ptr(), _lib.ptr(dc_n), w_hh_t.data_ptr(), _lib.ptr(dg), _lib.ptr(dg_t), bs_dev.data_ptr(), offs_dev.data_ptr(),
+                    _lib.ptr(step_masks), scratch.data_ptr(), _lib.ptr(dc_carry), T, max_batch, rows, H, ndir, s_begin, s_end,
+                    int(prefilled), _lib.stream(gates.device))
+    if rc == -2:
+        return False
+    _lib.check(rc, 'ptmi_lstm_backward_persistent')
+    return True
+
+
 @_register('lstm_recurrence_backward_range(Tensor gates, Tensor c, Tensor? c0, Tensor dhy, Tensor w_hh_t, Tensor(a!) dg, '
            'Tensor(b!) scratch, Tensor(c!) dc_carry, Tensor bs_dev, Tensor offs_dev, int T, int max_batch, int rows, int H, '
            'int ndir, int s_begin, int s_end, int prefilled=0, Tensor? dc_n=None) -> bool')
 def lstm_recurrence_backward_range(gates, c, c0, dhy, w_hh_t, dg, scratch, dc_carry, bs_dev, offs_dev, T, max_batch, rows, H, ndir,
                                    s_begin, s_end, prefilled=0, dc_n=None):
-    """The persistent backward recurrence over the processing steps [s_begin, s_end) (``ptmi_lstm_backward_persistent_range``;
-    ranges in order, same ``dg`` / ``scratch`` / ``dc_carry``).  False: the launch cannot be resident (nothing was run)."""
-    if dc_n is not None:        # + the gradient w.r.t. the final cell state (ptmi_lstm_backward_persistent_states; whole recurrence)
-        assert s_begin == 0 and s_end == T and dc_n.shape == (ndir, max_batch, H) and dc_n.is_contiguous(), (s_begin, s_end, dc_n.shape)
-        rc = _lib.timed('lstm_backward', _lib.load().ptmi_lstm_backward_persistent_states, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0),
-                        dhy.data_ptr(), dc_n.data_ptr(), w_hh_t.data_ptr(), dg.data_ptr(), bs_dev.data_ptr(), offs_dev.data_ptr(),
-                        scratch.data_ptr(), dc_carry.data_ptr(), T, max_batch, rows, H, ndir, int(prefilled), _lib.stream(gates.device))
-    else:
-        rc = _lib.timed('lstm_backward', _lib.load().ptmi_lstm_backward_persistent_range, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0),
-                        dhy.data_ptr(), w_hh_t.data_ptr(), dg.data_ptr(), bs_dev.data_ptr(), offs_dev.data_ptr(), scratch.data_ptr(),
-                        dc_carry.data_ptr(), T, max_batch, rows, H, ndir, s_begin, s_end, int(prefilled), _lib.stream(gates.device))
-    if rc == -2:
-        return False
-    _lib.check(rc, 'ptmi_lstm_backward_persistent_range')
-    return True
+    """The persistent backward recurrence over the processing steps [s_begin, s_end) (ranges in order, same ``dg`` / ``scratch`` /
+    ``dc_carry``); ``dc_n`` [ndir, max_batch, H]: + the gradient w.r.t. the final cell state (whole recurrence only).  False: the
+    launch cannot be resident (nothing was run)."""
+    assert dc_n is None or (dc_n.shape == (ndir, max_batch, H) and dc_n.is_contiguous()), dc_n.shape
+    return _lstm_backward_persistent(gates, c, c0, dhy, w_hh_t, dg, None, scratch, dc_carry, bs_dev, offs_dev, T, max_batch, rows, H, ndir,
+                                     s_begin, s_end, prefilled, dc_n=dc_n)
 
 
 @_register('lstm_recurrence_backward_planes(Tensor gates, Tensor c, Tensor? c0, Tensor dhy, Tensor w_hh_t, Tensor(a!)? dg, '
@@ -623,26 +629,14 @@ def lstm_recurrence_backward_range(gates, c, c0, dhy, w_hh_t, dg, scratch, dc_ca
            'int H, int ndir, int s_begin, int s_end, int prefilled=0, Tensor? step_masks=None) -> bool')
 def lstm_recurrence_backward_planes(gates, c, c0, dhy, w_hh_t, dg, dg_t, scratch, dc_carry, bs_dev, offs_dev, T, max_batch, rows, H, ndir,
                                     s_begin, s_end, prefilled=0, step_masks=None):
-    """``ptmi_lstm_backward_persistent_planes``: the persistent backward recurrence over the processing steps [s_begin, s_end) with
-    the gate gradients leaving as bf16 planes of ``dgates^T`` (``dg_t``: ``ndir * ptmi_planes_elems(4H, range rows)`` bf16 values, the
-    operand of the weight-gradient GEMMs) and, only when ``dg`` is given, as the row-major fp32 tensor too.  False: the launch
-    cannot be resident (nothing was run)."""
+    """The persistent backward recurrence over the processing steps [s_begin, s_end) with the gate gradients leaving as bf16 planes
+    of ``dgates^T`` (``dg_t``: ``ndir * ptmi_planes_elems(4H, range rows)`` bf16 values, the operand of the weight-gradient GEMMs)
+    and, only when ``dg`` is given, as the row-major fp32 tensor too; ``step_masks``: a row-slot batch (whole recurrence, no initial
+    states).  False: the launch cannot be resident (nothing was run)."""
     need = ndir * int(_lib.load().ptmi_planes_elems(4 * H, (s_end - s_begin) * max_batch))       # this step range's rows
     assert dg_t.dtype == torch.bfloat16 and dg_t.numel() >= need, (dg_t.dtype, dg_t.numel(), need)
-    if step_masks is not None:          # a row-slot batch (ptmi_lstm_backward_persistent_slots): the whole recurrence in one launch
-        assert c0 is None and s_begin == 0 and s_end == T, 'row-slot batches: no initial states, no step ranges'
-        rc = _lib.timed('lstm_backward', _lib.load().ptmi_lstm_backward_persistent_slots, gates.data_ptr(), c.data_ptr(), dhy.data_ptr(),
-                        w_hh_t.data_ptr(), _lib.ptr(dg), dg_t.data_ptr(), bs_dev.data_ptr(), offs_dev.data_ptr(), step_masks.data_ptr(),
-                        scratch.data_ptr(), T, max_batch, rows, H, ndir, int(prefilled), _lib.stream(gates.device))
-    else:
-        rc = _lib.timed('lstm_backward', _lib.load().ptmi_lstm_backward_persistent_planes, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0),
-                        dhy.data_ptr(), w_hh_t.data_ptr(), _lib.ptr(dg), dg_t.data_ptr(), bs_dev.data_ptr(), offs_dev.data_ptr(),
-                        scratch.data_ptr(), _lib.ptr(dc_carry), T, max_batch, rows, H, ndir, s_begin, s_end, int(prefilled),
-                        _lib.stream(gates.device))
-    if rc == -2:
-        return False
-    _lib.check(rc, 'ptmi_lstm_backward_persistent_planes')
-    return True
+    return _lstm_backward_persistent(gates, c, c0, dhy, w_hh_t, dg, dg_t, scratch, dc_carry, bs_dev, offs_dev, T, max_batch, rows, H, ndir,
+                                     s_begin, s_end, prefilled, step_masks=step_masks)
 
 
 @_register('lstm_bias_grad_add_(Tensor db, Tensor(a!)[] bias_ih_grad, Tensor(b!)[] bias_hh_grad) -> ()')
@@ -861,7 +855,7 @@ def lstm_recurrence_forward(gates, hy, c0, w_hh_pad, w_amax, bs_dev, offs_dev, b
     lib = _lib.load()
     dev = gates.device
     st = _lib.stream(dev)
-    # row-slot batches (step_masks: ptmi_lstm_forward_persistent_slots): idle rows are not written - they must read as zeros
+    # row-slot batches (step_masks): idle rows are not written - they must read as zeros
     c = (torch.zeros if step_masks is not None else torch.empty)((rows, ndir * H), dtype=torch.float32, device=dev)
     rc = -2
     flags = None
@@ -869,18 +863,12 @@ def lstm_recurrence_forward(gates, hy, c0, w_hh_pad, w_amax, bs_dev, offs_dev, b
         n = int(lib.ptmi_lstm_scratch_elems(T, ndir, max_batch, H, 0))
         flags = scratch if scratch is not None else torch.empty(n, dtype=torch.int32, device=dev)
         assert flags.numel() >= n and flags.dtype == torch.int32
-        if step_masks is not None:
-            assert step_masks.dtype == torch.int64 and step_masks.numel() == 3 * T and c0 is None
-            rc = _lib.timed('lstm_forward', lib.ptmi_lstm_forward_persistent_slots, gates.data_ptr(), hy.data_ptr(), c.data_ptr(),
-                            None, w_hh_pad.data_ptr(), _lib.ptr(w_amax), bs_dev.data_ptr(), offs_dev.data_ptr(), step_masks.data_ptr(),
-                            flags.data_ptr(), T, max_batch, rows, H, KP, ndir, int(bool(prefilled and scratch is not None)),
-                            _lib.ptr(backward_scratch), st)
-        else:
-            rc = _lib.timed('lstm_forward', lib.ptmi_lstm_forward_persistent, gates.data_ptr(), hy.data_ptr(), c.data_ptr(),
-                            _lib.ptr(c0), w_hh_pad.data_ptr(), _lib.ptr(w_amax), bs_dev.data_ptr(), offs_dev.data_ptr(),
-                            flags.data_ptr(), T, max_batch, rows, H, KP, ndir, int(bool(prefilled and scratch is not None)),
-                            _lib.ptr(backward_scratch), st)
-        if rc not in (0, -2) or (step_masks is not None and rc != 0):
+        assert step_masks is None or (step_masks.dtype == torch.int64 and step_masks.numel() == 3 * T)
+        rc = _lib.timed('lstm_forward', lib.ptmi_lstm_forward_persistent, gates.data_ptr(), hy.data_ptr(), c.data_ptr(),
+                        _lib.ptr(c0), w_hh_pad.data_ptr(), _lib.ptr(w_amax), bs_dev.data_ptr(), offs_dev.data_ptr(),
+                        _lib.ptr(step_masks), flags.data_ptr(), T, max_batch, rows, H, KP, ndir,
+                        int(bool(prefilled and scratch is not None)), _lib.ptr(backward_scratch), st)
+        if rc != -2 or step_masks is not None:          # (a row-slot batch has no step-per-launch form)
             _lib.check(rc, 'ptmi_lstm_forward_persistent')
     if rc == -2:        # configuration not resident-able: one launch per timestep
         flags = None
@@ -899,31 +887,22 @@ def lstm_recurrence_backward(gates, c, c0, dhy, w_hh_t, bs_dev, offs_dev, bs_hos
     and, for the split kernels, the word with max |dgates| (see ``ops.lstm``)."""
     lib = _lib.load()
     dev = gates.device
-    st = _lib.stream(dev)
     dg = torch.empty_like(gates)
-    rc = -2
     flags = None
     if persistent:
         n = int(lib.ptmi_lstm_scratch_elems(T, ndir, max_batch, H, 1))
         flags = scratch if scratch is not None else torch.empty(n, dtype=torch.int32, device=dev)
         assert flags.numel() >= n and flags.dtype == torch.int32
-        if step_masks is not None:      # row-slot batch
-            assert c0 is None
-            rc = _lib.timed('lstm_backward', lib.ptmi_lstm_backward_persistent_slots, gates.data_ptr(), c.data_ptr(), dhy.data_ptr(),
-                            w_hh_t.data_ptr(), dg.data_ptr(), None, bs_dev.data_ptr(), offs_dev.data_ptr(), step_masks.data_ptr(),
-                            flags.data_ptr(), T, max_batch, rows, H, ndir, int(prefilled) if scratch is not None else 0, st)
-        else:
-            rc = _lib.timed('lstm_backward', lib.ptmi_lstm_backward_persistent, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0),
-                            dhy.data_ptr(), w_hh_t.data_ptr(), dg.data_ptr(), bs_dev.data_ptr(), offs_dev.data_ptr(),
-                            flags.data_ptr(), T, max_batch, rows, H, ndir, int(prefilled) if scratch is not None else 0, st)
-        if rc not in (0, -2) or (step_masks is not None and rc != 0):
-            _lib.check(rc, 'ptmi_lstm_backward_persistent')
-    if rc == -2:
+        persistent = _lstm_backward_persistent(gates, c, c0, dhy, w_hh_t, dg, None, flags, None, bs_dev, offs_dev, T, max_batch, rows, H,
+                                               ndir, 0, T, int(prefilled) if scratch is not None else 0, step_masks=step_masks)
+        if not persistent and step_masks is not None:          # (a row-slot batch has no step-per-launch form)
+            _lib.check(-2, 'ptmi_lstm_backward_persistent')
+    if not persistent:
         flags = None
         dcs = torch.empty((max_batch, ndir, H), dtype=torch.float32, device=dev)
         _lib.check(_lib.timed('lstm_backward', lib.ptmi_lstm_backward, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0), dhy.data_ptr(),
                               w_hh_t.data_ptr(), dg.data_ptr(), dcs.data_ptr(), ctypes.c_void_p(bs_host), ctypes.c_void_p(offs_host),
-                              T, max_batch, H, ndir, st), 'ptmi_lstm_backward')
+                              T, max_batch, H, ndir, _lib.stream(dev)), 'ptmi_lstm_backward')
     return dg, flags
 
 

@@ -154,7 +154,7 @@ def _backward_plan(ctx, lib, x, h0, ndir, H, has_grads, has_dc):
     ``chunks``: launches of the recurrence.  The TOP layer's backward recurrence runs while the weight-gradient queue is still
     empty; for long batches, where that queue is the critical one of the backward phase (16 kHz configurations: 11.9 ms of GEMMs
     and pack passes beside 9.7 ms of recurrences), it runs as two launches over step ranges and the finished half's weight
-    gradients start under the second launch (ptmi_lstm_backward_persistent_range).  For every layer, or at B = 32 / T = 253, the
+    gradients start under the second launch (s_begin / s_end of ptmi_lstm_backward_persistent).  For every layer, or at B = 32 / T = 253, the
     same cut measured neutral to slower (a recurrence next to GEMMs loses what the GEMMs gain): c3 23.97 -> 23.55 ms with the top
     layer in two launches, 23.35 / 23.33 in three / four, 23.70 with every layer in two.
     (The BOTTOM layer in two launches - its first half's weight gradients under its second launch instead of in the step's tail -
@@ -228,7 +228,7 @@ def _backward_planes(lib, meta, plan, job, saved, scratch_b, pre_b, ndir, G, H):
         #  not end up behind the side queue's GEMMs - ops.wgrad)
         ok, dg_t, part_t = _launch_planes_range(lib, meta, saved, flags, carry, pre, plan.masks, ndir, G, H, cuts[i], cuts[i + 1])
         if not ok:
-            raise RuntimeError('ptmi_lstm_backward_persistent_planes: a later range was refused')
+            raise RuntimeError('ptmi_lstm_backward_persistent: a later range was refused')
         plan.side.wait_event(done)
         job.rows(None, finished_part, None, dg_t=finished)        # the finished range, under the next launch
         finished.record_stream(plan.side)
@@ -261,7 +261,7 @@ def _backward_ranges(lib, meta, plan, job, saved, scratch_b, pre_b, ndir, G, H, 
             ndir, cuts[i], cuts[i + 1], pre, dcn)
         if not ok:
             if i:
-                raise RuntimeError('ptmi_lstm_backward_persistent_range: a later range was refused')
+                raise RuntimeError('ptmi_lstm_backward_persistent: a later range was refused')
             if plan.state_grad:                          # (else not resident: the one-call path decides)
                 raise NotImplementedError('gradients w.r.t. the initial LSTM state: this configuration cannot run on the '
                                           'persistent kernels')

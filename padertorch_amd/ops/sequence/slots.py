@@ -6,7 +6,7 @@ take part (``DESIGN.md`` section 3.3) -, and a PackedSequence batch runs the lon
 (lengths ~ U[3 s, 6 s]: 23 of 32 rows busy on average).  A :class:`SlotLayout` places the sequences END TO END into ``slots`` row
 slots (longest-processing-time first: every sequence goes to the slot that is shortest so far), so that ``B`` sequences take about
 ``sum(lengths) / slots`` steps: 44 examples of that distribution fit the ~390 steps that 32 of them cost as a PackedSequence.
-The kernels reset (h, c) at every sequence boundary through per-step row masks (``ptmi_lstm_forward_persistent_slots``): per
+The kernels reset (h, c) at every sequence boundary through per-step row masks (``step_masks`` of ``ptmi_lstm_forward_persistent``): per
 sequence the results are those of one sequence per row, i.e. of ``torch.nn.LSTM`` on the PackedSequence
 (``pit/model.py:60-66,97``).  torch's PackedSequence cannot express the layout; the models keep their list-of-tensors contract and
 scatter / gather at the edges (:meth:`SlotLayout.scatter_rows` / :meth:`gather_rows`: one index pass each).
@@ -158,7 +158,7 @@ class StaticSlots:
     """A row-slot layout of FIXED capacity whose length pattern is DEVICE data: ``examples`` sequences of at most ``padded_time``
     frames, end to end in ``slots`` row slots of ``steps`` time steps.  Every shape a kernel launch depends on - the grid ``[steps,
     slots]``, the batch-major padded tensors ``[examples, padded_time, ...]`` - is a constant of the object; which grid row holds which
-    frame, where sequences start and end (the recurrences' per-step row masks, ``ptmi_lstm_*_persistent_slots``), the predecessor rows
+    frame, where sequences start and end (the recurrences' per-step row masks, ``step_masks`` of ``ptmi_lstm_*_persistent``), the predecessor rows
     of the weight-gradient operand and the examples' frame counts are tensors that :meth:`set` rewrites for every batch.  One captured
     optimizer step (``train.graphed.GraphedStep``) therefore serves every batch that FITS - the variable-length utterances the reference
     trains on (``pit/data.py:20-33,49-77``: lengths ~ U[3 s, 6 s]) - instead of one graph per length pattern.

@@ -165,7 +165,7 @@ def test_pit_step_random_small_configurations_vs_oracle(seed):
                                                   (5, 1, 8, 2)])
 def test_pit_step_on_row_slots_vs_oracle(B, slots, units, layers, in_place):
     """Ragged batches on the row-slot layout (model.row_slots; ops.sequence.SlotLayout): 2 - 5 sequences lie end to end in every
-    row slot, the recurrences reset (h, c) at the boundaries in both directions (ptmi_lstm_forward / backward_persistent_slots), idle
+    row slot, the recurrences reset (h, c) at the boundaries in both directions (``step_masks`` of ptmi_lstm_forward / backward_persistent), idle
     slot steps contribute nothing.  The whole step - masks of every example, both losses, every parameter gradient - against the
     oracle, which knows nothing of slots (one sequence per row, torch.nn.LSTM on the PackedSequence).  in_place: the Trainer's route
     (weight gradients accumulated in place on the side stream); with 16 / 32 / 64 slots the recurrences' planes then serve the

@@ -15,6 +15,7 @@ DEV = 'cuda:0'
     (257, 600, 1, True, [40, 37, 37, 20, 9, 3]),          # model size, ragged, B < 16
     (1200, 600, 1, True, [23] * 40 + [11] * 5),           # B > 32: two M chunks
     (64, 600, 1, True, [9] * 60 + [7] * 6 + [2] * 4),     # B = 70: row tiles run as several persistent launches
+    (20, 600, 1, True, [4] * 112),           # B = 112: the forward AND the backward recurrence take two launches each (2 + 2 / 3 + 1 row tiles)
 ])
 def test_packed_lstm_vs_torch_cpu(I, H, layers, bidir, lens, monkeypatch):
     from padertorch_amd.ops import packed_lstm, lstm as L
@@ -283,8 +284,8 @@ def test_weight_prep_of_parameters_at_odd_addresses():
 @pytest.mark.parametrize('lens', [[130] * 32, [200, 180, 180, 131, 77, 64, 3]])
 def test_in_place_weight_gradients_and_time_ranges(lens, monkeypatch):
     """The Trainer's path - weight gradients accumulated in place on the side stream - against autograd through torch's CPU
-    LSTM; then the backward recurrence of the same layer in TWO launches over step ranges (the C ABI's
-    ptmi_lstm_backward_persistent_range, whose whole-range form the initial-state gradients use): bit-identical gate gradients."""
+    LSTM; then the backward recurrence of the same layer in TWO launches over step ranges (s_begin / s_end of the C ABI's
+    ptmi_lstm_backward_persistent, whose whole-range form the initial-state gradients use): bit-identical gate gradients."""
     import copy
     from padertorch_amd.ops import lstm as L
     from padertorch_amd.ops import packed_lstm
@@ -385,7 +386,7 @@ def test_gradients_through_the_final_state(lens, with_hx):
     """``packed_lstm(..., return_state=True)`` returns ``(h_n, c_n)`` WITH their graph, like ``torch.nn.LSTM`` (the reference's
     StatefulLSTM hands them on, modules/recurrent.py:42): a loss on the output, on h_n and on c_n - parameter, input and initial-state
     gradients against torch's CPU LSTM (the gradient of c_n enters the backward kernel at every sequence's last step:
-    ptmi_lstm_backward_persistent_states), two layers, both directions, equal and ragged lengths."""
+    ``dc_n`` of ptmi_lstm_backward_persistent), two layers, both directions, equal and ragged lengths."""
     from padertorch_amd.ops import lstm as L
     torch.manual_seed(21)
     I, H, layers = 10, 12, 2
@@ -516,9 +517,10 @@ def test_recurrences_next_to_a_cu_occupying_kernel(wgs, threads, lds, monkeypatc
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('B,T,H,ndir', [(32, 21, 600, 2), (16, 9, 40, 2), (64, 11, 600, 2), (48, 7, 100, 1), (16, 5, 20, 1)])
+@pytest.mark.parametrize('B,T,H,ndir', [(32, 21, 600, 2), (16, 9, 40, 2), (64, 11, 600, 2), (48, 7, 100, 1), (16, 5, 20, 1),
+                                        (112, 4, 600, 2)])         # (the last: two launches over groups of row tiles)
 def test_backward_recurrence_hands_the_weight_gradient_operand_on(B, T, H, ndir):
-    """``ptmi_lstm_backward_persistent_planes``: the gate gradients leave the backward recurrence as bf16 (hi, lo) planes of
+    """``dgates_t`` of ``ptmi_lstm_backward_persistent``: the gate gradients leave the backward recurrence as bf16 (hi, lo) planes of
     ``dgates^T`` - bit for bit what ``ptmi_pack_planes_t_bf16`` makes of the row-major fp32 gate gradients of the plain launch
     (both are the same two roundings of the same fp32 values), with and without the row-major tensor next to them, for the whole
     recurrence and for two launches over step ranges (each range's planes hold that range's rows per direction); odd row counts
