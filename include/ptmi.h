@@ -695,6 +695,35 @@ int ptmi_gemm_planes_bf16(const uint16_t* a, const uint16_t* b, const float* bia
 int ptmi_gemm_planes_bf16_two(const uint16_t* a, const uint16_t* b, float* c, float* c2, int32_t m_split, int64_t ldc, int32_t m,
                               int32_t n, int32_t k, int32_t accumulate, int32_t split_k, int32_t products, float* workspace,
                               ptmi_stream_t stream);
+/* A GROUP of products over one reduction axis as ONE launch of the big-tile kernel and ONE slab reduction: a BLSTM layer's four weight
+ * gradients dW_ih_f = dG_f^T X, dW_ih_b = dG_b^T X, dW_hh_f = dG_f^T H_f,prev, dW_hh_b = dG_b^T H_b,prev (torch.nn.LSTM backward inside
+ * pit/model.py:60-66,97), whose operands reduce over the same packed rows.
+ *   a, m, m_split   bf16 planes of the m x k operand A; rows below m_split are part 0, the rest part 1 (as in ptmi_gemm_planes_bf16_two)
+ *   b, n, segments  1..3 B segments: host arrays of the segments' plane buffers (n[s] x k, each packed on its own, 16-byte aligned)
+ *                   and column counts
+ *   c, ldc          host arrays [2 * segments], entry part * segments + s: where the block (part, segment) goes (rows of the part x
+ *                   n[s], row stride ldc >= n[s]), or NULL: the block is skipped (no work item, no store)
+ *   split_k         the most k ranges the workspace holds (>= 1); tile and k ranges are picked by the cost model of the plain calls
+ *                   over the work items (k range, block, tile) of ALL blocks - a function of the shapes alone (PTMI_GEMM_TILE pins
+ *                   the tile and takes split_k as it is)
+ *   workspace       ptmi_gemm_planes_group_workspace_elems floats, 16-byte aligned: per block its slabs [k ranges][rows][n[s]]; the
+ *                   reduction sums them in slab order and honours accumulate and every block's ldc.  No atomics, no workgroup waits
+ *                   for another (safe beside a persistent recurrence); two identical calls give identical bits.
+ * Returns PTMI_E_UNSUPPORTED - and launches nothing - where the big-tile path is not possible: the cost model picks the 128 x 128
+ * kernel, m_split % 16 != 0, or an operand's planes reach 2 GB; the caller then issues separate calls.
+ * ptmi_gemm_planes_group_plan: 100 * tile + k ranges of such a call (tile 5: it would be refused), -1: invalid arguments. */
+int ptmi_gemm_planes_bf16_group(const uint16_t* a, int32_t m, int32_t m_split, const uint16_t* const* b, const int32_t* n, int32_t segments,
+                                float* const* c, const int64_t* ldc, int32_t k, int32_t accumulate, int32_t split_k, int32_t products,
+                                float* workspace, ptmi_stream_t stream);
+int64_t ptmi_gemm_planes_group_workspace_elems(int32_t m, int32_t m_split, const int32_t* n, int32_t segments, float* const* c, int32_t k,
+                                               int32_t split_k);
+int32_t ptmi_gemm_planes_group_plan(int32_t m, int32_t m_split, const int32_t* n, int32_t segments, float* const* c, int32_t k,
+                                    int32_t split_k);
+/* ptmi_pack_planes_t_bf16 for 1..3 sources x[i] ([k_rows][cols[i]], row stride ld[i]) with one k_rows in ONE launch, each into planes
+ * out[i] of its own (ptmi_planes_elems(cols[i], k_rows) values) - the B segments of the call above.  Host arrays.  The planes are
+ * bit for bit those of separate ptmi_pack_planes_t_bf16 calls (sources whose rows are not 16-byte aligned are read with scalar loads). */
+int ptmi_pack_planes_t_bf16_list(const float* const* x, const int64_t* cols, const int64_t* ld, uint16_t* const* out, int32_t sources,
+                                 int64_t k_rows, ptmi_stream_t stream);
 /* Calls without split K run on a persistent big-tile kernel (8 wavefronts, workgroup tile picked per problem by a cost model:
  * 0 = 256 x 320, 1 = 256 x 256, 2 = 256 x 192, 3 = 128 x 320, 4 = 128 x 256) or on the 128 x 128 kernel (5) that also carries
  * every co-resident split-K call; ptmi_gemm_planes_plan reports the choice.  (Tests and sweeps pin a tile through the environment

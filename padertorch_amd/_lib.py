@@ -143,6 +143,10 @@ SIGNATURES = {
     'ptmi_gemm_planes_bf16': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     'ptmi_gemm_planes_bf16_two': (c_int, [_P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     'ptmi_gemm_planes_plan': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
+    'ptmi_gemm_planes_bf16_group': (c_int, [_P, c_int32, c_int32, _P, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    'ptmi_gemm_planes_group_workspace_elems': (c_int64, [c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32]),
+    'ptmi_gemm_planes_group_plan': (c_int32, [c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32]),
+    'ptmi_pack_planes_t_bf16_list': (c_int, [_P, _P, _P, _P, c_int32, c_int64, _P]),
     'ptmi_comm_rccl_version': (c_int32, []),
     'ptmi_comm_unique_id': (c_int, [_P]),
     'ptmi_comm_create': (c_int, [_P, c_int32, c_int32, _P]),

@@ -248,9 +248,31 @@ struct BigArgs {
     unsigned* amax_out = nullptr;
 };
 
-template <bool BF16, int MT, int NT, bool ONE, bool RELU = false>
-__global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G) {
+// Grouped call (ptmi_gemm_planes_bf16_group): operand A in two parts (rows below / from m_split), up to three B segments with planes and
+// column counts of their own (one K), and a product per (part, segment) BLOCK that is not skipped - a BLSTM layer's four weight gradients
+// {dG_f, dG_b} x {X, H_f, H_b} without (f, H_b) and (b, H_f).  Work item = (k range, block, tile), range-major over the tiles of all
+// blocks; every item leaves its partial product in its block's slabs [splits][rows][cols] (at slab_off + z * slab_stride), summed in
+// slab order by ONE planes_reduce_kernel(ReduceGroupArgs) launch.  BigArgs' A / a_bytes / KB / splits / kb_per_split / slabs / band hold.
+constexpr int GROUP_SEGS = 3, GROUP_BLOCKS = 6;
+struct GroupTable {
+    const uint4* B[GROUP_SEGS];             // per segment: planes, their extent in bytes, 16-row tiles
+    unsigned b_bytes[GROUP_SEGS];
+    int rtb[GROUP_SEGS];
+    int part_rt0[2], part_rts[2];           // per part of A: first 16-row tile, number of them
+    int tile_start[GROUP_BLOCKS + 1];       // per block (the skipped ones left out): first tile; past the last block: INT_MAX,
+    int total_tiles;                        //   and the tiles of all blocks
+    int tiles_m[GROUP_BLOCKS], tiles_n[GROUP_BLOCKS], part[GROUP_BLOCKS], seg[GROUP_BLOCKS], rows[GROUP_BLOCKS], cols[GROUP_BLOCKS];
+    long long slab_off[GROUP_BLOCKS], slab_stride[GROUP_BLOCKS];          // floats, multiples of 4
+};
+struct GroupBigArgs : BigArgs {
+    GroupTable T;
+};
+
+// (ARGS = GroupBigArgs: the grouped call's instantiations - bf16 planes, slabs only)
+template <bool BF16, int MT, int NT, bool ONE, bool RELU = false, class ARGS = BigArgs>
+__global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const ARGS G) {
 #if __HIP_DEVICE_COMPILE__
+    constexpr bool GROUP = __is_same(ARGS, GroupBigArgs);
     constexpr int WM = 2, WN = 4, RA = WM * MT, RB = WN * NT, PIECES = 2 * (RA + RB);
     constexpr int PA = 2 * RA / 8, PB = 2 * RB / 8, PW = PA + PB;          // 1 KB plane tiles every wavefront copies per k step
     static_assert((2 * RA) % 8 == 0 && (2 * RB) % 8 == 0, "pieces per wave");
@@ -263,12 +285,13 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
     const int voff = lane * 16;
     const int KB = G.KB;
     const int rta = (G.M + 15) / 16, rtb = (G.N + 15) / 16;
-    const float inv = 1.f / (plane_scale(G.amax_a) * plane_scale(G.amax_b));
+    const float inv = GROUP ? 1.f : 1.f / (plane_scale(G.amax_a) * plane_scale(G.amax_b));
 
     // this workgroup's work items: workgroup id b runs on XCD b % 8; every XCD owns one contiguous range of the item list - k range
     // by k range the band-major tile list (bands of G.band tile rows, column by column) -, of which its j-th workgroup takes every
     // (grid / 8)-th
-    const int TT = G.tiles_m * G.tiles_n;
+    int TT = G.tiles_m * G.tiles_n;
+    if constexpr (GROUP) TT = G.T.total_tiles;
     const int T = TT * G.splits;
     const int xcd = blockIdx.x & 7, j0 = blockIdx.x >> 3, per = gridDim.x >> 3;
     const int q = T / 8, r8 = T % 8;
@@ -284,7 +307,39 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
         tn = rem / h;
         tm = b * G.band + (rem - tn * h);
     };
-    const int KBS = G.splits > 1 ? G.kb_per_split : KB;        // k blocks per work item (the last range may be shorter)
+    // grouped call: what an item's loads and stores need of its block (workgroup-uniform: scalar registers, looked up once per item)
+    struct Blk {
+        int a_rt0, a_rts, b_rts;            // A: first 16-row tile of the part and how many; B: 16-row tiles of the segment
+        __amdgpu_buffer_rsrc_t rb;
+        int rows, cols;
+        long long slab;                     // slab 0 of the block
+        long long slab_stride;
+    };
+    auto tile_rc_group = [&](int item, int& tm, int& tn, int& z, Blk& k) {
+        if constexpr (GROUP) {
+            z = item / TT;
+            int idx = item - z * TT, blk = 0;
+#pragma unroll
+            for (int b = 1; b < GROUP_BLOCKS; ++b) blk += idx >= G.T.tile_start[b] ? 1 : 0;
+            idx -= G.T.tile_start[blk];
+            const int tiles_m = G.T.tiles_m[blk], tiles_n = G.T.tiles_n[blk];
+            const int bt = G.band * tiles_n;
+            const int b = idx / bt, rem = idx - b * bt;
+            const int h = min(G.band, tiles_m - b * G.band);
+            tn = rem / h;
+            tm = b * G.band + (rem - tn * h);
+            const int p = G.T.part[blk], s = G.T.seg[blk];
+            k.a_rt0 = G.T.part_rt0[p];
+            k.a_rts = G.T.part_rts[p];
+            k.b_rts = G.T.rtb[s];
+            k.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(G.T.B[s]), 0, G.T.b_bytes[s], 0x00020000);
+            k.rows = G.T.rows[blk];
+            k.cols = G.T.cols[blk];
+            k.slab = G.T.slab_off[blk];
+            k.slab_stride = G.T.slab_stride[blk];
+        }
+    };
+    const int KBS = (GROUP || G.splits > 1) ? G.kb_per_split : KB;        // k blocks per work item (the last range may be shorter)
     auto issue = [&](int i, int tm, int tn, int kb, int st) {            // piece i of this wavefront for (tile, k step) into stage st
         if (i < PA) {
             const int f = wave * PA + i;
@@ -298,6 +353,20 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, &lds[(st * PIECES + 2 * RA + f) * FR], 16, voff, ((rt * KB + kb) * 2 + (f & 1)) * 1024, 0, 0);
         }
     };
+    // the same for an item of a grouped call: row tiles counted within the part / segment (a tile never reaches into the next part)
+    auto issue_group = [&](int i, int tm, int tn, int kb, int st, int a_rt0, int a_rts, int b_rts, __amdgpu_buffer_rsrc_t rbk) {
+        if (i < PA) {
+            const int f = wave * PA + i;
+            const int rt = a_rt0 + min(tm * RA + (f >> 1), a_rts - 1);
+            if (!ONE || !(f & 1))
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, &lds[(st * PIECES + f) * FR], 16, voff, ((rt * KB + kb) * 2 + (f & 1)) * 1024, 0, 0);
+        } else {
+            const int f = wave * PB + (i - PA);
+            const int rt = min(tn * RB + (f >> 1), b_rts - 1);
+            if (!ONE || !(f & 1))
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rbk, &lds[(st * PIECES + 2 * RA + f) * FR], 16, voff, ((rt * KB + kb) * 2 + (f & 1)) * 1024, 0, 0);
+        }
+    };
 
     f4 acc[MT][NT];
 #pragma unroll
@@ -306,9 +375,16 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
         for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
 
     int idx = j0, tm, tn, tz;
-    tile_rc(first + idx, tm, tn, tz);
+    Blk bk{}, nbk{};
+    if constexpr (GROUP) {
+        tile_rc_group(first + idx, tm, tn, tz, bk);
 #pragma unroll
-    for (int i = 0; i < PW; ++i) issue(i, tm, tn, tz * KBS, 0);
+        for (int i = 0; i < PW; ++i) issue_group(i, tm, tn, tz * KBS, 0, bk.a_rt0, bk.a_rts, bk.b_rts, bk.rb);
+    } else {
+        tile_rc(first + idx, tm, tn, tz);
+#pragma unroll
+        for (int i = 0; i < PW; ++i) issue(i, tm, tn, tz * KBS, 0);
+    }
     int st = 0;
     constexpr int PPI = (PW + MT - 1) / MT;             // pieces issued per row-tile iteration
     unsigned relu_max = 0u;                             // (G.relu: the largest output of all this workgroup's tiles, one atomic at the end)
@@ -316,7 +392,12 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
         const int nidx = idx + per;
         const bool has_next_tile = nidx < cnt;
         int ntm = tm, ntn = tn, ntz = tz;
-        if (has_next_tile) tile_rc(first + nidx, ntm, ntn, ntz);
+        if constexpr (GROUP) {
+            nbk = bk;
+            if (has_next_tile) tile_rc_group(first + nidx, ntm, ntn, ntz, nbk);
+        } else {
+            if (has_next_tile) tile_rc(first + nidx, ntm, ntn, ntz);
+        }
         const int kb_lo = tz * KBS, kb_hi = min(KB, kb_lo + KBS);
         for (int kb = kb_lo; kb < kb_hi; ++kb) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wavefront's pieces of stage `st` have landed
@@ -325,6 +406,8 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
             // very last step: this tile's first stage once more - never read, keeps the loop free of branches)
             const bool last = kb + 1 == kb_hi;
             const int ptm = last ? ntm : tm, ptn = last ? ntn : tn, pkb = last ? ntz * KBS : kb + 1;
+            const int pa0 = last ? nbk.a_rt0 : bk.a_rt0, pas = last ? nbk.a_rts : bk.a_rts, pbs = last ? nbk.b_rts : bk.b_rts;
+            const __amdgpu_buffer_rsrc_t prb = last ? nbk.rb : bk.rb;
             const uint4* sa = &lds[(st * PIECES + wm * MT * 2) * FR + lane];
             const uint4* sb = &lds[(st * PIECES + 2 * RA + wn * NT * 2) * FR + lane];
             h8 bh[NT], bl[NT];
@@ -342,8 +425,13 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
                     nl = ONE ? nh : __builtin_bit_cast(h8, sa[((i + 1) * 2 + 1) * FR]);
                 }
 #pragma unroll
-                for (int pc = i * PPI; pc < (i + 1) * PPI; ++pc)
-                    if (pc < PW) issue(pc, ptm, ptn, pkb, st ^ 1);
+                for (int pc = i * PPI; pc < (i + 1) * PPI; ++pc) {
+                    if constexpr (GROUP) {
+                        if (pc < PW) issue_group(pc, ptm, ptn, pkb, st ^ 1, pa0, pas, pbs, prb);
+                    } else {
+                        if (pc < PW) issue(pc, ptm, ptn, pkb, st ^ 1);
+                    }
+                }
                 // D[n = 4 (lane >> 4) + e][m = lane & 15]: the MFMA's "a" operand is the B fragment, so a lane holds four consecutive
                 // columns of C; product kind outermost: NT independent MFMAs between two on one accumulator
 #pragma unroll
@@ -374,24 +462,27 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
                 }
             }
             const int mrow = (tm * WM + wm) * MT * 16 + r;
-            if (G.splits > 1) {         // the partial product of this k range: slab tz, row stride N (planes_reduce_kernel adds bias / C)
-                float* const srow = G.slabs + ((long long)tz * G.M + mrow) * G.N + n0;
-                const bool svec = (G.N & 3) == 0 && (reinterpret_cast<unsigned long long>(G.slabs) & 15) == 0;
-                const bool sfull = svec && (tn * WN + wn + 1) * NT * 16 <= G.N;
+            if (GROUP || G.splits > 1) {         // the partial product of this k range: slab tz, row stride N (planes_reduce_kernel adds bias / C)
+                // (grouped call: slab tz of the item's block, that block's rows and columns)
+                const int sM = GROUP ? bk.rows : G.M, sN = GROUP ? bk.cols : G.N;
+                float* const srow = GROUP ? G.slabs + bk.slab + tz * bk.slab_stride + (long long)mrow * sN + n0
+                                          : G.slabs + ((long long)tz * G.M + mrow) * G.N + n0;
+                const bool svec = (sN & 3) == 0 && (reinterpret_cast<unsigned long long>(G.slabs) & 15) == 0;
+                const bool sfull = svec && (tn * WN + wn + 1) * NT * 16 <= sN;
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
-                    const bool ok = mrow + i * 16 < G.M;
+                    const bool ok = mrow + i * 16 < sM;
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
                         const f4 v = acc[i][j] * inv;
                         acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-                        float* o = srow + (long long)i * 16 * G.N + j * 16;
+                        float* o = srow + (long long)i * 16 * sN + j * 16;
                         if (sfull) {
                             if (ok) *reinterpret_cast<f4*>(o) = v;
                         } else {
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                if (ok && n0 + j * 16 + e < G.N) o[e] = v[e];
+                                if (ok && n0 + j * 16 + e < sN) o[e] = v[e];
                         }
                     }
                 }
@@ -400,6 +491,7 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_big_kernel(const BigArgs G
                 tm = ntm;
                 tn = ntn;
                 tz = ntz;
+                if constexpr (GROUP) bk = nbk;
                 continue;
             }
             // row of subtile i (two-part output: rows from m_split on live in C2)
@@ -577,6 +669,47 @@ __global__ __launch_bounds__(256) void planes_reduce_kernel(const float* __restr
     }
 }
 
+// The same pass behind a grouped call: every block's slabs summed in slab order into that block's output (row stride of its own:
+// views into wider .grad buffers), ONE launch over the elements of all blocks
+struct ReduceGroupArgs {
+    const float* ws;
+    int splits, nblocks, accumulate;
+    long long start[GROUP_BLOCKS + 1];          // first UNIT of block b in the launch's flat index (past the last block: the total)
+    long long slab_off[GROUP_BLOCKS], slab_stride[GROUP_BLOCKS];
+    float* C[GROUP_BLOCKS];
+    long long ldc[GROUP_BLOCKS];
+    int cols[GROUP_BLOCKS];
+    int vec[GROUP_BLOCKS];                      // unit = 4 consecutive elements of a row (cols, ldc multiples of 4, C 16-byte aligned), else 1
+};
+
+__global__ __launch_bounds__(256) void planes_reduce_kernel(const ReduceGroupArgs R) {
+    const long long total = R.start[R.nblocks];
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        int b = 0;
+#pragma unroll
+        for (int q = 1; q < GROUP_BLOCKS; ++q) b += (q < R.nblocks && i >= R.start[q]) ? 1 : 0;
+        const int N = R.cols[b];
+        const long long stride = R.slab_stride[b];
+        if (R.vec[b]) {
+            const long long j = (i - R.start[b]) * 4;
+            const int r = (int)(j / N), c = (int)(j - (long long)r * N);
+            const float* w = R.ws + R.slab_off[b] + j;
+            f4 sum = {0.f, 0.f, 0.f, 0.f};
+            for (int z = 0; z < R.splits; ++z) sum += *reinterpret_cast<const f4*>(w + (long long)z * stride);
+            f4* o = reinterpret_cast<f4*>(R.C[b] + (long long)r * R.ldc[b] + c);
+            *o = R.accumulate ? *o + sum : sum;
+        } else {
+            const long long j = i - R.start[b];
+            const int r = (int)(j / N), c = (int)(j - (long long)r * N);
+            const float* w = R.ws + R.slab_off[b] + j;
+            float sum = 0.f;
+            for (int z = 0; z < R.splits; ++z) sum += w[(long long)z * stride];
+            float* o = R.C[b] + (long long)r * R.ldc[b] + c;
+            *o = R.accumulate ? *o + sum : sum;
+        }
+    }
+}
+
 // dx of a ReLU and the operand scale of what multiplies it next, one pass: out = 0 where y <= 0 (y: the ReLU's OUTPUT), else g - torch's
 // threshold_backward, which lets the gradient through where y is NaN; float bits
 // of max |out| into *amax_out (zeroed by the host call)
@@ -661,14 +794,13 @@ __global__ __launch_bounds__(256) void pack_planes_t_kernel(const float* __restr
 // read whole rows.  scripts/mb/pack_t.hip: 32192 x 2400 of 4800 columns 153 -> 117 us, 32192 x 1200 82 -> 52 us (a copy of the same
 // bytes: 121 / 52 us); wider tiles or strips with the next tile's loads in flight are no faster.
 template <bool BF16>
-__global__ __launch_bounds__(256) void pack_planes_t4_kernel(const float* __restrict__ x, long long krows, long long cols, long long ld,
-                                                             const unsigned* __restrict__ amax, uint4* __restrict__ out, long long KBS,
-                                                             long long KBO) {
+__device__ __forceinline__ void pack_planes_t4_block(const float* __restrict__ x, long long krows, long long cols, long long ld, float s,
+                                                     uint4* __restrict__ out, long long KBS, long long KBO, long long kb, long long cblock,
+                                                     bool aligned) {
     constexpr int P = 68;                                   // row pitch: float4 stores stay aligned
     __shared__ float tile[32 * P];
     const int tid = threadIdx.x;
-    const long long kb = blockIdx.y, c0 = (long long)blockIdx.x * 64;
-    const float s = plane_scale(amax);
+    const long long c0 = cblock * 64;
     const int lx = tid & 15, ly = tid >> 4;
     f4 regs[2];
 #pragma unroll
@@ -676,7 +808,7 @@ __global__ __launch_bounds__(256) void pack_planes_t4_kernel(const float* __rest
         const long long k = kb * 32 + ly + p * 16, c = c0 + lx * 4;
         f4 z = {0.f, 0.f, 0.f, 0.f};
         if (k < krows) {
-            if (c + 4 <= cols) {
+            if (aligned && c + 4 <= cols) {
                 z = *reinterpret_cast<const f4*>(x + k * ld + c);
             } else {
 #pragma unroll
@@ -690,13 +822,41 @@ __global__ __launch_bounds__(256) void pack_planes_t4_kernel(const float* __rest
     for (int p = 0; p < 2; ++p) *reinterpret_cast<f4*>(&tile[(ly + p * 16) * P + lx * 4]) = regs[p] * s;
     __syncthreads();
     const int rl = tid >> 6, g = (tid >> 4) & 3, r = tid & 15;
-    const long long rt = (long long)blockIdx.x * 4 + rl;
+    const long long rt = cblock * 4 + rl;
     if (rt * 16 >= ((cols + 15) / 16) * 16) return;
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = tile[(g * 8 + e) * P + rl * 16 + r];
     uint4* o = out + ((rt * KBS + KBO + kb) * 2) * FR + g * 16 + r;
     split_chunk<BF16>(v, o, o + FR);
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(256) void pack_planes_t4_kernel(const float* __restrict__ x, long long krows, long long cols, long long ld,
+                                                             const unsigned* __restrict__ amax, uint4* __restrict__ out, long long KBS,
+                                                             long long KBO) {
+    pack_planes_t4_block<BF16>(x, krows, cols, ld, plane_scale(amax), out, KBS, KBO, blockIdx.y, blockIdx.x, true);
+}
+
+// Up to three sources with one k extent in ONE launch (a BLSTM layer's x, h_prev forward, h_prev reverse: the B segments of
+// ptmi_gemm_planes_bf16_group), every source into planes of its own: the column blocks of the sources lie behind each other in
+// grid.x.  A source whose rows are not 16-byte aligned (the 257-column input) is read with scalar loads - the same values, so
+// either way the planes are those of a launch of its own.
+constexpr int PACK_SRCS = 3;
+struct PackListArgs {
+    const float* x[PACK_SRCS];
+    uint4* out[PACK_SRCS];
+    long long cols[PACK_SRCS], ld[PACK_SRCS];
+    int cb_start[PACK_SRCS + 1];            // first column block of source i in grid.x (unused sources: the total)
+    int aligned[PACK_SRCS];
+    long long krows, KB;
+};
+
+template <bool BF16>
+__global__ __launch_bounds__(256) void pack_planes_t4_kernel(const PackListArgs L) {
+    const int cb = blockIdx.x;
+    const int i = (cb >= L.cb_start[1] ? 1 : 0) + (cb >= L.cb_start[2] ? 1 : 0);
+    pack_planes_t4_block<BF16>(L.x[i], L.krows, L.cols[i], L.ld[i], 1.f, L.out[i], L.KB, 0, blockIdx.y, cb - L.cb_start[i], L.aligned[i] != 0);
 }
 
 // Source x[r][k] (row stride ld, the reduction axis k contiguous) -> planes of the operand with rows r.  Workgroup: one
@@ -885,7 +1045,9 @@ static void launch_big_inst(const BigArgs& G0, hipStream_t st) {
 // against 148 for the 128 x 128 slabs; x 32192: 40 tiles x 6, 448 against 531 = 0.50 of the 16-bit peak / 3).
 struct BigPick { int tile; int splits; };       // tile -1: the 128 x 128 kernel
 
-static BigPick pick_big(int32_t m, int32_t n, int KB, int max_splits) {
+// (`rows` / `cols`: the products of the call - one, or the blocks of a grouped call, whose tiles and slab traffic add up;
+//  always_slabs: every k-range count leaves slabs and runs the reduction pass, S = 1 included - the grouped call)
+static BigPick pick_big(const int* rows, const int* cols, int nblocks, int KB, int max_splits, bool always_slabs = false) {
     struct Cand { int mt, nt; double eff; };
     static const Cand cands[] = {{8, 5, 1.0}, {8, 4, 1.0}, {8, 3, 0.92}, {4, 5, 0.86}, {4, 4, 0.85}};
     const int cus = cu_count();
@@ -894,12 +1056,15 @@ static BigPick pick_big(int32_t m, int32_t n, int KB, int max_splits) {
     double best_cost = 1e300;
     const int smax = std::max(1, std::min(max_splits, KB / 4));
     const int g_tile_override = tile_override();
+    double elems = 0.0;
+    for (int b = 0; b < nblocks; ++b) elems += (double)rows[b] * cols[b];
     for (int i = -1; i < 5; ++i) {
         if (g_tile_override >= 0 && g_tile_override != (i < 0 ? 5 : i)) continue;
-        const double area = i < 0 ? 128.0 * 128 : 32.0 * cands[i].mt * 64.0 * cands[i].nt;
+        const int tr = i < 0 ? 128 : 32 * cands[i].mt, tc = i < 0 ? 128 : 64 * cands[i].nt;
+        const double area = (double)tr * tc;
         const double eff = i < 0 ? 0.79 : cands[i].eff;
-        const long long tiles = i < 0 ? (long long)((m + 127) / 128) * ((n + 127) / 128)
-                                      : (long long)((m + 32 * cands[i].mt - 1) / (32 * cands[i].mt)) * ((n + 64 * cands[i].nt - 1) / (64 * cands[i].nt));
+        long long tiles = 0;
+        for (int b = 0; b < nblocks; ++b) tiles += (long long)((rows[b] + tr - 1) / tr) * ((cols[b] + tc - 1) / tc);
         const int slots = i < 0 ? 2 * cus : cus;                 // 128 x 128: two workgroups per CU, each at half the rate
         const double rate = i < 0 ? 2.0 : 1.0;
         for (int S = 1; S <= smax; ++S) {
@@ -907,9 +1072,9 @@ static BigPick pick_big(int32_t m, int32_t n, int KB, int max_splits) {
             if ((KB + per - 1) / per != S) continue;             // this S does not exist (ranges are whole k blocks)
             const long long rounds = (tiles * S + slots - 1) / slots;
             // (calls without split K keep round 3's model - rounds x area / efficiency -, which its measurements were fitted with)
-            double cost = max_splits <= 1 ? (double)rounds * rate * area / eff * KB * unit
-                                          : (double)rounds * rate * (per * area * unit / eff + 10.0 * area * unit);
-            if (S > 1) cost += (double)(S + 2) * m * n * 4.0 / 4.0e6 + 8.0;
+            double cost = (max_splits <= 1 && !always_slabs) ? (double)rounds * rate * area / eff * KB * unit
+                                                             : (double)rounds * rate * (per * area * unit / eff + 10.0 * area * unit);
+            if (S > 1 || always_slabs) cost += (double)(S + 2) * elems * 4.0 / 4.0e6 + 8.0;
             if (cost < best_cost) {
                 best_cost = cost;
                 best = BigPick{i, S};
@@ -917,6 +1082,10 @@ static BigPick pick_big(int32_t m, int32_t n, int KB, int max_splits) {
         }
     }
     return best;
+}
+
+static BigPick pick_big(int32_t m, int32_t n, int KB, int max_splits) {
+    return pick_big(&m, &n, 1, KB, max_splits);
 }
 
 // splits > 1: `splits` k ranges of `per` k blocks, partial products into `slabs` (the caller runs planes_reduce_kernel behind the launch)
@@ -1091,6 +1260,185 @@ int ptmi_gemm_planes_bf16_two(const uint16_t* a, const uint16_t* b, float* c, fl
     PTMI_RETURN_IF((reinterpret_cast<uintptr_t>(c) ^ reinterpret_cast<uintptr_t>(c2)) & 15, PTMI_E_INVALID);       // one alignment class
     return gemm_planes_impl(true, products == 1, a, nullptr, b, nullptr, nullptr, c, ldc, m, n, k, accumulate, split_k, workspace, stream,
                             c2, m_split);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- grouped call
+int ptmi_pack_planes_t_bf16_list(const float* const* x, const int64_t* cols, const int64_t* ld, uint16_t* const* out, int32_t sources,
+                                 int64_t k_rows, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!x || !cols || !ld || !out || sources < 1 || sources > PACK_SRCS || k_rows < 1, PTMI_E_INVALID);
+    PackListArgs L{};
+    L.krows = k_rows;
+    L.KB = (k_rows + 31) / 32;
+    PTMI_RETURN_IF(L.KB > 65535, PTMI_E_UNSUPPORTED);
+    long long cb = 0;
+    for (int i = 0; i < PACK_SRCS; ++i) {
+        L.cb_start[i] = (int)cb;
+        if (i >= sources) continue;
+        PTMI_RETURN_IF(!x[i] || !out[i] || cols[i] < 1 || ld[i] < cols[i], PTMI_E_INVALID);
+        PTMI_RETURN_IF((reinterpret_cast<uintptr_t>(out[i]) & 15) != 0, PTMI_E_INVALID);
+        L.x[i] = x[i];
+        L.out[i] = reinterpret_cast<uint4*>(out[i]);
+        L.cols[i] = cols[i];
+        L.ld[i] = ld[i];
+        L.aligned[i] = (ld[i] % 4 == 0 && (reinterpret_cast<uintptr_t>(x[i]) & 15) == 0) ? 1 : 0;
+        cb += (cols[i] + 63) / 64;
+        PTMI_RETURN_IF(cb > (1 << 30), PTMI_E_UNSUPPORTED);
+    }
+    L.cb_start[PACK_SRCS] = (int)cb;
+    hipLaunchKernelGGL(pack_planes_t4_kernel<true>, dim3((unsigned)cb, (unsigned)L.KB), dim3(256), 0, static_cast<hipStream_t>(stream), L);
+    return launch_status();
+}
+
+}  // extern "C"
+
+// the blocks of a grouped call that are not skipped, part-major, and their slab layout for `splits` k ranges
+namespace {
+struct GroupPlan {
+    int nblocks = 0;
+    int part[GROUP_BLOCKS], seg[GROUP_BLOCKS], rows[GROUP_BLOCKS], cols[GROUP_BLOCKS];
+    long long elems = 0;            // output elements of all blocks
+    long long slab_elems = 0;       // one slab of every block (each rounded up to 4 floats)
+};
+
+bool group_plan(GroupPlan& P, int32_t m, int32_t m_split, const int32_t* n, int32_t segments, float* const* c) {
+    if (!n || !c || segments < 1 || segments > GROUP_SEGS || m < 2 || m_split < 1 || m_split >= m) return false;
+    for (int p = 0; p < 2; ++p)
+        for (int s = 0; s < segments; ++s) {
+            if (n[s] < 1) return false;
+            if (!c[p * segments + s]) continue;
+            const int b = P.nblocks++;
+            P.part[b] = p;
+            P.seg[b] = s;
+            P.rows[b] = p ? m - m_split : m_split;
+            P.cols[b] = n[s];
+            P.elems += (long long)P.rows[b] * n[s];
+            P.slab_elems += ((long long)P.rows[b] * n[s] + 3) / 4 * 4;
+        }
+    return P.nblocks > 0;
+}
+
+// tile (0..4, or -1: the big-tile path is not possible) and k ranges of a grouped call: a function of the shapes alone
+BigPick group_choice(const GroupPlan& P, int32_t m, int32_t m_split, const int32_t* n, int32_t segments, int KB, int32_t split_k) {
+    int splits = std::max(1, std::min<int>(split_k, KB));
+    int per = (KB + splits - 1) / splits;
+    splits = (KB + per - 1) / per;
+    BigPick pk = pick_big(P.rows, P.cols, P.nblocks, KB, splits, true);          // the plain calls' model over the items of ALL blocks
+    if (tile_override() >= 0) pk.splits = splits;           // a pinned tile takes split_k as it is
+    if (m_split % 16 != 0) pk.tile = -1;
+    if ((long long)((m + 15) / 16) * KB * 2048 >= (1ll << 31)) pk.tile = -1;
+    for (int s = 0; s < segments; ++s)
+        if ((long long)((n[s] + 15) / 16) * KB * 2048 >= (1ll << 31)) pk.tile = -1;
+    return pk;
+}
+
+template <int MT, int NT>
+void launch_group_inst(GroupBigArgs& G, const GroupPlan& P, bool one, hipStream_t st) {
+    int t = 0;
+    for (int b = 0; b < GROUP_BLOCKS; ++b) {
+        G.T.tile_start[b] = b < P.nblocks ? t : 0x7fffffff;
+        if (b >= P.nblocks) continue;
+        G.T.tiles_m[b] = (P.rows[b] + 32 * MT - 1) / (32 * MT);
+        G.T.tiles_n[b] = (P.cols[b] + 64 * NT - 1) / (64 * NT);
+        t += G.T.tiles_m[b] * G.T.tiles_n[b];
+    }
+    G.T.tile_start[GROUP_BLOCKS] = 0x7fffffff;
+    G.T.total_tiles = t;
+    const int T = t * G.splits;
+    const int grid = std::min((T + 7) / 8 * 8, cu_count() / 8 * 8);
+    if (one)
+        hipLaunchKernelGGL((gemm_planes_big_kernel<true, MT, NT, true, false, GroupBigArgs>), dim3((unsigned)grid), dim3(512), 0, st, G);
+    else
+        hipLaunchKernelGGL((gemm_planes_big_kernel<true, MT, NT, false, false, GroupBigArgs>), dim3((unsigned)grid), dim3(512), 0, st, G);
+}
+}  // namespace
+
+extern "C" {
+
+int64_t ptmi_gemm_planes_group_workspace_elems(int32_t m, int32_t m_split, const int32_t* n, int32_t segments, float* const* c, int32_t k,
+                                               int32_t split_k) {
+    GroupPlan P;
+    if (k < 1 || !group_plan(P, m, m_split, n, segments, c)) return 0;
+    const int KB = (k + 31) / 32;
+    return (int64_t)std::max(1, std::min<int>(split_k, KB)) * P.slab_elems;
+}
+
+int32_t ptmi_gemm_planes_group_plan(int32_t m, int32_t m_split, const int32_t* n, int32_t segments, float* const* c, int32_t k,
+                                    int32_t split_k) {
+    GroupPlan P;
+    if (k < 1 || !group_plan(P, m, m_split, n, segments, c)) return -1;
+    const BigPick pk = group_choice(P, m, m_split, n, segments, (k + 31) / 32, split_k);
+    return (pk.tile < 0 ? 5 : pk.tile) * 100 + pk.splits;
+}
+
+int ptmi_gemm_planes_bf16_group(const uint16_t* a, int32_t m, int32_t m_split, const uint16_t* const* b, const int32_t* n, int32_t segments,
+                                float* const* c, const int64_t* ldc, int32_t k, int32_t accumulate, int32_t split_k, int32_t products,
+                                float* workspace, ptmi_stream_t stream) {
+    PTMI_RETURN_IF((products != 3 && products != 1) || !a || !b || !ldc || !workspace || k < 1 || split_k < 1, PTMI_E_INVALID);
+    GroupPlan P;
+    PTMI_RETURN_IF(!group_plan(P, m, m_split, n, segments, c), PTMI_E_INVALID);
+    PTMI_RETURN_IF((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(workspace)) & 15, PTMI_E_INVALID);
+    for (int q = 0; q < P.nblocks; ++q) {
+        const int s = P.seg[q];
+        PTMI_RETURN_IF(!b[s] || (reinterpret_cast<uintptr_t>(b[s]) & 15) != 0 || ldc[P.part[q] * segments + s] < n[s], PTMI_E_INVALID);
+    }
+    const int KB = (k + 31) / 32;
+    const BigPick pk = group_choice(P, m, m_split, n, segments, KB, split_k);
+    if (pk.tile < 0) return PTMI_E_UNSUPPORTED;         // the caller falls back to separate calls (no other route is taken here)
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GroupBigArgs G{};
+    G.A = reinterpret_cast<const uint4*>(a);
+    G.M = m;
+    G.KB = KB;
+    G.band = 4;
+    G.a_bytes = (unsigned)((long long)((m + 15) / 16) * KB * 2048);
+    G.splits = pk.splits;
+    G.kb_per_split = (KB + pk.splits - 1) / pk.splits;
+    G.slabs = workspace;
+    G.T.part_rt0[0] = 0;
+    G.T.part_rts[0] = m_split / 16;
+    G.T.part_rt0[1] = m_split / 16;
+    G.T.part_rts[1] = (m - m_split + 15) / 16;
+    for (int s = 0; s < segments; ++s) {
+        G.T.B[s] = reinterpret_cast<const uint4*>(b[s]);
+        G.T.rtb[s] = (n[s] + 15) / 16;
+        G.T.b_bytes[s] = (unsigned)((long long)G.T.rtb[s] * KB * 2048);
+    }
+    ReduceGroupArgs R{};
+    R.ws = workspace;
+    R.splits = pk.splits;
+    R.nblocks = P.nblocks;
+    R.accumulate = accumulate ? 1 : 0;
+    long long off = 0, start = 0;
+    for (int q = 0; q < P.nblocks; ++q) {
+        const long long e = (long long)P.rows[q] * P.cols[q], stride = (e + 3) / 4 * 4;
+        G.T.part[q] = P.part[q];
+        G.T.seg[q] = P.seg[q];
+        G.T.rows[q] = P.rows[q];
+        G.T.cols[q] = P.cols[q];
+        G.T.slab_off[q] = R.slab_off[q] = off;
+        G.T.slab_stride[q] = R.slab_stride[q] = stride;
+        R.start[q] = start;
+        R.C[q] = c[P.part[q] * segments + P.seg[q]];
+        R.ldc[q] = ldc[P.part[q] * segments + P.seg[q]];
+        R.cols[q] = P.cols[q];
+        R.vec[q] = (P.cols[q] % 4 == 0 && R.ldc[q] % 4 == 0 && (reinterpret_cast<uintptr_t>(R.C[q]) & 15) == 0) ? 1 : 0;
+        off += stride * pk.splits;
+        start += R.vec[q] ? e / 4 : e;
+    }
+    for (int q = P.nblocks; q <= GROUP_BLOCKS; ++q) R.start[q] = start;
+    const bool one = products == 1;
+    switch (pk.tile) {
+        case 0: launch_group_inst<8, 5>(G, P, one, st); break;
+        case 1: launch_group_inst<8, 4>(G, P, one, st); break;
+        case 2: launch_group_inst<8, 3>(G, P, one, st); break;
+        case 3: launch_group_inst<4, 5>(G, P, one, st); break;
+        default: launch_group_inst<4, 4>(G, P, one, st); break;
+    }
+    int rc = launch_status();
+    if (rc != PTMI_OK) return rc;
+    const unsigned rgrid = (unsigned)std::min<long long>((start + 255) / 256, 4096);
+    hipLaunchKernelGGL(planes_reduce_kernel, dim3(rgrid), dim3(256), 0, st, R);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ speed (fp32 MFMA runs at 1/16 of the fp16 rate on this part).
 gradients the backward recurrence hands on), fp32 accumulation: BASELINE's "bf16" run of the model, reduced precision, reported
 as a delta, never the default.
 """
+import ctypes
 import os
 import threading
 import weakref
@@ -390,6 +391,16 @@ def auto_split_k(M, N, K):
     if tiles >= 384:
         return 1
     return max(1, min(12, K // 256))
+
+
+def group_plan(M, m_split, ns, blocks, K, split_k):
+    """``100 * tile + k ranges`` of the ``torch.ops.ptmi.gemm_planes_bf16_group_`` call with these shapes (``ptmi_gemm_planes_group_plan``:
+    host arithmetic, a function of the shapes alone); tile 5: the call would be refused and its caller issues separate calls."""
+    S = len(ns)
+    c = (ctypes.c_void_p * (2 * S))()
+    for blk in blocks:
+        c[blk] = 1              # (only whether a block is there is read)
+    return int(_lib.load().ptmi_gemm_planes_group_plan(M, m_split, (ctypes.c_int32 * S)(*[int(v) for v in ns]), S, c, K, split_k))
 
 
 #: weight-gradient GEMMs that run BESIDE a persistent recurrence: up to this many reduction rows on the 128 x 128 kernel, whose

@@ -18,6 +18,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                                               (torch.nn.LSTM in pit/model.py:60-66,97)
     torch.ops.ptmi.absmax                          ptmi_absmax                (operand scale of the dense layers' fp32 operands)
     torch.ops.ptmi.pack_planes_t / _n, torch.ops.ptmi.gemm_planes_   ptmi_pack_planes_t / _n, ptmi_gemm_planes   (nn.LSTM input projections, nn.Linear, all their gradients)
+    torch.ops.ptmi.pack_planes_bf16_list, torch.ops.ptmi.gemm_planes_bf16_group_   ptmi_pack_planes_t_bf16_list, ptmi_gemm_planes_bf16_group
+                                                                              (one BLSTM layer's four weight gradients, one launch)
     torch.ops.ptmi.lstm_weight_prep                ptmi_lstm_weight_prep      (the nn.LSTM parameters' operand forms, once per optimizer step)
     torch.ops.ptmi.grad_norm, torch.ops.ptmi.adam_flat_  ptmi_grad_norm, ptmi_adam_flat (train/optimizer.py:27-42, trainer.py:512-532)
     torch.ops.ptmi.tas_analysis / tas_synthesis / tas_masked_decode_backward / tas_wgrad   ptmi_tas_*
@@ -820,6 +822,56 @@ def gemm_planes_bf16_two_(out, out2, a, a_offset, b, M, N, K, accumulate, split_
     _lib.check(_lib.timed(f'gemm_planes_bf16:{M}x{N}x{K}:{split_k}', lib.ptmi_gemm_planes_bf16_two, a.data_ptr() + a_offset, b.data_ptr(),
                           out.data_ptr(), out2.data_ptr(), out.shape[0], max(out.stride(0), N), M, N, K, int(accumulate), split_k,
                           _products(), _lib.ptr(ws), _lib.stream(out.device)), 'ptmi_gemm_planes_bf16_two')
+
+
+@_register('pack_planes_bf16_list(Tensor[] xs) -> Tensor[]')
+def pack_planes_bf16_list(xs):
+    """Every ``x [k, c_i]`` of up to three sources with one ``k`` -> bf16 (hi, lo) planes of the ``c_i x k`` operand, ONE launch
+    (``ptmi_pack_planes_t_bf16_list``): bit for bit ``pack_planes_bf16(x, True)`` of each."""
+    lib = _lib.load()
+    n, k = len(xs), xs[0].shape[0]
+    assert 1 <= n <= 3 and all(x.dim() == 2 and x.shape[0] == k and x.dtype == torch.float32 and (x.stride(1) == 1 or x.shape[1] == 1)
+                               for x in xs), [tuple(x.shape) for x in xs]
+    outs = [torch.empty(int(lib.ptmi_planes_elems(x.shape[1], k)), dtype=torch.bfloat16, device=x.device) for x in xs]
+    src = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    cols = (ctypes.c_int64 * n)(*[x.shape[1] for x in xs])
+    ld = (ctypes.c_int64 * n)(*[_ld(x) for x in xs])
+    _lib.check(_lib.timed(f'pack_planes_bf16_list:{k}x{sum(x.shape[1] for x in xs)}', lib.ptmi_pack_planes_t_bf16_list, src, cols, ld, dst, n,
+                          k, _lib.stream(xs[0].device)), 'ptmi_pack_planes_t_bf16_list')
+    return outs
+
+
+@_register('gemm_planes_bf16_group_(Tensor(a!)[] outs, int[] blocks, Tensor a, int a_offset, int M, int m_split, Tensor[] bs, int[] ns, '
+           'int K, bool accumulate, int split_k) -> bool')
+def gemm_planes_bf16_group_(outs, blocks, a, a_offset, M, m_split, bs, ns, K, accumulate, split_k):
+    """The products of the blocks ``(part, segment)`` = ``divmod(blocks[i], len(bs))`` of ``A`` (two parts: rows below / from
+    ``m_split``) and the B segments ``bs`` (planes of ``ns[s] x K``), ``outs[i] (+)= A_part B_s^T``, in ONE launch and one slab
+    reduction (``ptmi_gemm_planes_bf16_group``); blocks not listed are skipped.  ``a`` / ``a_offset`` as in ``gemm_planes_bf16_``.
+    ``False`` - nothing launched - where the big-tile path is not possible: the caller issues separate calls."""
+    lib = _lib.load()
+    S = len(bs)
+    assert len(outs) == len(blocks) and len(ns) == S and len(set(blocks)) == len(blocks), (len(outs), blocks, ns)
+    c = (ctypes.c_void_p * (2 * S))()
+    ldc = (ctypes.c_int64 * (2 * S))()
+    for o, blk in zip(outs, blocks):
+        p, s = divmod(int(blk), S)
+        assert p in (0, 1) and o.dtype == torch.float32 and o.shape == ((M - m_split) if p else m_split, ns[s]) and o.stride(1) == 1, \
+            (blk, o.shape, o.stride())
+        c[blk] = o.data_ptr()
+        ldc[blk] = max(o.stride(0), ns[s])
+    n = (ctypes.c_int32 * S)(*[int(v) for v in ns])
+    b = (ctypes.c_void_p * S)(*[t.data_ptr() for t in bs])
+    if int(lib.ptmi_gemm_planes_group_plan(M, m_split, n, S, c, K, split_k)) // 100 == 5:
+        return False
+    ws = torch.empty(int(lib.ptmi_gemm_planes_group_workspace_elems(M, m_split, n, S, c, K, split_k)), dtype=torch.float32, device=a.device)
+    shape = f'{M}/{m_split}x{"+".join(str(int(v)) for v in ns)}x{K}'
+    rc = _lib.timed(f'gemm_group_bf16:{shape}:{split_k}', lib.ptmi_gemm_planes_bf16_group, a.data_ptr() + a_offset, M, m_split, b, n, S, c,
+                    ldc, K, int(accumulate), split_k, _products(), ws.data_ptr(), _lib.stream(a.device))
+    if rc == -2:            # PTMI_E_UNSUPPORTED
+        return False
+    _lib.check(rc, 'ptmi_gemm_planes_bf16_group')
+    return True
 
 
 # ------------------------------------------------------------------------------------------------ unit norm

@@ -302,6 +302,12 @@ def _input_grad(ctx, lib, plan, dg, flags, amax_dg, amax_kernel, w_ih, ndir, H):
     return _gemm.mm(dg, w_ih, amax_x=amax_dg, amax_y=gm[1])
 
 
+#: a BLSTM layer's four weight gradients (both directions' dW_ih and dW_hh) over the recurrence's bf16 planes of dgates^T as ONE pack
+#: launch (x, h_prev forward, h_prev reverse) and ONE grouped GEMM launch with one slab reduction (``ptmi_gemm_planes_bf16_group``)
+#: instead of the fused dW_ih call and the two dW_hh calls with a pack and a reduction each.  Off: exactly those calls (tests, A/B runs).
+GROUP_WGRAD = True
+
+
 class _WgradJob:
     """The in-place weight gradients of one layer's backward pass: :meth:`rows` accumulates dW_ih / dW_hh over row ranges (as
     often as the recurrence is cut), :meth:`accumulate` the rest and the biases - at once or parked on ``ops.wgrad``.  Owns what
@@ -312,17 +318,31 @@ class _WgradJob:
         self.lib, self.plan, self.meta, self.gm, self.params, self.oc = lib, plan, ctx.meta, ctx.gemm, ctx.params, ctx.oc
         self.x, self.hy, self.h0, self.ext, self.ndir, self.H, self.G = x, hy, h0, ctx.ext, ndir, H, 4 * H
         self.first_layer = not ctx.needs_input_grad[0]
-        self.operands, self.xplanes, self.dgplanes = None, {}, {}
+        self.operands, self.xplanes, self.dgplanes, self.group = None, {}, {}, {}
 
     def rows(self, dg, ranges, amax_dg, both_queues=False, dg_t=None):
         """dW_ih, dW_hh of every direction d over the rows ranges[d] = (r0, r1) of the packed batch, on `side`
         (both_queues: all but the forward direction's dW_hh on the main stream - the step's tail, see `share_operands`).
-        dg_t: the kernel's bf16 planes of dgates^T for exactly these row ranges (then `dg` is None)."""
+        dg_t: the kernel's bf16 planes of dgates^T for exactly these row ranges (then `dg` is None); with both directions over ONE row
+        range all four products go out as one grouped call (`GROUP_WGRAD`) on one queue: `main` for both_queues, else `side`."""
         lib, gm, params, x, h0, ndir, H, G = self.lib, self.gm, self.params, self.x, self.h0, self.ndir, self.H, self.G
         main, side, xplanes = self.plan.main, self.plan.side, self.xplanes
         # the first layer's weight gradients have the chip to themselves (the step's tail): big tiles; every other layer's run
         # beside the next recurrence: short ones on the kernel whose workgroups share CUs with the recurrence's
         split_of = _gemm.auto_split_k if self.first_layer else _gemm.co_resident_split_k
+        if self._grouped(dg_t, ranges):
+            # all four products reduce over the same packed rows and share operands (x: both dW_ih; each direction's dgates^T: its
+            # dW_ih and dW_hh): one pack launch, one GEMM launch over the tiles of all four, one slab reduction
+            r0, r1 = ranges[0]
+            with torch.cuda.stream(main if both_queues else side):
+                if self.operands is None:
+                    self.operands = _recurrent_operands(self.meta, dg, self.hy, self.ext, h0, ndir, H)
+                px, pf, pb = torch.ops.ptmi.pack_planes_bf16_list([x[r0:r1], self.operands[0][1][r0:r1], self.operands[1][1][r0:r1]])
+                ok = torch.ops.ptmi.gemm_planes_bf16_group_(
+                    [params[0][0].grad, params[0][1].grad, params[1][0].grad, params[1][1].grad], self.GROUP_BLOCKS, dg_t, 0, 2 * G, G,
+                    [px, pf, pb], [x.shape[1], H, H], r1 - r0, True, _gemm.auto_split_k(G, H, r1 - r0))
+                assert ok, 'ptmi_gemm_planes_bf16_group refused a call its plan had accepted'
+            return
         # both directions' dW_ih = [dgates_f | dgates_r]^T x share the operand x and the kernel's planes of dgates^T lie behind each
         # other: ONE launch with a two-part output (ptmi_gemm_planes_bf16_two) instead of two GEMMs + two slab reductions
         fused_ih = False
@@ -384,6 +404,23 @@ class _WgradJob:
                     p_wih.grad.addmm_(dgt, x[r0:r1])
                     p_whh.grad.addmm_(dgt, h_prev[r0:r1])
 
+    #: blocks (part * 3 + segment) of the grouped call: (dG_f, x), (dG_f, h_f), (dG_b, x), (dG_b, h_b)
+    GROUP_BLOCKS = [0, 1, 3, 5]
+
+    def _grouped(self, dg_t, ranges):
+        """Whether :meth:`rows` takes the grouped call for these ranges: the recurrence's planes of both directions over one row range,
+        and a shape the big-tile kernel runs (else: the separate calls).  Decided once per row range."""
+        if not (GROUP_WGRAD and dg_t is not None and self.ndir == 2 and ranges[0] == ranges[1] and ranges[0][1] > ranges[0][0]):
+            return False
+        key = ranges[0]
+        if key not in self.group:
+            grads = [ps[i].grad for ps in self.params for i in (0, 1)]
+            k = key[1] - key[0]
+            self.group[key] = all(g is not None and g.dim() == 2 and g.stride(1) == 1 and g.dtype == torch.float32 for g in grads) and \
+                _gemm.group_plan(2 * self.G, self.G, [self.x.shape[1], self.H, self.H], self.GROUP_BLOCKS, k,
+                                 _gemm.auto_split_k(self.G, self.H, k)) // 100 != 5
+        return self.group[key]
+
     def finish(self, dg, dg_t, todo, amax_dg, db_kernel):
         """The rest of the layer's weight gradients (rows ``todo``) and its bias gradients, enqueued here or - a captured step -
         behind the next lower layer's recurrence launch."""
@@ -397,13 +434,15 @@ class _WgradJob:
         self.both = both = (plan.use_side and ndir > 1 and gm is not None and _gemm.planes_enabled()
                             and self.first_layer and todo[0] == (0, self.meta.rows))
         if both:
+            # (one grouped launch: all of it on the main queue - nothing to share between the queues)
+            group = self._grouped(dg_t, todo)
             # earlier side-stream accumulations into the same .grad views
-            _wgrad.wait_done(plan.main, (params[0][0], params[1][0], params[1][1]))
+            _wgrad.wait_done(plan.main, (params[0][0], params[1][0], params[1][1]) + ((params[0][1],) if group else ()))
             self.operands = _recurrent_operands(self.meta, dg, self.hy, self.ext, self.h0, ndir, self.H)
             # shared between the queues: packed before they part
-            if dg_t is not None:
+            if dg_t is not None and not group:
                 self.xplanes[todo[0]] = torch.ops.ptmi.pack_planes_bf16(x, True)
-            else:
+            elif dg_t is None:
                 self.xplanes[todo[0]] = _gemm.pack_t(x, gm[0])
                 self.dgplanes[(0, todo[0])] = _gemm.pack_t(self.operands[0][0], amax_dg)
         # captured steps: enqueue behind the next lower layer's recurrence launch (ops.wgrad.defer); the side stream waits for the
@@ -444,8 +483,9 @@ class _WgradJob:
             _wgrad.mark_done([p for ps in params for p in ps[:2]], done)
         if both:
             main.wait_event(done)                          # the main queue is now behind both
-            for t in (self.dgplanes[(0, todo[0])][:1] if dg_t is None else (self.xplanes[todo[0]],)):
-                t.record_stream(side)
+            shared = self.dgplanes[(0, todo[0])][0] if dg_t is None else self.xplanes.get(todo[0])       # (grouped call: none)
+            if shared is not None:
+                shared.record_stream(side)
             if oc.grad_ready_hook is not None:
                 side.wait_stream(main)                     # whoever orders itself after `side` sees every gradient
         if use_side:
