@@ -620,6 +620,34 @@ int ptmi_orpit_flag_backward(const float* gflag, const float* gpre, const float*
                              float* dparams, float* dmask, float* dencoded, double* workspace, int64_t B, int32_t A, int64_t E, int32_t N,
                              int32_t K, int32_t k, int32_t weighted, ptmi_stream_t stream);
 
+/* ---- Mask-based MVDR beamforming --------------------------------------------------------------------
+ * What the mask estimators are trained for (padertorch/contrib/examples/speech_enhancement/mask_estimator/evaluate.py:110-137,
+ * contrib/jensheit/evaluation.py:14-45; there through pb_bss / paderbox on the host).  Y and X [B, C, T, F] complex64 as interleaved
+ * floats (F contiguous), 1 <= C <= 8, B <= 65535; frames [B] int32 or NULL: frames t >= frames[b] are never read, contribute nothing
+ * and come out as zero.  fp32 data and products, every sum fp64, no atomics, workspace partials added in a fixed order
+ * (bit-reproducible); no allocation, no synchronisation (capturable).
+ *
+ * ptmi_bf_psd   : psd [M, B, F, C, C] complex128 (interleaved doubles) for the M (1 or 2) masks from ONE pass over Y:
+ *   psd[k][b,f,d,e] = sum_t m_k[b,t,f] Y[b,d,t,f] conj(Y[b,e,t,f]) / max(sum_t m_k[b,t,f], 1e-10) (normalize == 0: no division);
+ *   both triangles are written from the one sum of the upper one (exactly Hermitian, real diagonal).
+ *   mask_mode 2: mask_k [B, C, T, F] fp32 and m_k is its median over the channels (even C: the mean of the two middle values);
+ *   mask_mode 1: mask_k [B, T, F] is m_k; mask_mode 0: no mask, m = 1 (M must be 1, the masks NULL): the covariance over the valid
+ *   frames.  workspace: ptmi_bf_psd_workspace_elems(B, C, T, F, M) float64.
+ * ptmi_bf_souden: psd_target, psd_noise [B, F, C, C] complex128 -> X = psd_noise^-1 psd_target by Gaussian elimination with partial
+ *   pivoting (a pivot that is exactly zero leaves the unknowns of its column zero: an all-zero psd_noise gives w = 0),
+ *   w_all [B, F, C, C] complex64 = X / max(Re trace X, DBL_MIN) and w [B, F, C] = w_all[:, :, :, ref].  ref_channel >= 0: that column
+ *   for every example; ref_channel < 0: per example argmax_r sum_f Re(w_r^H psd_target w_r) / max(sum_f Re(w_r^H psd_noise w_r), DBL_MIN)
+ *   with w_r = w_all[:, :, :, r] before rounding, the first maximum; numden [B, F, C, 2] float64 holds the summands (may be NULL for
+ *   ref_channel >= 0).  ref_out [B] int32: the column taken.  Rank-deficient, non-zero psd_noise is not guarded.
+ * ptmi_bf_apply : Z[b,t,f] = sum_c conj(w[b,f,c]) X[b,c,t,f], Z [B, T, F] complex64; T <= 32 * 65535. */
+int64_t ptmi_bf_psd_workspace_elems(int64_t B, int32_t C, int64_t T, int64_t F, int32_t M);
+int ptmi_bf_psd(const float* Y, const float* mask0, const float* mask1, const int32_t* frames, int64_t B, int32_t C, int64_t T, int64_t F,
+                int32_t M, int32_t mask_mode, int32_t normalize, double* workspace, double* psd, ptmi_stream_t stream);
+int ptmi_bf_souden(const double* psd_target, const double* psd_noise, int64_t B, int64_t F, int32_t C, int32_t ref_channel, float* w_all,
+                   double* numden, float* w, int32_t* ref_out, ptmi_stream_t stream);
+int ptmi_bf_apply(const float* w, const float* X, const int32_t* frames, int64_t B, int32_t C, int64_t T, int64_t F, float* Z,
+                  ptmi_stream_t stream);
+
 /* ---- Dense layers: fp32 GEMM on the 16-bit matrix cores (split operands) --------------------------
  * Replaces the library GEMMs behind torch.nn.LSTM's input projections and torch.nn.Linear in
  * padertorch/contrib/examples/source_separation/pit/model.py:60-66,97-104 and contrib/tcl/dc.py:32-40,61-66

@@ -56,6 +56,53 @@ class SimpleMaskEstimator(base.Model):
             review['images'] = self.add_images(batch, output)
         return review
 
+    def enhance(self, y, num_samples=None, stft=None, ref_channel=None):
+        """What the masks are trained for (the reference's ``evaluate.py:110-137``, there on the host): mixtures ``y [B, C, N]`` (or a
+        list of ``[C, N_b]``) -> ``dict(masked=[...], beamformed=[...])``, per example one waveform ``[N_b]`` each: the first
+        channel times its speech mask, and the mask-based Souden MVDR beamformer (``ops.mask_beamforming``: channel medians of both
+        masks, reference channel chosen on the device unless ``ref_channel`` names one).  HIP STFT -> the model on the channels'
+        magnitudes -> beamformer -> HIP iSTFT, cut to ``N_b``; nothing leaves the device in between.
+
+        ``num_samples``: host integers, the valid samples of the rows of a padded ``[B, C, N]``.  The model's normalisation takes no
+        lengths, so examples of ONE length go through as one batch and examples of differing lengths one by one, as in the
+        reference's evaluation.  ``stft``: an ``ops.STFT`` with ``num_features`` bins (default ``STFT(1024, 256)``).  Runs in eval
+        mode under ``torch.no_grad()``."""
+        from .....ops import STFT
+        stft = STFT(1024, 256) if stft is None else stft
+        if stft.size // 2 + 1 != self.num_features or stft.complex_representation != 'complex':
+            raise ValueError(f'enhance: a complex STFT with {self.num_features} bins, got size {stft.size} '
+                             f'({stft.complex_representation})')
+        examples = list(y.unbind(0)) if torch.is_tensor(y) else list(y)
+        if not examples or any(e.dim() != 2 for e in examples):
+            raise ValueError('enhance: mixtures [B, C, N] or a list of [C, N_b]')
+        lengths = [e.shape[-1] for e in examples] if num_samples is None else [int(n) for n in num_samples]
+        if len(lengths) != len(examples) or any(not 0 < n <= e.shape[-1] for n, e in zip(lengths, examples)):
+            raise ValueError(f'enhance: one length in (0, N_b] per example, got {lengths}')
+        training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                if len(set(lengths)) == 1 and len({e.shape[0] for e in examples}) == 1:
+                    batch = y if torch.is_tensor(y) else torch.stack(examples)
+                    masked, beamformed = self._enhance_batch(batch[..., :lengths[0]], stft, ref_channel)
+                    return dict(masked=list(masked.unbind(0)), beamformed=list(beamformed.unbind(0)))
+                pairs = [self._enhance_batch(e[None, :, :n], stft, ref_channel) for e, n in zip(examples, lengths)]
+                return dict(masked=[m[0] for m, _ in pairs], beamformed=[b[0] for _, b in pairs])
+        finally:
+            self.train(training)
+
+    def _enhance_batch(self, y, stft, ref_channel):
+        """``y [B, C, N]`` -> ``(masked [B, N], beamformed [B, N])``."""
+        from .....ops import mask_beamforming
+        Y = stft(y)                                                       # [B, C, T, F] complex64
+        B, C, T, F = Y.shape
+        out = self(dict(observation_abs=Y.abs().reshape(B * C, T, F)))    # the channels are the model's batch
+        speech = out['speech_mask_prediction'].reshape(B, C, T, F)
+        noise = out['noise_mask_prediction'].reshape(B, C, T, F)
+        spectra = torch.stack([speech[:, 0] * Y[:, 0], mask_beamforming(Y, speech, noise, ref_channel=ref_channel)])
+        masked, beamformed = stft.inverse(spectra)[..., :y.shape[-1]]
+        return masked, beamformed
+
     @staticmethod
     def add_images(batch, output):
         """First example of the (batch-first) tensors as tensorboard images (reference ``:74-90``); the target masks

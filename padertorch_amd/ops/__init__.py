@@ -22,3 +22,6 @@ from .tcn import depthwise_prelu, channel_norm  # noqa: F401
 from . import tasnet  # noqa: F401
 from . import orpit  # noqa: F401
 from . import dprnn  # noqa: F401
+from . import beamforming  # noqa: F401
+from .beamforming import (get_power_spectral_density_matrix, get_mvdr_vector_souden, apply_beamforming_vector,  # noqa: F401
+                          mask_beamforming)

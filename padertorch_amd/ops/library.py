@@ -31,6 +31,7 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.orpit_flag_forward / _backward  ptmi_orpit_flag_*          (or_pit/model.py:187-218)
     torch.ops.ptmi.dprnn_tables / chunk_lstm_forward / chunk_lstm_backward / dprnn_colsum / dprnn_colsum_pair / dprnn_norm_residual_forward / _backward /
     torch.ops.ptmi.dprnn_segment / dprnn_overlap_add   ptmi_dprnn_*, ptmi_chunk_lstm_*   (modules/dual_path_rnn.py)
+    torch.ops.ptmi.bf_psd / bf_souden / bf_apply   ptmi_bf_*                  (mask_estimator/evaluate.py:110-137, jensheit/evaluation.py:14-45)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -569,6 +570,70 @@ def orpit_flag_backward(gflag, gpre, flag, stat, pre, w, additional, weight, mas
                           _lib.ptr(mask), _lib.ptr(encoded), dadd.data_ptr(), dparams.data_ptr(), _lib.ptr(dmask), _lib.ptr(denc),
                           ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev)), 'ptmi_orpit_flag_backward')
     return dadd, dparams, dmask, denc
+
+
+# ------------------------------------------------------------------------------------------------ beamforming (csrc/beamform.hip)
+def _bf_spectrum(x):
+    """``[B, C, T, F]`` complex64, contiguous -> its ``(B, C, T, F)``."""
+    assert x.dim() == 4 and x.dtype == torch.complex64 and x.is_contiguous(), (x.shape, x.stride(), x.dtype)
+    return x.shape
+
+
+def _bf_frames(frames, B):
+    assert frames is None or (frames.dtype == torch.int32 and frames.shape == (B,) and frames.is_contiguous()), \
+        (frames.dtype, frames.shape)
+    return _lib.ptr(frames)
+
+
+@_register('bf_psd(Tensor observation, Tensor? mask0, Tensor? mask1, Tensor? frames, bool normalize) -> Tensor')
+def bf_psd(observation, mask0, mask1, frames, normalize):
+    """``observation [B, C, T, F]`` complex64 and up to two masks (``[B, C, T, F]``: the channel median is taken in the kernel,
+    ``[B, T, F]``: as it is; none: the plain covariance) -> ``psd [M, B, F, C, C]`` complex128, one pass over the observation
+    (``ptmi_bf_psd``)."""
+    lib = _lib.load()
+    B, C, T, F = _bf_spectrum(observation)
+    masks = [m for m in (mask0, mask1) if m is not None]
+    assert mask0 is not None or mask1 is None
+    _f32c(*masks)
+    mode = 0 if not masks else masks[0].dim() - 2
+    assert all(tuple(m.shape) == ((B, C, T, F) if mode == 2 else (B, T, F)) for m in masks), ([m.shape for m in masks], observation.shape)
+    M = max(len(masks), 1)
+    dev = observation.device
+    psd = _doubles(M * B * F * C * C * 2, dev).view(M, B, F, C, C, 2)
+    ws = _doubles(lib.ptmi_bf_psd_workspace_elems(B, C, T, F, M), dev)
+    _lib.check(_lib.timed('bf_psd', lib.ptmi_bf_psd, observation.data_ptr(), _lib.ptr(mask0), _lib.ptr(mask1), _bf_frames(frames, B),
+                          B, C, T, F, M, mode, int(normalize), ws.data_ptr(), psd.data_ptr(), _lib.stream(dev)), 'ptmi_bf_psd')
+    return torch.view_as_complex(psd)
+
+
+@_register('bf_souden(Tensor target_psd, Tensor noise_psd, int ref_channel) -> (Tensor, Tensor, Tensor)')
+def bf_souden(target_psd, noise_psd, ref_channel):
+    """``[B, F, C, C]`` complex128 PSD matrices -> ``(w [B, F, C] complex64, w_all [B, F, C, C] complex64, ref [B] int32)``;
+    ``ref_channel < 0``: the reference channel is chosen on the device (``ptmi_bf_souden``)."""
+    for p in (target_psd, noise_psd):
+        assert p.dim() == 4 and p.dtype == torch.complex128 and p.is_contiguous() and p.shape == target_psd.shape, (p.shape, p.dtype)
+    B, F, C, _ = target_psd.shape
+    assert target_psd.shape[3] == C and ref_channel < C, (target_psd.shape, ref_channel)
+    dev = target_psd.device
+    w_all = torch.empty((B, F, C, C), dtype=torch.complex64, device=dev)
+    w = torch.empty((B, F, C), dtype=torch.complex64, device=dev)
+    ref = torch.empty(B, dtype=torch.int32, device=dev)
+    numden = _doubles(B * F * C * 2 if ref_channel < 0 else 0, dev)
+    _lib.check(_lib.timed('bf_souden', _lib.load().ptmi_bf_souden, target_psd.data_ptr(), noise_psd.data_ptr(), B, F, C,
+                          max(int(ref_channel), -1), w_all.data_ptr(), numden.data_ptr() if ref_channel < 0 else None, w.data_ptr(),
+                          ref.data_ptr(), _lib.stream(dev)), 'ptmi_bf_souden')
+    return w, w_all, ref
+
+
+@_register('bf_apply(Tensor vector, Tensor mix, Tensor? frames) -> Tensor')
+def bf_apply(vector, mix, frames):
+    """``vector [B, F, C]``, ``mix [B, C, T, F]`` complex64 -> ``[B, T, F]``: ``sum_c conj(vector) mix`` (``ptmi_bf_apply``)."""
+    B, C, T, F = _bf_spectrum(mix)
+    assert vector.shape == (B, F, C) and vector.dtype == torch.complex64 and vector.is_contiguous(), (vector.shape, vector.dtype)
+    out = torch.empty((B, T, F), dtype=torch.complex64, device=mix.device)
+    _lib.check(_lib.timed('bf_apply', _lib.load().ptmi_bf_apply, vector.data_ptr(), mix.data_ptr(), _bf_frames(frames, B), B, C, T, F,
+                          out.data_ptr(), _lib.stream(mix.device)), 'ptmi_bf_apply')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ dense layers
