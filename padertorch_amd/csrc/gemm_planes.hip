@@ -1004,7 +1004,8 @@ int64_t ptmi_gemm_planes_workspace_elems(int32_t m, int32_t n, int32_t k, int32_
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------------------------------------- big-tile dispatch
+// ---------------------------------------------------------------------------------------------------------------- planner and launch path
+#include <type_traits>
 // PTMI_GEMM_TILE=0..5 pins the workgroup tile of every call (5 = the 128 x 128 kernel) for the sweeps of scripts/ and the tile tests; read at
 // every call (the tests change it between calls), unset / -1: the cost model.  Not an entry point of the library.
 static int tile_override() {
@@ -1026,14 +1027,40 @@ static int cu_count() {
     return cus;
 }
 
-template <bool BF16, int MT, int NT, bool ONE, bool RELU = false>
-static void launch_big_inst(const BigArgs& G0, hipStream_t st) {
-    BigArgs G = G0;
-    G.tiles_m = (G.M + 32 * MT - 1) / (32 * MT);
-    G.tiles_n = (G.N + 64 * NT - 1) / (64 * NT);
-    const int T = G.tiles_m * G.tiles_n * G.splits;
-    const int grid = std::min((T + 7) / 8 * 8, cu_count() / 8 * 8);
-    hipLaunchKernelGGL((gemm_planes_big_kernel<BF16, MT, NT, ONE, RELU>), dim3((unsigned)grid), dim3(512), 0, st, G);
+// The instantiations of gemm_planes_big_kernel by tile index: workgroup tile (32 mt) x (64 nt), eff: the efficiency of the tile shape in
+// pick_big's cost model.  Index -1 (5 in a plan answer and in PTMI_GEMM_TILE): the 128 x 128 kernel.
+struct Tile { int mt, nt; double eff; };
+constexpr Tile TILES[] = {{8, 5, 1.0}, {8, 4, 1.0}, {8, 3, 0.92}, {4, 5, 0.86}, {4, 4, 0.85}};
+constexpr int NTILES = 5;
+
+// f(std::integral_constant<int, tile>) for the tile index 0..4 of a plan: f reads its (MT, NT) from TILES as constants
+template <int I = NTILES - 1, class F>
+static void with_tile(int tile, F&& f) {
+    if constexpr (I > 0)
+        if (tile != I) return with_tile<I - 1>(tile, f);
+    f(std::integral_constant<int, I>{});
+}
+
+// f(BF16, ONE, RELU) as std::bool_constants: the five variants either single-product kernel exists in (RELU: fp16, three products)
+template <class F>
+static void with_variant(bool bf16, bool one, bool relu, F&& f) {
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (relu) return f(no, no, yes);
+    if (bf16) return one ? f(yes, yes, no) : f(yes, no, no);
+    return one ? f(no, yes, no) : f(no, no, no);
+}
+
+// bytes of the planes of an operand with `rows` rows; the big-tile kernel forms piece offsets in 32-bit signed arithmetic, so planes
+// of PLANES_LIMIT bytes and more go to the 128 x 128 kernel (a grouped call with such planes is refused)
+constexpr long long PLANES_LIMIT = 1ll << 31;
+static long long planes_bytes(int rows, int KB) { return (long long)((rows + 15) / 16) * KB * 2048; }
+
+// the k-range count a split_k >= 1 stands for: at most KB, and one that exists (ranges are whole k blocks)
+static int whole_ranges(int split_k, int KB) {
+    const int splits = std::max(1, std::min(split_k, KB));
+    const int per = (KB + splits - 1) / splits;
+    return (KB + per - 1) / per;
 }
 
 // Picks the tile - and, for calls that allow split K, the number of k ranges - by a cost model fitted to scripts/mb/gemm_big.hip's
@@ -1046,23 +1073,21 @@ static void launch_big_inst(const BigArgs& G0, hipStream_t st) {
 struct BigPick { int tile; int splits; };       // tile -1: the 128 x 128 kernel
 
 // (`rows` / `cols`: the products of the call - one, or the blocks of a grouped call, whose tiles and slab traffic add up;
-//  always_slabs: every k-range count leaves slabs and runs the reduction pass, S = 1 included - the grouped call)
-static BigPick pick_big(const int* rows, const int* cols, int nblocks, int KB, int max_splits, bool always_slabs = false) {
-    struct Cand { int mt, nt; double eff; };
-    static const Cand cands[] = {{8, 5, 1.0}, {8, 4, 1.0}, {8, 3, 0.92}, {4, 5, 0.86}, {4, 4, 0.85}};
+//  always_slabs: every k-range count leaves slabs and runs the reduction pass, S = 1 included - the grouped call;
+//  pinned: tile_override() - only that tile is a candidate)
+static BigPick pick_big(const int* rows, const int* cols, int nblocks, int KB, int max_splits, bool always_slabs, int pinned) {
     const int cus = cu_count();
     const double unit = 3.1e-5;                  // us per (k block x output element) of a 256-row tile on one CU
     BigPick best{-1, 1};
     double best_cost = 1e300;
     const int smax = std::max(1, std::min(max_splits, KB / 4));
-    const int g_tile_override = tile_override();
     double elems = 0.0;
     for (int b = 0; b < nblocks; ++b) elems += (double)rows[b] * cols[b];
-    for (int i = -1; i < 5; ++i) {
-        if (g_tile_override >= 0 && g_tile_override != (i < 0 ? 5 : i)) continue;
-        const int tr = i < 0 ? 128 : 32 * cands[i].mt, tc = i < 0 ? 128 : 64 * cands[i].nt;
+    for (int i = -1; i < NTILES; ++i) {
+        if (pinned >= 0 && pinned != (i < 0 ? 5 : i)) continue;
+        const int tr = i < 0 ? 128 : 32 * TILES[i].mt, tc = i < 0 ? 128 : 64 * TILES[i].nt;
         const double area = (double)tr * tc;
-        const double eff = i < 0 ? 0.79 : cands[i].eff;
+        const double eff = i < 0 ? 0.79 : TILES[i].eff;
         long long tiles = 0;
         for (int b = 0; b < nblocks; ++b) tiles += (long long)((rows[b] + tr - 1) / tr) * ((cols[b] + tc - 1) / tc);
         const int slots = i < 0 ? 2 * cus : cus;                 // 128 x 128: two workgroups per CU, each at half the rate
@@ -1084,111 +1109,100 @@ static BigPick pick_big(const int* rows, const int* cols, int nblocks, int KB, i
     return best;
 }
 
-static BigPick pick_big(int32_t m, int32_t n, int KB, int max_splits) {
-    return pick_big(&m, &n, 1, KB, max_splits);
-}
+// What a single-product call runs - gemm_planes_impl launches it, ptmi_gemm_planes_plan encodes it: tile (0..4: TILES, -1: 128 x 128) and
+// `splits` k ranges of `kb_per_split` of the KB k blocks, a function of the shape alone, so a call is reproducible bit for bit.
+//   split_k > 0: the MOST k ranges the caller's workspace holds; how many are used, and on which tile, is the cost model's choice.
+//   split_k < 0: exactly -split_k ranges on the 128 x 128 kernel, whose workgroups (4 wavefronts, 64 KB of LDS) fit on a CU next to a
+//                persistent recurrence workgroup, where a big tile needs a whole CU.  A pinned tile takes |split_k| as it is.
+struct Plan { int tile, splits, kb_per_split, KB; };
 
-// splits > 1: `splits` k ranges of `per` k blocks, partial products into `slabs` (the caller runs planes_reduce_kernel behind the launch)
-static bool launch_big(int pick, bool bf16, bool one, const uint16_t* a, const uint32_t* amax_a, const uint16_t* b, const uint32_t* amax_b,
-                       const float* bias, float* c, int64_t ldc, int32_t m, int32_t n, int KB, int32_t accumulate, hipStream_t st,
-                       int splits = 1, int per = 0, float* slabs = nullptr, float* c2 = nullptr, int m_split = 0, int relu = 0,
-                       unsigned* amax_out = nullptr) {
-    const long long a_bytes = (long long)((m + 15) / 16) * KB * 2048, b_bytes = (long long)((n + 15) / 16) * KB * 2048;
-    if (pick < 0 || a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31)) return false;      // piece offsets are formed in 32-bit signed arithmetic
-    BigArgs G{reinterpret_cast<const uint4*>(a), reinterpret_cast<const uint4*>(b), c, amax_a, amax_b, bias, m, n, KB, (long long)ldc,
-              accumulate ? 1 : 0, 0, 0, 4, (unsigned)a_bytes, (unsigned)b_bytes};
-    G.splits = splits;
-    G.kb_per_split = per;
-    G.slabs = slabs;
-    G.C2 = c2;
-    G.m_split = m_split;
-    G.relu = splits > 1 ? 0 : relu;
-    G.amax_out = amax_out;
-#define PTMI_BIG_CASE(I, MT_, NT_)                                    \
-    case I:                                                           \
-        if (G.relu) launch_big_inst<false, MT_, NT_, false, true>(G, st);     \
-        else if (bf16 && one) launch_big_inst<true, MT_, NT_, true>(G, st);   \
-        else if (bf16) launch_big_inst<true, MT_, NT_, false>(G, st);         \
-        else if (one) launch_big_inst<false, MT_, NT_, true>(G, st);          \
-        else launch_big_inst<false, MT_, NT_, false>(G, st);                  \
-        break;
-    switch (pick) {
-        PTMI_BIG_CASE(0, 8, 5)
-        PTMI_BIG_CASE(1, 8, 4)
-        PTMI_BIG_CASE(2, 8, 3)
-        PTMI_BIG_CASE(3, 4, 5)
-        PTMI_BIG_CASE(4, 4, 4)
-    }
-#undef PTMI_BIG_CASE
-    return true;
-}
-
-static int gemm_planes_impl(bool bf16, bool one, const uint16_t* a, const uint32_t* amax_a, const uint16_t* b, const uint32_t* amax_b,
-                            const float* bias, float* c, int64_t ldc, int32_t m, int32_t n, int32_t k, int32_t accumulate,
-                            int32_t split_k, float* workspace, ptmi_stream_t stream, float* c2 = nullptr, int32_t m_split = 0, int relu = 0,
-                            unsigned* amax_out = nullptr) {
-    PTMI_RETURN_IF(!a || !b || !c || m < 1 || n < 1 || k < 1 || ldc < n, PTMI_E_INVALID);
-    PTMI_RETURN_IF(relu && (accumulate || c2 || bf16 || one), PTMI_E_INVALID);
-    PTMI_RETURN_IF(c2 && (m_split < 16 || m_split >= m || m_split % 16 != 0), PTMI_E_INVALID);
-    PTMI_RETURN_IF(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) != 0, PTMI_E_INVALID);
+static Plan plan_call(int m, int n, int k, int split_k) {
     const int KB = (k + 31) / 32;
-    // split_k = the most k ranges the caller's workspace holds; how many are used (and on which tile) is the cost model's choice - a
-    // function of the shape alone, so a call is reproducible bit for bit.  A pinned tile (PTMI_GEMM_TILE: tests, sweeps)
-    // takes split_k as it is.
-    // split_k < 0: exactly -split_k ranges on the 128 x 128 kernel - its workgroups (4 wavefronts, 64 KB of LDS) fit on a CU NEXT TO a
-    // persistent recurrence workgroup, a big tile needs a whole CU and only gets the ~100 the recurrence leaves free: what a caller
-    // asks for whose GEMM runs beside a recurrence and is short (measured in the B = 32 step: 7.15 against 7.18 ms with the big tiles)
     const bool co_resident = split_k < 0;
-    if (co_resident) split_k = -split_k;
-    int splits = std::max(1, std::min<int>(split_k, KB));
-    int per = (KB + splits - 1) / splits;
-    splits = (KB + per - 1) / per;
-    PTMI_RETURN_IF(splits > 1 && !workspace, PTMI_E_INVALID);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    static const bool big_split = !(getenv("PTMI_GEMM_BIG_SPLIT") && atoi(getenv("PTMI_GEMM_BIG_SPLIT")) == 0);
-    const int g_tile_override = tile_override();
-    BigPick pk = pick_big(m, n, KB, ((big_split && !co_resident) || g_tile_override >= 0) ? splits : 1);
-    if (g_tile_override >= 0) pk.splits = splits;
-    else if (co_resident || (!big_split && splits > 1)) pk = BigPick{-1, splits};    // 128 x 128 (slabs) as asked for
-    if (pk.splits != splits) {
-        splits = pk.splits;
-        per = (KB + splits - 1) / splits;
-    }
-    if (pk.tile >= 0 && launch_big(pk.tile, bf16, one, a, amax_a, b, amax_b, splits > 1 ? nullptr : bias, c, ldc, m, n, KB,
-                                   splits > 1 ? 0 : accumulate, st, splits, per, workspace, c2, m_split, relu, amax_out)) {
-        int rc = launch_status();
-        if (rc != PTMI_OK || splits == 1) return rc;
-        const long long total = (long long)m * n;
-        const unsigned rgrid = (unsigned)std::min<long long>((total + 255) / 256, relu ? 1024 : 4096);      // (relu: one atomic per workgroup)
-        hipLaunchKernelGGL(planes_reduce_kernel, dim3(rgrid), dim3(256), 0, st, workspace, splits, c, (long long)ldc, bias, m, n,
-                           accumulate ? 1 : 0, c2, m_split, relu, amax_out);
-        return launch_status();
-    }
-    PlanesArgs G{reinterpret_cast<const uint4*>(a), reinterpret_cast<const uint4*>(b), c, workspace, amax_a, amax_b, bias, m, n, KB,
-                 (long long)ldc, accumulate ? 1 : 0, per, (m + PBM - 1) / PBM, (n + PBN - 1) / PBN};
-    G.C2 = c2;
-    G.m_split = m_split;
-    G.relu = splits > 1 ? 0 : relu;
-    G.amax_out = amax_out;
-    const int tiles = G.tiles_m * G.tiles_n;
-    const dim3 grid((unsigned)((tiles + 7) / 8 * 8), 1u, (unsigned)splits);
-    if (G.relu)
-        hipLaunchKernelGGL((gemm_planes_kernel<false, false, true>), grid, dim3(256), 0, st, G);
-    else if (bf16 && one)
-        hipLaunchKernelGGL((gemm_planes_kernel<true, true>), grid, dim3(256), 0, st, G);
-    else if (bf16)
-        hipLaunchKernelGGL((gemm_planes_kernel<true, false>), grid, dim3(256), 0, st, G);
-    else if (one)
-        hipLaunchKernelGGL((gemm_planes_kernel<false, true>), grid, dim3(256), 0, st, G);
-    else
-        hipLaunchKernelGGL((gemm_planes_kernel<false, false>), grid, dim3(256), 0, st, G);
-    int rc = launch_status();
-    if (rc != PTMI_OK || splits == 1) return rc;
-    const long long total = (long long)m * n;
-    const unsigned rgrid = (unsigned)std::min<long long>((total + 255) / 256, relu ? 1024 : 4096);
-    hipLaunchKernelGGL(planes_reduce_kernel, dim3(rgrid), dim3(256), 0, st, workspace, splits, c, (long long)ldc, bias, m, n,
-                       accumulate ? 1 : 0, c2, m_split, relu, amax_out);
+    const int splits = whole_ranges(co_resident ? -split_k : split_k, KB), pinned = tile_override();
+    BigPick pk = pick_big(&m, &n, 1, KB, (co_resident && pinned < 0) ? 1 : splits, false, pinned);
+    if (pinned >= 0) pk.splits = splits;
+    else if (co_resident) pk = BigPick{-1, splits};
+    if (planes_bytes(m, KB) >= PLANES_LIMIT || planes_bytes(n, KB) >= PLANES_LIMIT) pk.tile = -1;
+    return Plan{pk.tile, pk.splits, (KB + pk.splits - 1) / pk.splits, KB};
+}
+
+static int32_t plan_code(int tile, int splits) { return (tile < 0 ? 5 : tile) * 100 + splits; }
+
+// A single-product call as its entry point states it: C (+)= A B^T (+ bias), rows from m_split on into c2 where c2 is set.  The entry
+// points fill it by field name (designated initializers: in declaration order).
+struct PlanesCall {
+    const uint16_t *a = nullptr, *b = nullptr;                  // planes: fp16 with the operand scales amax_a / amax_b, or bf16 (no scales)
+    const uint32_t *amax_a = nullptr, *amax_b = nullptr;
+    const float* bias = nullptr;
+    float *c = nullptr, *c2 = nullptr;
+    int32_t m_split = 0;
+    int64_t ldc = 0;
+    int32_t m = 0, n = 0, k = 0, accumulate = 0, split_k = 1;
+    int relu = 0;                                               // the fused epilogue of PlanesArgs, with amax_out
+    uint32_t* amax_out = nullptr;
+    float* workspace = nullptr;                                 // slabs: ptmi_gemm_planes_workspace_elems floats
+    bool bf16 = false, one = false;                             // one: only the hi planes are multiplied
+    ptmi_stream_t stream = nullptr;
+};
+
+// (a launch with slabs leaves bare partial products: bias, accumulate and relu are reduce_slabs' business then; tiles_m / tiles_n: by tile)
+static BigArgs big_args(const PlanesCall& q, const Plan& p) {
+    const bool slabs = p.splits > 1;
+    return {.A = reinterpret_cast<const uint4*>(q.a), .B = reinterpret_cast<const uint4*>(q.b), .C = q.c, .amax_a = q.amax_a, .amax_b = q.amax_b,
+            .bias = slabs ? nullptr : q.bias, .M = q.m, .N = q.n, .KB = p.KB, .ldc = q.ldc, .accumulate = (q.accumulate && !slabs) ? 1 : 0,
+            .band = 4, .a_bytes = (unsigned)planes_bytes(q.m, p.KB), .b_bytes = (unsigned)planes_bytes(q.n, p.KB), .splits = p.splits,
+            .kb_per_split = p.kb_per_split, .slabs = q.workspace, .C2 = q.c2, .m_split = q.m_split, .relu = slabs ? 0 : q.relu,
+            .amax_out = q.amax_out};
+}
+
+static PlanesArgs planes_args(const PlanesCall& q, const Plan& p) {
+    return {.A = reinterpret_cast<const uint4*>(q.a), .B = reinterpret_cast<const uint4*>(q.b), .C = q.c, .workspace = q.workspace,
+            .amax_a = q.amax_a, .amax_b = q.amax_b, .bias = q.bias, .M = q.m, .N = q.n, .KB = p.KB, .ldc = q.ldc,
+            .accumulate = q.accumulate ? 1 : 0, .kb_per_split = p.kb_per_split, .tiles_m = (q.m + PBM - 1) / PBM, .tiles_n = (q.n + PBN - 1) / PBN,
+            .C2 = q.c2, .m_split = q.m_split, .relu = p.splits > 1 ? 0 : q.relu, .amax_out = q.amax_out};
+}
+
+// the slabs of a single-product call, summed in slab order into its outputs (with bias, accumulate and the ReLU epilogue)
+static int reduce_slabs(const PlanesCall& q, int splits, hipStream_t st) {
+    const long long total = (long long)q.m * q.n;
+    const unsigned rgrid = (unsigned)std::min<long long>((total + 255) / 256, q.relu ? 1024 : 4096);      // (relu: one atomic per workgroup)
+    hipLaunchKernelGGL(planes_reduce_kernel, dim3(rgrid), dim3(256), 0, st, q.workspace, splits, q.c, (long long)q.ldc, q.bias, q.m, q.n,
+                       q.accumulate ? 1 : 0, q.c2, q.m_split, q.relu, q.amax_out);
     return launch_status();
+}
+
+static int gemm_planes_impl(const PlanesCall& q) {
+    PTMI_RETURN_IF(!q.a || !q.b || !q.c || q.m < 1 || q.n < 1 || q.k < 1 || q.ldc < q.n, PTMI_E_INVALID);
+    PTMI_RETURN_IF(q.relu && (q.accumulate || q.c2 || q.bf16 || q.one), PTMI_E_INVALID);
+    PTMI_RETURN_IF(q.c2 && (q.m_split < 16 || q.m_split >= q.m || q.m_split % 16 != 0), PTMI_E_INVALID);
+    PTMI_RETURN_IF(((reinterpret_cast<uintptr_t>(q.a) | reinterpret_cast<uintptr_t>(q.b)) & 15) != 0, PTMI_E_INVALID);
+    // (a split_k whose workspace query is not zero needs the workspace, whatever the plan makes of it)
+    PTMI_RETURN_IF(!q.workspace && ptmi_gemm_planes_workspace_elems(q.m, q.n, q.k, q.split_k) > 0, PTMI_E_INVALID);
+    const Plan p = plan_call(q.m, q.n, q.k, q.split_k);
+    const bool relu = q.relu && p.splits == 1;
+    hipStream_t st = static_cast<hipStream_t>(q.stream);
+    if (p.tile >= 0) {
+        BigArgs G = big_args(q, p);
+        with_tile(p.tile, [&](auto t) {
+            constexpr int MT = TILES[decltype(t)::value].mt, NT = TILES[decltype(t)::value].nt;
+            G.tiles_m = (q.m + 32 * MT - 1) / (32 * MT);
+            G.tiles_n = (q.n + 64 * NT - 1) / (64 * NT);
+            const dim3 grid((unsigned)std::min((G.tiles_m * G.tiles_n * p.splits + 7) / 8 * 8, cu_count() / 8 * 8));
+            with_variant(q.bf16, q.one, relu, [&](auto bf16, auto one, auto rl) {
+                hipLaunchKernelGGL((gemm_planes_big_kernel<decltype(bf16)::value, MT, NT, decltype(one)::value, decltype(rl)::value>), grid,
+                                   dim3(512), 0, st, G);
+            });
+        });
+    } else {
+        const PlanesArgs G = planes_args(q, p);
+        const dim3 grid((unsigned)((G.tiles_m * G.tiles_n + 7) / 8 * 8), 1u, (unsigned)p.splits);
+        with_variant(q.bf16, q.one, relu, [&](auto bf16, auto one, auto rl) {
+            hipLaunchKernelGGL((gemm_planes_kernel<decltype(bf16)::value, decltype(one)::value, decltype(rl)::value>), grid, dim3(256), 0, st, G);
+        });
+    }
+    const int rc = launch_status();
+    return (rc != PTMI_OK || p.splits == 1) ? rc : reduce_slabs(q, p.splits, st);
 }
 
 extern "C" {
@@ -1201,8 +1215,8 @@ int ptmi_gemm_planes_relu(const uint16_t* a, const uint32_t* amax_a, const uint1
         hipError_t e = zero_words_async(amax_out, 1, static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return (int)e;
     }
-    return gemm_planes_impl(false, products == 1, a, amax_a, b, amax_b, bias, c, ldc, m, n, k, 0, split_k, workspace, stream, nullptr, 0, 1,
-                            amax_out);
+    return gemm_planes_impl({.a = a, .b = b, .amax_a = amax_a, .amax_b = amax_b, .bias = bias, .c = c, .ldc = ldc, .m = m, .n = n, .k = k,
+                             .split_k = split_k, .relu = 1, .amax_out = amax_out, .workspace = workspace, .one = products == 1, .stream = stream});
 }
 
 int ptmi_relu_backward_absmax(const float* g, const float* y, float* out, int64_t rows, int64_t cols, int64_t ld_g, int64_t ld_y,
@@ -1225,32 +1239,22 @@ int ptmi_gemm_planes(const uint16_t* a, const uint32_t* amax_a, const uint16_t* 
                      int64_t ldc, int32_t m, int32_t n, int32_t k, int32_t accumulate, int32_t split_k, int32_t products,
                      float* workspace, ptmi_stream_t stream) {
     PTMI_RETURN_IF(products != 3 && products != 1, PTMI_E_INVALID);
-    return gemm_planes_impl(false, products == 1, a, amax_a, b, amax_b, bias, c, ldc, m, n, k, accumulate, split_k, workspace, stream);
+    return gemm_planes_impl({.a = a, .b = b, .amax_a = amax_a, .amax_b = amax_b, .bias = bias, .c = c, .ldc = ldc, .m = m, .n = n, .k = k,
+                             .accumulate = accumulate, .split_k = split_k, .workspace = workspace, .one = products == 1, .stream = stream});
 }
 
 int32_t ptmi_gemm_planes_plan(int32_t m, int32_t n, int32_t k, int32_t split_k) {
-    // the choice gemm_planes_impl makes for this call: 100 * tile + k ranges (tile 0..4: the big-tile instantiations, 5: 128 x 128)
+    // what gemm_planes_impl runs for this call: 100 * tile + k ranges (tile 0..4: the big-tile instantiations, 5: 128 x 128)
     if (m < 1 || n < 1 || k < 1) return -1;
-    const int KB = (k + 31) / 32;
-    const bool co_resident = split_k < 0;
-    if (co_resident) split_k = -split_k;
-    int splits = std::max(1, std::min<int>(split_k, KB));
-    const int per0 = (KB + splits - 1) / splits;
-    splits = (KB + per0 - 1) / per0;
-    static const bool big_split = !(getenv("PTMI_GEMM_BIG_SPLIT") && atoi(getenv("PTMI_GEMM_BIG_SPLIT")) == 0);
-    const int g_tile_override = tile_override();
-    BigPick pk = pick_big(m, n, KB, ((big_split && !co_resident) || g_tile_override >= 0) ? splits : 1);
-    if (g_tile_override >= 0) pk.splits = splits;
-    else if (co_resident || (!big_split && splits > 1)) pk = BigPick{-1, splits};
-    const long long a_bytes = (long long)((m + 15) / 16) * KB * 2048, b_bytes = (long long)((n + 15) / 16) * KB * 2048;
-    if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31)) pk.tile = -1;
-    return (pk.tile < 0 ? 5 : pk.tile) * 100 + pk.splits;
+    const Plan p = plan_call(m, n, k, split_k);
+    return plan_code(p.tile, p.splits);
 }
 
 int ptmi_gemm_planes_bf16(const uint16_t* a, const uint16_t* b, const float* bias, float* c, int64_t ldc, int32_t m, int32_t n,
                           int32_t k, int32_t accumulate, int32_t split_k, int32_t products, float* workspace, ptmi_stream_t stream) {
     PTMI_RETURN_IF(products != 3 && products != 1, PTMI_E_INVALID);
-    return gemm_planes_impl(true, products == 1, a, nullptr, b, nullptr, bias, c, ldc, m, n, k, accumulate, split_k, workspace, stream);
+    return gemm_planes_impl({.a = a, .b = b, .bias = bias, .c = c, .ldc = ldc, .m = m, .n = n, .k = k, .accumulate = accumulate,
+                             .split_k = split_k, .workspace = workspace, .bf16 = true, .one = products == 1, .stream = stream});
 }
 
 int ptmi_gemm_planes_bf16_two(const uint16_t* a, const uint16_t* b, float* c, float* c2, int32_t m_split, int64_t ldc, int32_t m,
@@ -1258,8 +1262,8 @@ int ptmi_gemm_planes_bf16_two(const uint16_t* a, const uint16_t* b, float* c, fl
                               ptmi_stream_t stream) {
     PTMI_RETURN_IF((products != 3 && products != 1) || !c2, PTMI_E_INVALID);
     PTMI_RETURN_IF((reinterpret_cast<uintptr_t>(c) ^ reinterpret_cast<uintptr_t>(c2)) & 15, PTMI_E_INVALID);       // one alignment class
-    return gemm_planes_impl(true, products == 1, a, nullptr, b, nullptr, nullptr, c, ldc, m, n, k, accumulate, split_k, workspace, stream,
-                            c2, m_split);
+    return gemm_planes_impl({.a = a, .b = b, .c = c, .c2 = c2, .m_split = m_split, .ldc = ldc, .m = m, .n = n, .k = k, .accumulate = accumulate,
+                             .split_k = split_k, .workspace = workspace, .bf16 = true, .one = products == 1, .stream = stream});
 }
 
 // ---------------------------------------------------------------------------------------------------------------- grouped call
@@ -1296,7 +1300,6 @@ namespace {
 struct GroupPlan {
     int nblocks = 0;
     int part[GROUP_BLOCKS], seg[GROUP_BLOCKS], rows[GROUP_BLOCKS], cols[GROUP_BLOCKS];
-    long long elems = 0;            // output elements of all blocks
     long long slab_elems = 0;       // one slab of every block (each rounded up to 4 floats)
 };
 
@@ -1311,7 +1314,6 @@ bool group_plan(GroupPlan& P, int32_t m, int32_t m_split, const int32_t* n, int3
             P.seg[b] = s;
             P.rows[b] = p ? m - m_split : m_split;
             P.cols[b] = n[s];
-            P.elems += (long long)P.rows[b] * n[s];
             P.slab_elems += ((long long)P.rows[b] * n[s] + 3) / 4 * 4;
         }
     return P.nblocks > 0;
@@ -1319,15 +1321,12 @@ bool group_plan(GroupPlan& P, int32_t m, int32_t m_split, const int32_t* n, int3
 
 // tile (0..4, or -1: the big-tile path is not possible) and k ranges of a grouped call: a function of the shapes alone
 BigPick group_choice(const GroupPlan& P, int32_t m, int32_t m_split, const int32_t* n, int32_t segments, int KB, int32_t split_k) {
-    int splits = std::max(1, std::min<int>(split_k, KB));
-    int per = (KB + splits - 1) / splits;
-    splits = (KB + per - 1) / per;
-    BigPick pk = pick_big(P.rows, P.cols, P.nblocks, KB, splits, true);          // the plain calls' model over the items of ALL blocks
-    if (tile_override() >= 0) pk.splits = splits;           // a pinned tile takes split_k as it is
-    if (m_split % 16 != 0) pk.tile = -1;
-    if ((long long)((m + 15) / 16) * KB * 2048 >= (1ll << 31)) pk.tile = -1;
+    const int splits = whole_ranges(split_k, KB), pinned = tile_override();
+    BigPick pk = pick_big(P.rows, P.cols, P.nblocks, KB, splits, true, pinned);  // the plain calls' model over the items of ALL blocks
+    if (pinned >= 0) pk.splits = splits;                    // a pinned tile takes split_k as it is
+    if (m_split % 16 != 0 || planes_bytes(m, KB) >= PLANES_LIMIT) pk.tile = -1;
     for (int s = 0; s < segments; ++s)
-        if ((long long)((n[s] + 15) / 16) * KB * 2048 >= (1ll << 31)) pk.tile = -1;
+        if (planes_bytes(n[s], KB) >= PLANES_LIMIT) pk.tile = -1;
     return pk;
 }
 
@@ -1367,7 +1366,7 @@ int32_t ptmi_gemm_planes_group_plan(int32_t m, int32_t m_split, const int32_t* n
     GroupPlan P;
     if (k < 1 || !group_plan(P, m, m_split, n, segments, c)) return -1;
     const BigPick pk = group_choice(P, m, m_split, n, segments, (k + 31) / 32, split_k);
-    return (pk.tile < 0 ? 5 : pk.tile) * 100 + pk.splits;
+    return plan_code(pk.tile, pk.splits);
 }
 
 int ptmi_gemm_planes_bf16_group(const uint16_t* a, int32_t m, int32_t m_split, const uint16_t* const* b, const int32_t* n, int32_t segments,
@@ -1390,7 +1389,7 @@ int ptmi_gemm_planes_bf16_group(const uint16_t* a, int32_t m, int32_t m_split, c
     G.M = m;
     G.KB = KB;
     G.band = 4;
-    G.a_bytes = (unsigned)((long long)((m + 15) / 16) * KB * 2048);
+    G.a_bytes = (unsigned)planes_bytes(m, KB);
     G.splits = pk.splits;
     G.kb_per_split = (KB + pk.splits - 1) / pk.splits;
     G.slabs = workspace;
@@ -1401,7 +1400,7 @@ int ptmi_gemm_planes_bf16_group(const uint16_t* a, int32_t m, int32_t m_split, c
     for (int s = 0; s < segments; ++s) {
         G.T.B[s] = reinterpret_cast<const uint4*>(b[s]);
         G.T.rtb[s] = (n[s] + 15) / 16;
-        G.T.b_bytes[s] = (unsigned)((long long)G.T.rtb[s] * KB * 2048);
+        G.T.b_bytes[s] = (unsigned)planes_bytes(n[s], KB);
     }
     ReduceGroupArgs R{};
     R.ws = workspace;
@@ -1426,14 +1425,10 @@ int ptmi_gemm_planes_bf16_group(const uint16_t* a, int32_t m, int32_t m_split, c
         start += R.vec[q] ? e / 4 : e;
     }
     for (int q = P.nblocks; q <= GROUP_BLOCKS; ++q) R.start[q] = start;
-    const bool one = products == 1;
-    switch (pk.tile) {
-        case 0: launch_group_inst<8, 5>(G, P, one, st); break;
-        case 1: launch_group_inst<8, 4>(G, P, one, st); break;
-        case 2: launch_group_inst<8, 3>(G, P, one, st); break;
-        case 3: launch_group_inst<4, 5>(G, P, one, st); break;
-        default: launch_group_inst<4, 4>(G, P, one, st); break;
-    }
+    with_tile(pk.tile, [&](auto t) {
+        constexpr Tile tl = TILES[decltype(t)::value];
+        launch_group_inst<tl.mt, tl.nt>(G, P, products == 1, st);
+    });
     int rc = launch_status();
     if (rc != PTMI_OK) return rc;
     const unsigned rgrid = (unsigned)std::min<long long>((start + 255) / 256, 4096);

@@ -403,25 +403,6 @@ def group_plan(M, m_split, ns, blocks, K, split_k):
     return int(_lib.load().ptmi_gemm_planes_group_plan(M, m_split, (ctypes.c_int32 * S)(*[int(v) for v in ns]), S, c, K, split_k))
 
 
-#: weight-gradient GEMMs that run BESIDE a persistent recurrence: up to this many reduction rows on the 128 x 128 kernel, whose
-#: workgroups share a CU with the recurrence's (``co_resident_split_k``); longer ones on big tiles on the CUs the recurrence leaves free.
-#: 0 since the end of round 4 (every such GEMM on the big tiles): with the recurrences' step time down to 2.3 / 3.6 us the
-#: weight-gradient queue, not the recurrence, ends the backward phase, and workgroups that share CUs with a recurrence slow it by more than
-#: they gain (B = 32, 8 kHz: 6.645 -> 6.60 ms per step; until then 16384: 7.15 against 7.18; ``profiles/r4_ab_step.txt``)
-CO_RESIDENT_MAX_K = 0
-
-
-def co_resident_split_k(M, N, K):
-    """``split_k`` of a weight-gradient GEMM that runs next to a recurrence (``ptmi_gemm_planes``: negative = exactly that many k ranges
-    on the 128 x 128 kernel, measured: until about two workgroups per CU exist, every range at least 16 k steps)."""
-    if K > CO_RESIDENT_MAX_K:
-        return auto_split_k(M, N, K)
-    tiles = -(-M // 128) * -(-N // 128)
-    if tiles >= 1024:
-        return 1
-    return -max(1, min(512 // tiles, K // 512, 8))
-
-
 def mm(x, y, bias=None, out=None, accumulate=False, amax_x=None, amax_y=None, split_k=None):
     """``out (+)= x @ y + bias`` for fp32 CUDA tensors ``x [M, K]``, ``y [K, N]`` with one unit stride each (transposed views
     and column blocks of wider matrices are consumed in place): either operand is split into planes by the pack pass of its

@@ -791,24 +791,18 @@ def pack_planes_n(x, amax):
 @_register('gemm_planes_(Tensor(a!) out, Tensor a, Tensor? amax_a, Tensor b, Tensor? amax_b, Tensor? bias, int M, int N, int K, '
            'bool accumulate, int split_k) -> ()')
 def gemm_planes_(out, a, amax_a, b, amax_b, bias, M, N, K, accumulate, split_k):
-    lib = _lib.load()
-    nws = int(lib.ptmi_gemm_planes_workspace_elems(M, N, K, split_k))
-    ws = torch.empty(nws, dtype=torch.float32, device=out.device) if nws else None
-    _lib.check(_lib.timed(f'gemm_planes:{M}x{N}x{K}:{split_k}', lib.ptmi_gemm_planes, a.data_ptr(), _lib.ptr(amax_a), b.data_ptr(),
-                          _lib.ptr(amax_b), _lib.ptr(bias), out.data_ptr(), max(out.stride(0), N), M, N, K, int(accumulate), split_k,
-                          _products(), _lib.ptr(ws), _lib.stream(out.device)), 'ptmi_gemm_planes')
+    _gemm_planes_call('ptmi_gemm_planes', 'gemm_planes', out, M, N, K, split_k,
+                      (a.data_ptr(), _lib.ptr(amax_a), b.data_ptr(), _lib.ptr(amax_b), _lib.ptr(bias), out.data_ptr(), max(out.stride(0), N),
+                       M, N, K, int(accumulate)))
 
 
 @_register('gemm_planes_relu_(Tensor(a!) out, Tensor a, Tensor? amax_a, Tensor b, Tensor? amax_b, Tensor? bias, int M, int N, int K, '
            'int split_k, Tensor(b!) amax_out) -> ()')
 def gemm_planes_relu_(out, a, amax_a, b, amax_b, bias, M, N, K, split_k, amax_out):
     """``out = relu(A B^T + bias)`` and the float bits of ``max out`` into the ZEROED word ``amax_out`` (``ptmi_gemm_planes_relu``)."""
-    lib = _lib.load()
-    nws = int(lib.ptmi_gemm_planes_workspace_elems(M, N, K, split_k))
-    ws = torch.empty(nws, dtype=torch.float32, device=out.device) if nws else None
-    _lib.check(_lib.timed(f'gemm_planes:{M}x{N}x{K}:{split_k}', lib.ptmi_gemm_planes_relu, a.data_ptr(), _lib.ptr(amax_a), b.data_ptr(),
-                          _lib.ptr(amax_b), _lib.ptr(bias), out.data_ptr(), max(out.stride(0), N), M, N, K, split_k, _products(),
-                          _lib.ptr(ws), amax_out.data_ptr(), 1, _lib.stream(out.device)), 'ptmi_gemm_planes_relu')
+    _gemm_planes_call('ptmi_gemm_planes_relu', 'gemm_planes', out, M, N, K, split_k,
+                      (a.data_ptr(), _lib.ptr(amax_a), b.data_ptr(), _lib.ptr(amax_b), _lib.ptr(bias), out.data_ptr(), max(out.stride(0), N),
+                       M, N, K), (amax_out.data_ptr(), 1))
 
 
 @_register('relu_backward_absmax(Tensor g, Tensor y, Tensor(a!) amax_out) -> Tensor')
@@ -833,6 +827,15 @@ def _products():
     from . import gemm
     return 1 if gemm.PRODUCTS == 1 else 3
 
+
+def _gemm_planes_call(entry, timer, out, M, N, K, split_k, head, tail=()):
+    """One single-product planes GEMM ``entry(*head, split_k, products, workspace, *tail, stream)``: the slab workspace ``split_k`` asks
+    for, the timed call (``timer:MxNxK:split_k`` - ``bench.py`` parses the name) and its return code."""
+    lib = _lib.load()
+    nws = int(lib.ptmi_gemm_planes_workspace_elems(M, N, K, split_k))
+    ws = torch.empty(nws, dtype=torch.float32, device=out.device) if nws else None
+    _lib.check(_lib.timed(f'{timer}:{M}x{N}x{K}:{split_k}', getattr(lib, entry), *head, split_k, _products(), _lib.ptr(ws), *tail,
+                          _lib.stream(out.device)), entry)
 
 
 @_register('pack_planes_bf16(Tensor x, bool transposed) -> Tensor')
@@ -867,12 +870,8 @@ def pack_planes_into_(out, x, amax, transposed, kb_total, kb_offset, kb_count):
 def gemm_planes_bf16_(out, a, a_offset, b, bias, M, N, K, accumulate, split_k):
     """``a``: any tensor whose storage holds the bf16 planes of the M x K operand from byte ``a_offset`` on (16-byte aligned) -
     e.g. the scratch of the persistent backward recurrence (``ptmi_lstm_handoff_cols``)."""
-    lib = _lib.load()
-    nws = int(lib.ptmi_gemm_planes_workspace_elems(M, N, K, split_k))
-    ws = torch.empty(nws, dtype=torch.float32, device=out.device) if nws else None
-    _lib.check(_lib.timed(f'gemm_planes_bf16:{M}x{N}x{K}:{split_k}', lib.ptmi_gemm_planes_bf16, a.data_ptr() + a_offset, b.data_ptr(),
-                          _lib.ptr(bias), out.data_ptr(), max(out.stride(0), N), M, N, K, int(accumulate), split_k, _products(),
-                          _lib.ptr(ws), _lib.stream(out.device)), 'ptmi_gemm_planes_bf16')
+    _gemm_planes_call('ptmi_gemm_planes_bf16', 'gemm_planes_bf16', out, M, N, K, split_k,
+                      (a.data_ptr() + a_offset, b.data_ptr(), _lib.ptr(bias), out.data_ptr(), max(out.stride(0), N), M, N, K, int(accumulate)))
 
 
 @_register('gemm_planes_bf16_two_(Tensor(a!) out, Tensor(b!) out2, Tensor a, int a_offset, Tensor b, int M, int N, int K, bool accumulate, '
@@ -880,13 +879,10 @@ def gemm_planes_bf16_(out, a, a_offset, b, bias, M, N, K, accumulate, split_k):
 def gemm_planes_bf16_two_(out, out2, a, a_offset, b, M, N, K, accumulate, split_k):
     """``[out; out2] (+)= A B^T`` (``ptmi_gemm_planes_bf16_two``): ``out`` takes the first ``out.shape[0]`` rows of the M x N product,
     ``out2`` the rest - two parameters' gradient buffers with one row stride (both directions' ``dW_ih`` of a BLSTM layer)."""
-    lib = _lib.load()
     assert out.shape[0] + out2.shape[0] == M and out.shape[1] == out2.shape[1] == N and out.stride(0) == out2.stride(0), (out.shape, out2.shape)
-    nws = int(lib.ptmi_gemm_planes_workspace_elems(M, N, K, split_k))
-    ws = torch.empty(nws, dtype=torch.float32, device=out.device) if nws else None
-    _lib.check(_lib.timed(f'gemm_planes_bf16:{M}x{N}x{K}:{split_k}', lib.ptmi_gemm_planes_bf16_two, a.data_ptr() + a_offset, b.data_ptr(),
-                          out.data_ptr(), out2.data_ptr(), out.shape[0], max(out.stride(0), N), M, N, K, int(accumulate), split_k,
-                          _products(), _lib.ptr(ws), _lib.stream(out.device)), 'ptmi_gemm_planes_bf16_two')
+    _gemm_planes_call('ptmi_gemm_planes_bf16_two', 'gemm_planes_bf16', out, M, N, K, split_k,
+                      (a.data_ptr() + a_offset, b.data_ptr(), out.data_ptr(), out2.data_ptr(), out.shape[0], max(out.stride(0), N), M, N, K,
+                       int(accumulate)))
 
 
 @_register('pack_planes_bf16_list(Tensor[] xs) -> Tensor[]')

@@ -327,9 +327,6 @@ class _WgradJob:
         range all four products go out as one grouped call (`GROUP_WGRAD`) on one queue: `main` for both_queues, else `side`."""
         lib, gm, params, x, h0, ndir, H, G = self.lib, self.gm, self.params, self.x, self.h0, self.ndir, self.H, self.G
         main, side, xplanes = self.plan.main, self.plan.side, self.xplanes
-        # the first layer's weight gradients have the chip to themselves (the step's tail): big tiles; every other layer's run
-        # beside the next recurrence: short ones on the kernel whose workgroups share CUs with the recurrence's
-        split_of = _gemm.auto_split_k if self.first_layer else _gemm.co_resident_split_k
         if self._grouped(dg_t, ranges):
             # all four products reduce over the same packed rows and share operands (x: both dW_ih; each direction's dgates^T: its
             # dW_ih and dW_hh): one pack launch, one GEMM launch over the tiles of all four, one slab reduction
@@ -355,7 +352,7 @@ class _WgradJob:
                     if key not in xplanes:
                         xplanes[key] = torch.ops.ptmi.pack_planes_bf16(x[r0:r1], True)
                     torch.ops.ptmi.gemm_planes_bf16_two_(ga, gb, dg_t, 0, xplanes[key], 2 * G, x.shape[1], r1 - r0, True,
-                                                         split_of(2 * G, x.shape[1], r1 - r0))
+                                                         _gemm.auto_split_k(2 * G, x.shape[1], r1 - r0))
                 fused_ih = True
         for d, ((p_wih, p_whh, _, _), (r0, r1)) in enumerate(zip(params, ranges)):
             q_ih = main if both_queues else side
@@ -376,10 +373,10 @@ class _WgradJob:
                         xplanes[key] = torch.ops.ptmi.pack_planes_bf16(x[r0:r1], True)
                     if not fused_ih:
                         torch.ops.ptmi.gemm_planes_bf16_(p_wih.grad, dg_t, a_off, xplanes[key], None, G, x.shape[1], k, True,
-                                                         split_of(G, x.shape[1], k))
+                                                         _gemm.auto_split_k(G, x.shape[1], k))
                     with torch.cuda.stream(q_hh):
                         hpl = torch.ops.ptmi.pack_planes_bf16(h_prev[r0:r1], True)
-                        torch.ops.ptmi.gemm_planes_bf16_(p_whh.grad, dg_t, a_off, hpl, None, G, H, k, True, split_of(G, H, k))
+                        torch.ops.ptmi.gemm_planes_bf16_(p_whh.grad, dg_t, a_off, hpl, None, G, H, k, True, _gemm.auto_split_k(G, H, k))
                     continue
                 dgt = dgd[r0:r1].t()
                 if gm is not None and _gemm.planes_enabled():
@@ -392,10 +389,10 @@ class _WgradJob:
                         dgp = _gemm.pack_t(dgd[r0:r1], amax_dg)
                     if key not in xplanes:
                         xplanes[key] = _gemm.pack_t(x[r0:r1], gm[0])
-                    _gemm.mm_planes_(p_wih.grad, dgp, xplanes[key], G, x.shape[1], k, accumulate=True, split_k=split_of(G, x.shape[1], k))
+                    _gemm.mm_planes_(p_wih.grad, dgp, xplanes[key], G, x.shape[1], k, accumulate=True, split_k=_gemm.auto_split_k(G, x.shape[1], k))
                     with torch.cuda.stream(q_hh):
                         hpl = _gemm.pack_t(h_prev[r0:r1], _gemm.UNIT_RANGE if h0 is None else None)
-                        _gemm.mm_planes_(p_whh.grad, dgp, hpl, G, H, k, accumulate=True, split_k=split_of(G, H, k))
+                        _gemm.mm_planes_(p_whh.grad, dgp, hpl, G, H, k, accumulate=True, split_k=_gemm.auto_split_k(G, H, k))
                 elif gm is not None:
                     _gemm.mm(dgt, x[r0:r1], out=p_wih.grad, accumulate=True, amax_x=amax_dg, amax_y=gm[0])
                     _gemm.mm(dgt, h_prev[r0:r1], out=p_whh.grad, accumulate=True, amax_x=amax_dg,
