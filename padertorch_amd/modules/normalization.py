@@ -127,13 +127,14 @@ class _Normalize(Function):
         g32 = _f32(gamma)
         a = _reduce(1, x, grad_y, lengths, mean, None, g32, geom, shift, ctx.n_groups)
         sum_g, sum_gx, sum_x = a[:, 0], a[:, 1], a[:, 2]
-        scale_ = torch.sqrt(power_scale + eps)
         grad_mean_ = -sum_g if shift else torch.zeros_like(sum_g)
         c1 = torch.zeros_like(sum_g)
         if scale:
             grad_power_ = sum_gx * (-1 / 2) * (power_scale + eps) ** (-3 / 2)
             if shift:
-                grad_mean_ = grad_mean_ / scale_ - 2 * grad_power_ * sum_x / n
+                # the float32 rstd the kernel multiplies ghat with: ghat * rstd and sum(ghat) * rstd / n cancel (exactly for
+                # a group of one value, where both are ~ghat / sqrt(eps)) only if they carry the same rounding of rstd
+                grad_mean_ = grad_mean_ * rstd.to(torch.float64) - 2 * grad_power_ * sum_x / n
             c1 = grad_power_ * 2 / n
         c0 = grad_mean_ / n if shift else torch.zeros_like(sum_g)
         grad_x = None
