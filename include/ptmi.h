@@ -639,7 +639,22 @@ int ptmi_orpit_flag_backward(const float* gflag, const float* gpre, const float*
  *   for every example; ref_channel < 0: per example argmax_r sum_f Re(w_r^H psd_target w_r) / max(sum_f Re(w_r^H psd_noise w_r), DBL_MIN)
  *   with w_r = w_all[:, :, :, r] before rounding, the first maximum; numden [B, F, C, 2] float64 holds the summands (may be NULL for
  *   ref_channel >= 0).  ref_out [B] int32: the column taken.  Rank-deficient, non-zero psd_noise is not guarded.
- * ptmi_bf_apply : Z[b,t,f] = sum_c conj(w[b,f,c]) X[b,c,t,f], Z [B, T, F] complex64; T <= 32 * 65535. */
+ * ptmi_bf_apply : Z[b,t,f] = sum_c conj(w[b,f,c]) X[b,c,t,f], Z [B, T, F] complex64; T <= 32 * 65535.
+ * ptmi_bf_eig   : the GEV (mode 0) or PCA (mode 1) vector per bin, fp64, one lane a bin: w [B, F, C] complex64, lambda [B, F] float64
+ *   (the eigenvalue), sweeps [B, F] int32 or NULL (the Jacobi sweeps a bin took).
+ *   mode 0: Cholesky psd_noise = L L^H (lower triangle read), A = L^-1 psd_target L^-H by two triangular solves, made exactly
+ *   Hermitian ((A + A^H) / 2); cyclic complex Jacobi (pairs p < q in row order) while off(A)^2 > (2^-52)^2 ||A||_F^2, at most 16
+ *   sweeps; v the eigenvector of the largest eigenvalue (first maximum), w = L^-H v, so w^H psd_noise w = 1.
+ *   mode 1: the same Jacobi on (psd_target + psd_target^H) / 2, |w|_2 = 1; psd_noise may be NULL unless ban.
+ *   Gauge: w is rotated so that its component of largest squared magnitude (first maximum) is real and positive.
+ *   A Cholesky pivot that is not > 0 (zero or indefinite psd_noise, NaN) or an all-zero A gives w = 0 and lambda = 0.
+ *   ban != 0: the rounded (complex64) w goes through ptmi_bf_ban's arithmetic before it is stored: the same bits as the two calls.
+ * ptmi_bf_ban   : blind analytic normalisation, out = w sqrt(|w^H N N w|) / max(|w^H N w|, DBL_MIN) with N = psd_noise, in fp64 on the
+ *   complex64 w; a zero vector stays zero.  out may be w.
+ * ptmi_bf_phase : per example, for f = 1 .. F-1 in order out_f = w_f exp(-i arg(sum_c w_f,c conj(out_{f-1},c))), out_0 = w_0; a sum that
+ *   is exactly zero rotates by nothing.  Computed as out_f = c_f w_f, c_f = c_{f-1} conj(d_f / |d_f|) with d_f = sum_c w_f,c conj(w_{f-1},c)
+ *   (c_f = 1 where d_f = 0): a segmented inclusive scan of fp64 unit phasors by one workgroup per example in one fixed order for any
+ *   F (bit-reproducible).  out must not be w. */
 int64_t ptmi_bf_psd_workspace_elems(int64_t B, int32_t C, int64_t T, int64_t F, int32_t M);
 int ptmi_bf_psd(const float* Y, const float* mask0, const float* mask1, const int32_t* frames, int64_t B, int32_t C, int64_t T, int64_t F,
                 int32_t M, int32_t mask_mode, int32_t normalize, double* workspace, double* psd, ptmi_stream_t stream);
@@ -647,6 +662,10 @@ int ptmi_bf_souden(const double* psd_target, const double* psd_noise, int64_t B,
                    double* numden, float* w, int32_t* ref_out, ptmi_stream_t stream);
 int ptmi_bf_apply(const float* w, const float* X, const int32_t* frames, int64_t B, int32_t C, int64_t T, int64_t F, float* Z,
                   ptmi_stream_t stream);
+int ptmi_bf_eig(const double* psd_target, const double* psd_noise, int64_t B, int64_t F, int32_t C, int32_t mode, int32_t ban, float* w,
+                double* lambda, int32_t* sweeps, ptmi_stream_t stream);
+int ptmi_bf_ban(const float* w, const double* psd_noise, int64_t B, int64_t F, int32_t C, float* out, ptmi_stream_t stream);
+int ptmi_bf_phase(const float* w, int64_t B, int64_t F, int32_t C, float* out, ptmi_stream_t stream);
 
 /* ---- Dense layers: fp32 GEMM on the 16-bit matrix cores (split operands) --------------------------
  * Replaces the library GEMMs behind torch.nn.LSTM's input projections and torch.nn.Linear in

@@ -103,6 +103,9 @@ SIGNATURES = {
     'ptmi_bf_psd': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P]),
     'ptmi_bf_souden': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     'ptmi_bf_apply': (c_int, [_P, _P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P]),
+    'ptmi_bf_eig': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    'ptmi_bf_ban': (c_int, [_P, _P, c_int64, c_int64, c_int32, _P, _P]),
+    'ptmi_bf_phase': (c_int, [_P, c_int64, c_int64, c_int32, _P, _P]),
     'ptmi_dprnn_num_chunks': (c_int64, [c_int64, c_int32, c_int32]),
     'ptmi_dprnn_tables': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     'ptmi_chunk_lstm_max_hidden': (c_int32, []),

@@ -39,6 +39,10 @@ def _layers(num_features, num_units, dropout, activation):
 
 
 class SimpleMaskEstimator(base.Model):
+    #: the vector ``enhance`` beamforms with: one of ``ops.beamforming.BEAMFORMERS`` (``'gev+ban'``: the neural-mask GEV beamformer
+    #: with blind analytic normalization; ``gev*`` and ``pca*`` are phase-corrected along the bins and take no ``ref_channel``)
+    beamformer: str = 'mvdr_souden'
+
     def __init__(self, num_features, num_units=1024, dropout=0.5, activation='elu'):
         super().__init__()
         self.num_features = num_features
@@ -59,19 +63,21 @@ class SimpleMaskEstimator(base.Model):
     def enhance(self, y, num_samples=None, stft=None, ref_channel=None):
         """What the masks are trained for (the reference's ``evaluate.py:110-137``, there on the host): mixtures ``y [B, C, N]`` (or a
         list of ``[C, N_b]``) -> ``dict(masked=[...], beamformed=[...])``, per example one waveform ``[N_b]`` each: the first
-        channel times its speech mask, and the mask-based Souden MVDR beamformer (``ops.mask_beamforming``: channel medians of both
-        masks, reference channel chosen on the device unless ``ref_channel`` names one).  HIP STFT -> the model on the channels'
-        magnitudes -> beamformer -> HIP iSTFT, cut to ``N_b``; nothing leaves the device in between.
+        channel times its speech mask, and the mask-based beamformer ``self.beamformer`` (``ops.mask_beamforming``: channel medians
+        of both masks; Souden MVDR by default, reference channel chosen on the device unless ``ref_channel`` names one).
+        HIP STFT -> the model on the channels' magnitudes -> beamformer -> HIP iSTFT, cut to ``N_b``; nothing leaves the device in between.
 
         ``num_samples``: host integers, the valid samples of the rows of a padded ``[B, C, N]``.  The model's normalisation takes no
         lengths, so examples of ONE length go through as one batch and examples of differing lengths one by one, as in the
         reference's evaluation.  ``stft``: an ``ops.STFT`` with ``num_features`` bins (default ``STFT(1024, 256)``).  Runs in eval
         mode under ``torch.no_grad()``."""
         from .....ops import STFT
+        from .....ops.beamforming import parse_beamformer
         stft = STFT(1024, 256) if stft is None else stft
         if stft.size // 2 + 1 != self.num_features or stft.complex_representation != 'complex':
             raise ValueError(f'enhance: a complex STFT with {self.num_features} bins, got size {stft.size} '
                              f'({stft.complex_representation})')
+        parse_beamformer('enhance', self.beamformer, ref_channel)       # (before any kernel runs)
         examples = list(y.unbind(0)) if torch.is_tensor(y) else list(y)
         if not examples or any(e.dim() != 2 for e in examples):
             raise ValueError('enhance: mixtures [B, C, N] or a list of [C, N_b]')
@@ -99,7 +105,8 @@ class SimpleMaskEstimator(base.Model):
         out = self(dict(observation_abs=Y.abs().reshape(B * C, T, F)))    # the channels are the model's batch
         speech = out['speech_mask_prediction'].reshape(B, C, T, F)
         noise = out['noise_mask_prediction'].reshape(B, C, T, F)
-        spectra = torch.stack([speech[:, 0] * Y[:, 0], mask_beamforming(Y, speech, noise, ref_channel=ref_channel)])
+        spectra = torch.stack([speech[:, 0] * Y[:, 0], mask_beamforming(Y, speech, noise, ref_channel=ref_channel,
+                                                                        beamformer=self.beamformer)])
         masked, beamformed = stft.inverse(spectra)[..., :y.shape[-1]]
         return masked, beamformed
 

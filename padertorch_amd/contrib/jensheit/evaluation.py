@@ -18,11 +18,14 @@ def beamforming(observation, speech_mask, noise_mask, speech_image=None, noise_i
     :param noise_mask: ...xCxTxF
     :param speech_image: ...xCxTxF
     :param noise_image: ...xCxTxF
-    :param get_bf_fn: None or ``ops.get_mvdr_vector_souden`` (the reference's default); there is no kernel for another vector
+    :param get_bf_fn: None or ``ops.get_mvdr_vector_souden`` (the reference's default), ``ops.get_gev_vector`` or
+        ``ops.get_pca_vector`` (the plain vector, without normalization or phase correction, as the reference would apply it);
+        there is no kernel for another vector
     :return: predicted speech signal ...xTxF, and the beamformed speech and noise images (None where no image was given)
     """
-    if get_bf_fn not in (None, _bf.get_mvdr_vector_souden):
-        raise NotImplementedError(f'beamforming: only the Souden MVDR vector has a kernel, got get_bf_fn={get_bf_fn!r}')
+    beamformers = {None: 'mvdr_souden', _bf.get_mvdr_vector_souden: 'mvdr_souden', _bf.get_gev_vector: 'gev', _bf.get_pca_vector: 'pca'}
+    if get_bf_fn not in beamformers:
+        raise NotImplementedError(f'beamforming: only the Souden MVDR, GEV and PCA vectors have a kernel, got get_bf_fn={get_bf_fn!r}')
     if observation.dim() < 3:
         raise ValueError(f'beamforming: ...xCxTxF tensors, got {tuple(observation.shape)}')
     lead, tail = observation.shape[:-3], observation.shape[-3:]
@@ -31,7 +34,7 @@ def beamforming(observation, speech_mask, noise_mask, speech_image=None, noise_i
         if x.shape != observation.shape:
             raise ValueError(f'beamforming: every tensor of the observation\'s shape {tuple(observation.shape)}, got {tuple(x.shape)}')
         return x.reshape(-1, *tail)
-    w, Y, _, _ = _bf.beamforming_vector(rows(observation), rows(speech_mask), rows(noise_mask))
+    w, Y, _, _ = _bf.beamforming_vector(rows(observation), rows(speech_mask), rows(noise_mask), beamformer=beamformers[get_bf_fn])
 
     def apply(x):
         return _bf.apply_beamforming_vector(w, x).reshape(*lead, tail[1], tail[2])

@@ -4,6 +4,10 @@
 //   psd     Phi_k[b,f,d,e] = sum_t m_k[b,t,f] Y[b,d,t,f] conj(Y[b,e,t,f]) / max(sum_t m_k[b,t,f], 1e-10),  m_k = median_c mask_k[b,c,t,f]
 //   souden  X = Phi_n^-1 Phi_s (Gaussian elimination with partial pivoting), M = X / max(Re trace X, DBL_MIN), w = M[:, ref]
 //   apply   Z[b,t,f] = sum_c conj(w[b,f,c]) X_in[b,c,t,f]
+//   eig     gev: Phi_n = L L^H, A = L^-1 Phi_s L^-H, cyclic complex Jacobi, v of the largest eigenvalue, w = L^-H v (w^H Phi_n w = 1);
+//           pca: the same Jacobi on Phi_s, |w| = 1; gauge: the largest component real and positive
+//   ban     w sqrt(|w^H Phi_n Phi_n w|) / max(|w^H Phi_n w|, DBL_MIN)
+//   phase   w'_f = w_f exp(-i arg(sum_c w_f,c conj(w'_{f-1},c))) along the bins, as a scan of unit phasors
 //
 // Layout: Y and X_in [B, C, T, F] complex64 (interleaved), masks [B, C, T, F] or [B, T, F] fp32, Phi [B, F, C, C] complex128,
 // w [B, F, C] complex64; frames [B] int32 (frames t >= frames[b] contribute nothing, are never loaded and come out as zero).
@@ -354,6 +358,352 @@ __global__ __launch_bounds__(256) void bf_pick_kernel(const double* __restrict__
     for (long long i = threadIdx.x; i < F * C; i += 256) w[b * F * C + i] = w_all[(b * F * C + i) * C + ref];
 }
 
+// ---- GEV / PCA ------------------------------------------------------------------------------------------------------------------------
+// One bin's principal (generalized) eigenvector in fp64, on three C x C complex matrices of the bin that are addressed as
+// m[((r C + c) 2 + part) L] (the [element][lane] layout of bf_souden_kernel with L lanes; L = 1 on the host):
+//   l   Phi_n, then its Cholesky factor in the lower triangle (mode gev only)
+//   a   Phi_s, then A = L^-1 Phi_s L^-H (gev) or Phi_s itself (pca), then what the Jacobi rotations leave of it
+//   v   the accumulated rotations
+// Returns the sweeps done and leaves w in a[(2 c + part) L], c < C.  Every product is an explicit fma or stands alone, so the host and
+// the device build of this function round alike.
+#define BF_M(m, r, c, p) m[(((r) * C + (c)) * 2 + (p)) * L]
+
+// Cholesky of the lower triangle in place; false when a pivot is not > 0 (zero, indefinite, NaN).
+__host__ __device__ inline bool bf_cholesky(double* l, int C, int L) {
+    for (int j = 0; j < C; ++j) {
+        double d = BF_M(l, j, j, 0);
+        for (int k = 0; k < j; ++k) d = fma(-BF_M(l, j, k, 0), BF_M(l, j, k, 0), fma(-BF_M(l, j, k, 1), BF_M(l, j, k, 1), d));
+        if (!(d > 0.0)) return false;
+        const double dj = sqrt(d);
+        BF_M(l, j, j, 0) = dj;
+        BF_M(l, j, j, 1) = 0.0;
+        for (int i = j + 1; i < C; ++i) {
+            double sr = BF_M(l, i, j, 0), si = BF_M(l, i, j, 1);
+            for (int k = 0; k < j; ++k) {      // - L_ik conj(L_jk)
+                const double ar = BF_M(l, i, k, 0), ai = BF_M(l, i, k, 1), br = BF_M(l, j, k, 0), bi = BF_M(l, j, k, 1);
+                sr = fma(-ar, br, fma(-ai, bi, sr));
+                si = fma(-ai, br, fma(ar, bi, si));
+            }
+            BF_M(l, i, j, 0) = sr / dj;
+            BF_M(l, i, j, 1) = si / dj;
+        }
+    }
+    return true;
+}
+
+// a <- L^-1 a L^-H by two triangular solves (not an inverse).
+__host__ __device__ inline void bf_whiten(const double* l, double* a, int C, int L) {
+    for (int c = 0; c < C; ++c)                // X = L^-1 a, column by column
+        for (int i = 0; i < C; ++i) {
+            double sr = BF_M(a, i, c, 0), si = BF_M(a, i, c, 1);
+            for (int k = 0; k < i; ++k) {      // - L_ik X_kc
+                const double ar = BF_M(l, i, k, 0), ai = BF_M(l, i, k, 1), br = BF_M(a, k, c, 0), bi = BF_M(a, k, c, 1);
+                sr = fma(-ar, br, fma(ai, bi, sr));
+                si = fma(-ar, bi, fma(-ai, br, si));
+            }
+            const double d = BF_M(l, i, i, 0);
+            BF_M(a, i, c, 0) = sr / d;
+            BF_M(a, i, c, 1) = si / d;
+        }
+    for (int r = 0; r < C; ++r)                // A L^H = X, row by row
+        for (int j = 0; j < C; ++j) {
+            double sr = BF_M(a, r, j, 0), si = BF_M(a, r, j, 1);
+            for (int k = 0; k < j; ++k) {      // - A_rk conj(L_jk)
+                const double ar = BF_M(a, r, k, 0), ai = BF_M(a, r, k, 1), br = BF_M(l, j, k, 0), bi = BF_M(l, j, k, 1);
+                sr = fma(-ar, br, fma(-ai, bi, sr));
+                si = fma(-ai, br, fma(ar, bi, si));
+            }
+            const double d = BF_M(l, j, j, 0);
+            BF_M(a, r, j, 0) = sr / d;
+            BF_M(a, r, j, 1) = si / d;
+        }
+}
+
+// a <- (a + a^H) / 2: exactly Hermitian, a real diagonal (an exactly Hermitian a is left as it is).
+__host__ __device__ inline void bf_hermitian(double* a, int C, int L) {
+    for (int p = 0; p < C; ++p) {
+        BF_M(a, p, p, 1) = 0.0;
+        for (int q = p + 1; q < C; ++q) {
+            const double re = 0.5 * (BF_M(a, p, q, 0) + BF_M(a, q, p, 0)), im = 0.5 * (BF_M(a, p, q, 1) - BF_M(a, q, p, 1));
+            BF_M(a, p, q, 0) = re;
+            BF_M(a, p, q, 1) = im;
+            BF_M(a, q, p, 0) = re;
+            BF_M(a, q, p, 1) = -im;
+        }
+    }
+}
+
+// Cyclic complex Jacobi on the Hermitian a (pairs p < q in row order): a <- J^H a J, v <- v J with J_pp = J_qq = c, J_pq = s e,
+// J_qp = -s conj(e), e = a_pq / |a_pq|, t = s / c the smaller root of t^2 + 2 tau t - 1 = 0, tau = (a_qq - a_pp) / (2 |a_pq|).
+// Both triangles are written from the one new value, so a stays exactly Hermitian.  A sweep starts while
+// off(a)^2 = 2 sum_{p<q} |a_pq|^2 > (2^-52)^2 ||a||_F^2 (the norm is invariant: taken once), at most kBfMaxSweeps times.
+constexpr int kBfMaxSweeps = 16;
+
+__host__ __device__ inline int bf_jacobi(double* __restrict__ a, double* __restrict__ v, int C, int L, double fro2) {
+    for (int r = 0; r < C; ++r)
+        for (int c = 0; c < C; ++c) {
+            BF_M(v, r, c, 0) = r == c ? 1.0 : 0.0;
+            BF_M(v, r, c, 1) = 0.0;
+        }
+    const double limit = (DBL_EPSILON * DBL_EPSILON) * fro2;
+    int sweeps = 0;
+    for (; sweeps < kBfMaxSweeps; ++sweeps) {
+        double off2 = 0.0;
+        for (int p = 0; p < C; ++p)
+            for (int q = p + 1; q < C; ++q) off2 = fma(BF_M(a, p, q, 0), BF_M(a, p, q, 0), fma(BF_M(a, p, q, 1), BF_M(a, p, q, 1), off2));
+        if (2.0 * off2 <= limit) break;
+        for (int p = 0; p < C; ++p)
+            for (int q = p + 1; q < C; ++q) {
+                const double xr = BF_M(a, p, q, 0), xi = BF_M(a, p, q, 1), g = hypot(xr, xi);
+                if (!(g > 0.0)) continue;
+                const double ig = 1.0 / g, er = xr * ig, ei = xi * ig;      // (one division for e and tau: the chain is the kernel's time)
+                const double tau = (BF_M(a, q, q, 0) - BF_M(a, p, p, 0)) * (0.5 * ig);
+                const double t = (tau < 0.0 ? -1.0 : 1.0) / (fabs(tau) + sqrt(fma(tau, tau, 1.0)));
+                const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
+                const double sr = s * er, si = s * ei;      // s e
+                for (int k = 0; k < C; ++k) {
+                    // x_kp' = c x_kp - s conj(e) x_kq, x_kq' = s e x_kp + c x_kq for x = a (k != p, q; rows p, q: the conjugates) and
+                    // x = v.  All eight values are read before the first store: one LDS round trip a k, not four.
+                    const double pr = BF_M(a, k, p, 0), pi = BF_M(a, k, p, 1), qr = BF_M(a, k, q, 0), qi = BF_M(a, k, q, 1);
+                    const double ur = BF_M(v, k, p, 0), ui = BF_M(v, k, p, 1), wr = BF_M(v, k, q, 0), wi = BF_M(v, k, q, 1);
+                    if (k != p && k != q) {
+                        const double npr = fma(c, pr, fma(-sr, qr, -(si * qi))), npi = fma(c, pi, fma(-sr, qi, si * qr));
+                        const double nqr = fma(c, qr, fma(sr, pr, -(si * pi))), nqi = fma(c, qi, fma(sr, pi, si * pr));
+                        BF_M(a, k, p, 0) = npr;
+                        BF_M(a, k, p, 1) = npi;
+                        BF_M(a, p, k, 0) = npr;
+                        BF_M(a, p, k, 1) = -npi;
+                        BF_M(a, k, q, 0) = nqr;
+                        BF_M(a, k, q, 1) = nqi;
+                        BF_M(a, q, k, 0) = nqr;
+                        BF_M(a, q, k, 1) = -nqi;
+                    }
+                    BF_M(v, k, p, 0) = fma(c, ur, fma(-sr, wr, -(si * wi)));
+                    BF_M(v, k, p, 1) = fma(c, ui, fma(-sr, wi, si * wr));
+                    BF_M(v, k, q, 0) = fma(c, wr, fma(sr, ur, -(si * ui)));
+                    BF_M(v, k, q, 1) = fma(c, wi, fma(sr, ui, si * ur));
+                }
+                BF_M(a, p, p, 0) = fma(-t, g, BF_M(a, p, p, 0));
+                BF_M(a, q, q, 0) = fma(t, g, BF_M(a, q, q, 0));
+                BF_M(a, p, q, 0) = 0.0;
+                BF_M(a, p, q, 1) = 0.0;
+                BF_M(a, q, p, 0) = 0.0;
+                BF_M(a, q, p, 1) = 0.0;
+            }
+    }
+    return sweeps;
+}
+
+// gev != 0: l holds Phi_n and a Phi_s; else a holds the matrix whose principal eigenvector is wanted.  -> w in a[(2 c + part) L],
+// *lambda; returns the Jacobi sweeps.  A Cholesky pivot that is not > 0, or an all-zero a, gives w = 0 and lambda = 0.
+__host__ __device__ inline int bf_eig_bin(double* l, double* a, double* v, int C, int L, int gev, double* lambda) {
+    bool ok = !gev || bf_cholesky(l, C, L);
+    if (ok && gev) bf_whiten(l, a, C, L);
+    bf_hermitian(a, C, L);
+    double fro2 = 0.0;
+    for (int i = 0; i < 2 * C * C; ++i) fro2 = fma(a[i * L], a[i * L], fro2);
+    ok = ok && fro2 != 0.0;
+    int sweeps = 0, top = 0;
+    if (ok) {
+        sweeps = bf_jacobi(a, v, C, L, fro2);
+        for (int k = 1; k < C; ++k)
+            if (BF_M(a, k, k, 0) > BF_M(a, top, top, 0)) top = k;
+        *lambda = BF_M(a, top, top, 0);
+        if (gev)                                // w = L^-H v, in place in the column
+            for (int i = C - 1; i >= 0; --i) {
+                double sr = BF_M(v, i, top, 0), si = BF_M(v, i, top, 1);
+                for (int j = i + 1; j < C; ++j) {       // - conj(L_ji) w_j
+                    const double ar = BF_M(l, j, i, 0), ai = BF_M(l, j, i, 1), br = BF_M(v, j, top, 0), bi = BF_M(v, j, top, 1);
+                    sr = fma(-ar, br, fma(-ai, bi, sr));
+                    si = fma(-ar, bi, fma(ai, br, si));
+                }
+                const double d = BF_M(l, i, i, 0);
+                BF_M(v, i, top, 0) = sr / d;
+                BF_M(v, i, top, 1) = si / d;
+            }
+        int big = 0;                            // the gauge: the component of largest squared magnitude (first maximum) real, positive
+        double best = -1.0;
+        for (int i = 0; i < C; ++i) {
+            const double m = fma(BF_M(v, i, top, 0), BF_M(v, i, top, 0), BF_M(v, i, top, 1) * BF_M(v, i, top, 1));
+            if (m > best) {
+                best = m;
+                big = i;
+            }
+        }
+        const double h = hypot(BF_M(v, big, top, 0), BF_M(v, big, top, 1));
+        const double gr = BF_M(v, big, top, 0) / h, gi = BF_M(v, big, top, 1) / h;      // w <- w conj(g)
+        for (int i = 0; i < C; ++i) {
+            const double wr = BF_M(v, i, top, 0), wi = BF_M(v, i, top, 1);
+            a[(2 * i) * L] = i == big ? h : fma(wr, gr, wi * gi);
+            a[(2 * i + 1) * L] = i == big ? 0.0 : fma(wi, gr, -(wr * gi));
+        }
+    } else {
+        *lambda = 0.0;
+        for (int i = 0; i < 2 * C; ++i) a[i * L] = 0.0;
+    }
+    return sweeps;
+}
+#undef BF_M
+
+// Blind analytic normalisation of one bin: w <- w sqrt(|w^H Phi_n Phi_n w|) / max(|w^H Phi_n w|, DBL_MIN), on the stored complex64
+// vector, in fp64.  Explicit fmas only: the eigen kernel and the stand-alone kernel give the same bits.  The channel loops are
+// unrolled to kBfMaxChannels and guarded, so w and Phi_n w stay in registers.
+__device__ __forceinline__ void bf_ban_bin(float2 (&w)[kBfMaxChannels], const double* __restrict__ Pn, int C) {
+    double ur[kBfMaxChannels], ui[kBfMaxChannels];
+#pragma unroll
+    for (int d = 0; d < kBfMaxChannels; ++d) {
+        ur[d] = 0.0;
+        ui[d] = 0.0;
+#pragma unroll
+        for (int e = 0; e < kBfMaxChannels; ++e)
+            if (d < C && e < C) {
+                const double p0 = Pn[(d * C + e) * 2], p1 = Pn[(d * C + e) * 2 + 1], wr = (double)w[e].x, wi = (double)w[e].y;
+                ur[d] = fma(p0, wr, fma(-p1, wi, ur[d]));
+                ui[d] = fma(p0, wi, fma(p1, wr, ui[d]));
+            }
+    }
+    double nr = 0.0, ni = 0.0, dr = 0.0, di = 0.0;      // w^H (Phi_n u) and w^H u, u = Phi_n w
+#pragma unroll
+    for (int d = 0; d < kBfMaxChannels; ++d) {
+        double vr = 0.0, vi = 0.0;
+#pragma unroll
+        for (int e = 0; e < kBfMaxChannels; ++e)
+            if (d < C && e < C) {
+                const double p0 = Pn[(d * C + e) * 2], p1 = Pn[(d * C + e) * 2 + 1];
+                vr = fma(p0, ur[e], fma(-p1, ui[e], vr));
+                vi = fma(p0, ui[e], fma(p1, ur[e], vi));
+            }
+        if (d < C) {
+            const double wr = (double)w[d].x, wi = (double)w[d].y;
+            nr = fma(wr, vr, fma(wi, vi, nr));
+            ni = fma(wr, vi, fma(-wi, vr, ni));
+            dr = fma(wr, ur[d], fma(wi, ui[d], dr));
+            di = fma(wr, ui[d], fma(-wi, ur[d], di));
+        }
+    }
+    const double scale = sqrt(hypot(nr, ni)) / fmax(hypot(dr, di), DBL_MIN);
+#pragma unroll
+    for (int d = 0; d < kBfMaxChannels; ++d)
+        if (d < C) w[d] = make_float2((float)((double)w[d].x * scale), (float)((double)w[d].y * scale));
+}
+
+// One lane per (b, f) as in bf_souden_kernel, three matrices a lane: 768 C C bytes of LDS a workgroup of kBfEigLanes = 16 lanes,
+// 48 KiB at C = 8.  Why 16: the kernel is a chain of dependent fp64 and LDS operations per lane on a few hundred to a few thousand
+// bins, so its time is one lane's latency and what counts is how many CUs the bins reach: 513 bins make 33 workgroups on 33 CUs
+// (a full wave a workgroup: 9); three workgroups fit the 160 KiB of a CU at C = 8, and a row of 16 doubles covers 32 banks once.
+constexpr int kBfEigLanes = 16;
+
+__global__ __launch_bounds__(kBfEigLanes) void bf_eig_kernel(const double* __restrict__ ps, const double* __restrict__ pn,
+                                                             float2* __restrict__ w, double* __restrict__ lambda,
+                                                             int32_t* __restrict__ sweeps, long long BF, int C, int gev, int ban) {
+    extern __shared__ double sm[];
+    constexpr int L = kBfEigLanes;
+    const int lane = threadIdx.x;
+    const long long bin = (long long)blockIdx.x * L + lane;
+    if (bin >= BF) return;
+    const int CC = C * C;
+    double* l = sm + lane;
+    double* a = sm + 2 * CC * L + lane;
+    double* v = sm + 4 * CC * L + lane;
+    const double* Ps = ps + bin * CC * 2;
+    const double* Pn = pn ? pn + bin * CC * 2 : nullptr;
+    for (int i = 0; i < 2 * CC; ++i) {
+        a[i * L] = Ps[i];
+        if (gev) l[i * L] = Pn[i];
+    }
+    double lam;
+    const int n = bf_eig_bin(l, a, v, C, L, gev, &lam);
+    float2 wf[kBfMaxChannels];
+#pragma unroll
+    for (int c = 0; c < kBfMaxChannels; ++c)
+        wf[c] = c < C ? make_float2((float)a[(2 * c) * L], (float)a[(2 * c + 1) * L]) : make_float2(0.f, 0.f);
+    if (ban) bf_ban_bin(wf, Pn, C);             // Phi_n from global memory again: the factorisation has overwritten it
+#pragma unroll
+    for (int c = 0; c < kBfMaxChannels; ++c)
+        if (c < C) w[bin * C + c] = wf[c];
+    lambda[bin] = lam;
+    if (sweeps) sweeps[bin] = n;
+}
+
+// Grid ceil(B F / 256), 256 threads: a lane normalises one bin.
+__global__ __launch_bounds__(256) void bf_ban_kernel(const float2* __restrict__ w, const double* __restrict__ pn, float2* __restrict__ out,
+                                                     long long BF, int C) {
+    const long long bin = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (bin >= BF) return;
+    float2 wf[kBfMaxChannels];
+#pragma unroll
+    for (int c = 0; c < kBfMaxChannels; ++c) wf[c] = c < C ? w[bin * C + c] : make_float2(0.f, 0.f);
+    bf_ban_bin(wf, pn + bin * C * C * 2, C);
+#pragma unroll
+    for (int c = 0; c < kBfMaxChannels; ++c)
+        if (c < C) out[bin * C + c] = wf[c];
+}
+
+// ---- phase correction -----------------------------------------------------------------------------------------------------------------
+// w'_f = c_f w_f with c_0 = 1 and c_f = c_{f-1} conj(d_f / |d_f|), d_f = sum_c w_f,c conj(w_{f-1},c) on the stored vectors; a d_f that is
+// exactly zero STARTS AGAIN at c_f = 1 (the serial definition: the rotation is by arg 0 = 0 against a zero or orthogonal corrected
+// neighbour).  That is a segmented inclusive scan of unit phasors: an element is (restart, phasor), and
+//   (r1, p1) then (r2, p2)  =  r2 ? (1, p2) : (r1, p1 p2).
+// One workgroup per example, ONE fixed order for any F: thread x owns the K = ceil(F / 256) consecutive bins from x K, combines them
+// ascending, the 256 totals go through a Hillis-Steele scan in LDS (8 steps, distances 1, 2, .. 128, earlier operand on the left),
+// and the thread walks its bins again from the total of the threads before it.
+struct BfPhasor {
+    double re, im;
+    int restart;
+};
+
+__device__ __forceinline__ BfPhasor bf_then(const BfPhasor& x, const BfPhasor& y) {
+    if (y.restart) return y;
+    return BfPhasor{fma(x.re, y.re, -(x.im * y.im)), fma(x.re, y.im, x.im * y.re), x.restart};
+}
+
+// (restart, conj(d_f / |d_f|)) of bin f >= 1
+__device__ __forceinline__ BfPhasor bf_phasor(const float2* __restrict__ w, long long f, int C) {
+    double dr = 0.0, di = 0.0;
+    for (int c = 0; c < C; ++c) {               // w_f conj(w_{f-1})
+        const float2 x = w[f * C + c], y = w[(f - 1) * C + c];
+        dr = fma((double)x.x, (double)y.x, fma((double)x.y, (double)y.y, dr));
+        di = fma((double)x.y, (double)y.x, fma(-(double)x.x, (double)y.y, di));
+    }
+    if (dr == 0.0 && di == 0.0) return BfPhasor{1.0, 0.0, 1};
+    const double h = hypot(dr, di);
+    return BfPhasor{dr / h, -di / h, 0};
+}
+
+__global__ __launch_bounds__(256) void bf_phase_kernel(const float2* __restrict__ w_all, float2* __restrict__ out_all, long long F, int C) {
+    __shared__ double sre[2][256], sim[2][256];
+    __shared__ int srs[2][256];
+    const int x = threadIdx.x;
+    const float2* w = w_all + (long long)blockIdx.x * F * C;
+    float2* out = out_all + (long long)blockIdx.x * F * C;
+    const long long K = (F + 255) / 256, f0 = x * K, f1 = min(f0 + K, F);
+    BfPhasor tot{1.0, 0.0, 0};                  // bin 0 is (0, 1): c_0 = 1
+    for (long long f = max(f0, 1LL); f < f1; ++f) tot = bf_then(tot, bf_phasor(w, f, C));
+    int cur = 0;
+    sre[0][x] = tot.re;
+    sim[0][x] = tot.im;
+    srs[0][x] = tot.restart;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        BfPhasor me{sre[cur][x], sim[cur][x], srs[cur][x]};
+        if (x >= d) me = bf_then(BfPhasor{sre[cur][x - d], sim[cur][x - d], srs[cur][x - d]}, me);
+        cur ^= 1;
+        sre[cur][x] = me.re;
+        sim[cur][x] = me.im;
+        srs[cur][x] = me.restart;
+        __syncthreads();
+    }
+    BfPhasor run = x == 0 ? BfPhasor{1.0, 0.0, 0} : BfPhasor{sre[cur][x - 1], sim[cur][x - 1], srs[cur][x - 1]};
+    for (long long f = f0; f < f1; ++f) {
+        if (f >= 1) run = bf_then(run, bf_phasor(w, f, C));
+        for (int c = 0; c < C; ++c) {
+            const float2 v = w[f * C + c];
+            out[f * C + c] = make_float2((float)fma((double)v.x, run.re, -((double)v.y * run.im)),
+                                         (float)fma((double)v.x, run.im, (double)v.y * run.re));
+        }
+    }
+}
+
 // ---- apply --------------------------------------------------------------------------------------------------------------------------
 // Grid (nfb, ceil(T / 32), B), 256 threads: a lane holds its bin's C weights in registers, wave w takes frames t0 + w, t0 + w + 4, ...;
 // 8-byte loads and stores, 512 contiguous bytes per wave and row.
@@ -458,6 +808,39 @@ int ptmi_bf_souden(const double* psd_target, const double* psd_noise, int64_t B,
     if (rc) return rc;
     hipLaunchKernelGGL(bf_pick_kernel, dim3((unsigned)B), dim3(256), 0, st, numden, reinterpret_cast<const float2*>(w_all),
                        reinterpret_cast<float2*>(w), ref_out, (long long)F, C, ref_channel);
+    return launch_status();
+}
+
+int ptmi_bf_eig(const double* psd_target, const double* psd_noise, int64_t B, int64_t F, int32_t C, int32_t mode, int32_t ban, float* w,
+                double* lambda, int32_t* sweeps, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!psd_target || !w || !lambda || mode < 0 || mode > 1, PTMI_E_INVALID);
+    PTMI_RETURN_IF((mode == 0 || ban) && !psd_noise, PTMI_E_INVALID);
+    PTMI_RETURN_IF(B < 1 || F < 1 || C < 1, PTMI_E_INVALID);
+    PTMI_RETURN_IF(C > kBfMaxChannels || B > 2147483647LL || B * F > 2147483647LL * kBfEigLanes, PTMI_E_UNSUPPORTED);
+    const long long BF = B * F;
+    const size_t lds = (size_t)6 * C * C * kBfEigLanes * sizeof(double);
+    hipLaunchKernelGGL(bf_eig_kernel, dim3((unsigned)((BF + kBfEigLanes - 1) / kBfEigLanes)), dim3(kBfEigLanes), lds,
+                       static_cast<hipStream_t>(stream), psd_target, psd_noise, reinterpret_cast<float2*>(w), lambda, sweeps, BF, C,
+                       mode == 0, ban != 0);
+    return launch_status();
+}
+
+int ptmi_bf_ban(const float* w, const double* psd_noise, int64_t B, int64_t F, int32_t C, float* out, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!w || !psd_noise || !out, PTMI_E_INVALID);
+    PTMI_RETURN_IF(B < 1 || F < 1 || C < 1, PTMI_E_INVALID);
+    PTMI_RETURN_IF(C > kBfMaxChannels || B > 2147483647LL || B * F > 2147483647LL * 256, PTMI_E_UNSUPPORTED);
+    const long long BF = B * F;
+    hipLaunchKernelGGL(bf_ban_kernel, dim3((unsigned)((BF + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const float2*>(w), psd_noise, reinterpret_cast<float2*>(out), BF, C);
+    return launch_status();
+}
+
+int ptmi_bf_phase(const float* w, int64_t B, int64_t F, int32_t C, float* out, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!w || !out, PTMI_E_INVALID);
+    PTMI_RETURN_IF(B < 1 || F < 1 || C < 1, PTMI_E_INVALID);
+    PTMI_RETURN_IF(C > kBfMaxChannels || B > 2147483647LL, PTMI_E_UNSUPPORTED);
+    hipLaunchKernelGGL(bf_phase_kernel, dim3((unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const float2*>(w), reinterpret_cast<float2*>(out), (long long)F, C);
     return launch_status();
 }
 

@@ -1,4 +1,5 @@
-"""Mask-based MVDR beamforming on the HIP kernels of ``csrc/beamform.hip``: what a speech and a noise mask are estimated for
+"""Mask-based beamforming (Souden MVDR, GEV and PCA vectors, blind analytic normalization, phase correction) on the HIP kernels of
+``csrc/beamform.hip``: what a speech and a noise mask are estimated for
 (``padertorch/contrib/examples/speech_enhancement/mask_estimator/evaluate.py:110-137``, ``contrib/jensheit/evaluation.py:14-45``).
 The reference does this on the host with the third-party ``pb_bss`` / ``paderbox``; the functions here restate their documented
 behaviour in the layout ``ops.STFT`` and the estimators produce, and nothing leaves the device.
@@ -23,9 +24,35 @@ behaviour in the layout ``ops.STFT`` and the estimators produce, and nothing lea
         elimination gives.
     apply_beamforming_vector(vector, mix, *, frames=None)
         ``Z[b,t,f] = sum_c conj(vector[b,f,c]) mix[b,c,t,f]`` -> ``[B, T, F]`` complex64
-    mask_beamforming(observation, speech_mask, noise_mask, *, frames=None, ref_channel=None)
-        the three together -> ``Z [B, T, F]``: both PSD matrices from ONE pass over the observation, three launches plus the
-        reference-channel stage.
+    get_gev_vector(target_psd_matrix, noise_psd_matrix, *, return_eigenvalue=False)
+        the principal generalized eigenvector of ``(Phi_s, Phi_n)`` per bin (``pb_bss.extraction.get_bf_vector('gev', ...)``), all in
+        float64: Cholesky ``Phi_n = L L^H``; ``A = L^-1 Phi_s L^-H`` by two triangular solves (no inverse), made exactly Hermitian
+        (``(A + A^H) / 2``); cyclic complex Jacobi on ``A``, a sweep while ``off(A)^2 > (2^-52)^2 ||A||_F^2``, at most 16 sweeps;
+        ``v`` the eigenvector of the largest eigenvalue ``lambda`` (first maximum); ``w = L^-H v``, so ``w^H Phi_n w = 1``
+        (``scipy.linalg.eigh(a, b)``'s normalisation) -> ``[B, F, C]`` complex64.  Gauge: ``w`` is rotated so that its component of
+        largest squared magnitude (first maximum, compared in float64) is real and positive.  A bin whose Cholesky meets a pivot that
+        is not ``> 0`` (a zero or indefinite ``Phi_n``, NaN) gives ``w = 0`` and ``lambda = 0`` - the Souden kernel's "all-zero
+        ``Phi_n`` gives a zero output" - and so does an all-zero ``Phi_s``.  ``return_eigenvalue`` also returns ``lambda`` as
+        ``[B, F]`` float64.
+    get_pca_vector(target_psd_matrix, *, return_eigenvalue=False)
+        the same Jacobi on ``Phi_s`` alone: the principal eigenvector with unit 2-norm, same gauge; an all-zero matrix gives ``w = 0``.
+    blind_analytic_normalization(vector, noise_psd_matrix)
+        ``w sqrt(|w^H Phi_n Phi_n w|) / max(|w^H Phi_n w|, tiny)`` in float64 on the complex64 vector; a zero vector stays zero.
+    phase_correction(vector)
+        per example, for ``f = 1 .. F-1`` in order: ``w'_f = w_f exp(-i arg(sum_c w_f,c conj(w'_{f-1},c)))``; a sum that is exactly
+        zero rotates by nothing.  Every step is a unit rotation, ``w'_f = c_f w_f`` with ``c_0 = 1``,
+        ``c_f = c_{f-1} conj(d_f / |d_f|)`` and ``d_f = sum_c w_f,c conj(w_{f-1},c)`` on the uncorrected vectors (``c_f = 1`` where
+        ``d_f = 0``): the kernel computes the ``c_f`` as a parallel scan of float64 phasors in one fixed order (two runs agree bit
+        for bit).  It is defined on the stored complex64 vector, so this function and ``mask_beamforming`` give the same bits.
+    get_bf_vector(beamformer, target_psd_matrix, noise_psd_matrix, *, ref_channel=None)
+        ``pb_bss.extraction.get_bf_vector``: ``beamformer`` one of ``BEAMFORMERS`` (``'mvdr_souden'``, ``'gev'``, ``'pca'``, each
+        optionally with ``'+ban'``: the vector goes through ``blind_analytic_normalization``); ``ref_channel`` is for
+        ``mvdr_souden`` only; any other name raises ``ValueError``.  No phase correction, as upstream.
+    mask_beamforming(observation, speech_mask, noise_mask, *, frames=None, ref_channel=None, beamformer='mvdr_souden')
+        PSD matrices, vector and application together -> ``Z [B, T, F]``: both PSD matrices from ONE pass over the observation, then
+        for ``mvdr_souden`` the solve and the reference-channel stage, for ``gev*`` / ``pca*`` ONE eigen launch (BAN inside) and
+        one ``phase_correction`` launch - without it the phase of every bin is the gauge's artefact and the iSTFT of the output
+        means nothing -, then the apply pass.
 
 Inference only: an input that requires grad raises.  complex64 / float32 (PSD matrices complex128) on the GPU only: other dtypes
 raise ``NotImplementedError``, CPU tensors the "no CPU fallback" error; more than 8 channels raise ``NotImplementedError``.
@@ -36,6 +63,7 @@ from .. import _lib
 from . import library  # noqa: F401  (registers torch.ops.ptmi.*)
 
 __all__ = ['get_power_spectral_density_matrix', 'get_mvdr_vector_souden', 'apply_beamforming_vector', 'mask_beamforming',
+           'get_gev_vector', 'get_pca_vector', 'blind_analytic_normalization', 'phase_correction', 'get_bf_vector', 'BEAMFORMERS',
            'MAX_CHANNELS']
 
 #: the kernels keep a bin's C (C + 1) / 2 products per mask in registers
@@ -143,10 +171,106 @@ def apply_beamforming_vector(vector, mix, *, frames=None):
     return Z[0] if squeeze else Z
 
 
-def beamforming_vector(observation, speech_mask, noise_mask, *, frames=None, ref_channel=None, channel_reduce='median'):
-    """The Souden MVDR vector of ``mask_beamforming``: both PSD matrices from one ``bf_psd`` launch -> ``(w [B, F, C], Y, frames,
-    squeeze)`` with the checked, batched (``[B, C, T, F]``) observation ``Y`` and whether the batch axis was added."""
+BEAMFORMERS = ('mvdr_souden', 'gev', 'pca', 'mvdr_souden+ban', 'gev+ban', 'pca+ban')
+
+
+def parse_beamformer(name, beamformer, ref_channel=None):
+    """``'gev+ban'`` -> ``('gev', True)``; any name but ``BEAMFORMERS`` raises, and so does a reference channel for another vector
+    than the Souden one."""
+    if beamformer not in BEAMFORMERS:
+        raise ValueError(f'{name}: beamformer one of {", ".join(map(repr, BEAMFORMERS))}, got {beamformer!r}')
+    kind, _, ban = beamformer.partition('+')
+    if kind != 'mvdr_souden' and ref_channel is not None:
+        raise ValueError(f'{name}: ref_channel is for mvdr_souden only, got {ref_channel} for {beamformer!r}')
+    return kind, bool(ban)
+
+
+def _psd_matrices(name, *matrices):
+    """Checked ``[B, F, C, C]`` or ``[F, C, C]`` complex128 matrices of one shape -> contiguous ``[B, F, C, C]`` ones and whether the
+    batch axis was added."""
+    _check(name, (torch.complex128,) * len(matrices), *matrices)
+    s = matrices[0]
+    if s.dim() not in (3, 4) or any(m.shape != s.shape for m in matrices) or s.shape[-1] != s.shape[-2] or s.numel() == 0:
+        raise ValueError(f'{name}: [B, F, C, C] or [F, C, C] matrices of one shape, got '
+                         + ', '.join(str(tuple(m.shape)) for m in matrices))
+    _channels(name, s.shape[-1])
+    squeeze = s.dim() == 3
+    return [(m[None] if squeeze else m).contiguous() for m in matrices], squeeze
+
+
+def _vector(name, vector, psd=None):
+    """A checked ``[B, F, C]`` or ``[F, C]`` complex64 vector (for the matrices ``psd``, when given) -> contiguous ``[B, F, C]`` and
+    whether the batch axis was added."""
+    if vector.dim() not in (2, 3) or vector.numel() == 0:
+        raise ValueError(f'{name}: a vector [B, F, C] or [F, C], got {tuple(vector.shape)}')
+    _channels(name, vector.shape[-1])
+    if psd is not None and tuple(psd.shape) != (*vector.shape, vector.shape[-1]):
+        raise ValueError(f'{name}: a noise PSD matrix {(*vector.shape, vector.shape[-1])} for this vector, got {tuple(psd.shape)}')
+    squeeze = vector.dim() == 2
+    return (vector[None] if squeeze else vector).contiguous(), squeeze
+
+
+def _eig(name, target, noise, gev, ban, return_eigenvalue):
+    matrices, squeeze = _psd_matrices(name, *(m for m in (target, noise) if m is not None))
+    _lib.require_gpu(*matrices)
+    w, lam, _ = torch.ops.ptmi.bf_eig(matrices[0], matrices[1] if noise is not None else None, gev, ban)
+    w, lam = (w[0], lam[0]) if squeeze else (w, lam)
+    return (w, lam) if return_eigenvalue else w
+
+
+def get_gev_vector(target_psd_matrix, noise_psd_matrix, *, return_eigenvalue=False):
+    return _eig('get_gev_vector', target_psd_matrix, noise_psd_matrix, True, False, return_eigenvalue)
+
+
+def get_pca_vector(target_psd_matrix, *, return_eigenvalue=False):
+    return _eig('get_pca_vector', target_psd_matrix, None, False, False, return_eigenvalue)
+
+
+def blind_analytic_normalization(vector, noise_psd_matrix):
+    name = 'blind_analytic_normalization'
+    _check(name, (torch.complex64, torch.complex128), vector, noise_psd_matrix)
+    w, squeeze = _vector(name, vector, noise_psd_matrix)
+    _lib.require_gpu(w, noise_psd_matrix)
+    out = torch.ops.ptmi.bf_ban(w, (noise_psd_matrix[None] if squeeze else noise_psd_matrix).contiguous())
+    return out[0] if squeeze else out
+
+
+def phase_correction(vector):
+    name = 'phase_correction'
+    _check(name, (torch.complex64,), vector)
+    w, squeeze = _vector(name, vector)
+    _lib.require_gpu(w)
+    out = torch.ops.ptmi.bf_phase(w)
+    return out[0] if squeeze else out
+
+
+def _bf_vector(kind, ban, target, noise, ref_channel):
+    """The vector of a checked, batched pair of PSD matrices: one launch for ``gev`` / ``pca`` (BAN inside), the Souden stages and
+    the stand-alone BAN launch for ``mvdr_souden``."""
+    if kind == 'mvdr_souden':
+        w, _, _ = torch.ops.ptmi.bf_souden(target, noise, -1 if ref_channel is None else int(ref_channel))
+        return torch.ops.ptmi.bf_ban(w, noise) if ban else w
+    return torch.ops.ptmi.bf_eig(target, noise if kind == 'gev' or ban else None, kind == 'gev', ban)[0]
+
+
+def get_bf_vector(beamformer, target_psd_matrix, noise_psd_matrix, *, ref_channel=None):
+    name = 'get_bf_vector'
+    kind, ban = parse_beamformer(name, beamformer, ref_channel)
+    (s, n), squeeze = _psd_matrices(name, target_psd_matrix, noise_psd_matrix)
+    if ref_channel is not None and not 0 <= int(ref_channel) < s.shape[-1]:
+        raise ValueError(f'{name}: ref_channel in [0, {s.shape[-1]}), got {ref_channel}')
+    _lib.require_gpu(s, n)
+    w = _bf_vector(kind, ban, s, n, ref_channel)
+    return w[0] if squeeze else w
+
+
+def beamforming_vector(observation, speech_mask, noise_mask, *, frames=None, ref_channel=None, channel_reduce='median',
+                       beamformer='mvdr_souden'):
+    """The vector of ``mask_beamforming`` WITHOUT the phase correction: both PSD matrices from one ``bf_psd`` launch ->
+    ``(w [B, F, C], Y, frames, squeeze)`` with the checked, batched (``[B, C, T, F]``) observation ``Y`` and whether the batch axis
+    was added."""
     name = 'mask_beamforming'
+    kind, ban = parse_beamformer(name, beamformer, ref_channel)
     reduce = _reduce_flag(name, channel_reduce)
     _check(name, (torch.complex64, torch.float32, torch.float32), observation, speech_mask, noise_mask)
     Y, squeeze = _spectrum(name, observation)
@@ -159,11 +283,13 @@ def beamforming_vector(observation, speech_mask, noise_mask, *, frames=None, ref
     frames = _frames(name, frames, Y.shape[0])
     _lib.require_gpu(Y, speech_mask, noise_mask, frames)
     psd = torch.ops.ptmi.bf_psd(Y, speech_mask, noise_mask, frames, True)
-    w, _, _ = torch.ops.ptmi.bf_souden(psd[0], psd[1], -1 if ref_channel is None else int(ref_channel))
-    return w, Y, frames, squeeze
+    return _bf_vector(kind, ban, psd[0], psd[1], ref_channel), Y, frames, squeeze
 
 
-def mask_beamforming(observation, speech_mask, noise_mask, *, frames=None, ref_channel=None):
-    w, Y, frames, squeeze = beamforming_vector(observation, speech_mask, noise_mask, frames=frames, ref_channel=ref_channel)
+def mask_beamforming(observation, speech_mask, noise_mask, *, frames=None, ref_channel=None, beamformer='mvdr_souden'):
+    w, Y, frames, squeeze = beamforming_vector(observation, speech_mask, noise_mask, frames=frames, ref_channel=ref_channel,
+                                               beamformer=beamformer)
+    if not beamformer.startswith('mvdr_souden'):
+        w = torch.ops.ptmi.bf_phase(w)
     Z = torch.ops.ptmi.bf_apply(w, Y, frames)
     return Z[0] if squeeze else Z

@@ -31,7 +31,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.orpit_flag_forward / _backward  ptmi_orpit_flag_*          (or_pit/model.py:187-218)
     torch.ops.ptmi.dprnn_tables / chunk_lstm_forward / chunk_lstm_backward / dprnn_colsum / dprnn_colsum_pair / dprnn_norm_residual_forward / _backward /
     torch.ops.ptmi.dprnn_segment / dprnn_overlap_add   ptmi_dprnn_*, ptmi_chunk_lstm_*   (modules/dual_path_rnn.py)
-    torch.ops.ptmi.bf_psd / bf_souden / bf_apply   ptmi_bf_*                  (mask_estimator/evaluate.py:110-137, jensheit/evaluation.py:14-45)
+    torch.ops.ptmi.bf_psd / bf_souden / bf_apply / bf_eig / bf_ban / bf_phase   ptmi_bf_*   (mask_estimator/evaluate.py:110-137,
+                                                                              jensheit/evaluation.py:14-45)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -633,6 +634,55 @@ def bf_apply(vector, mix, frames):
     out = torch.empty((B, T, F), dtype=torch.complex64, device=mix.device)
     _lib.check(_lib.timed('bf_apply', _lib.load().ptmi_bf_apply, vector.data_ptr(), mix.data_ptr(), _bf_frames(frames, B), B, C, T, F,
                           out.data_ptr(), _lib.stream(mix.device)), 'ptmi_bf_apply')
+    return out
+
+
+def _bf_vector(vector):
+    """``[B, F, C]`` complex64, contiguous -> its ``(B, F, C)``."""
+    assert vector.dim() == 3 and vector.dtype == torch.complex64 and vector.is_contiguous(), (vector.shape, vector.dtype)
+    return vector.shape
+
+
+@_register('bf_eig(Tensor target_psd, Tensor? noise_psd, bool gev, bool ban) -> (Tensor, Tensor, Tensor)')
+def bf_eig(target_psd, noise_psd, gev, ban):
+    """``[B, F, C, C]`` complex128 PSD matrices -> ``(w [B, F, C] complex64, lambda [B, F] float64, sweeps [B, F] int32)``: the
+    principal generalized eigenvector of ``(target, noise)`` (``gev``) or the principal eigenvector of ``target``, blind analytic
+    normalization with ``noise`` included when ``ban`` (``ptmi_bf_eig``)."""
+    assert noise_psd is not None or not (gev or ban)
+    for p in (target_psd, noise_psd):
+        assert p is None or (p.dim() == 4 and p.dtype == torch.complex128 and p.is_contiguous() and p.shape == target_psd.shape), \
+            (p.shape, p.dtype)
+    B, F, C, _ = target_psd.shape
+    assert target_psd.shape[3] == C, target_psd.shape
+    dev = target_psd.device
+    w = torch.empty((B, F, C), dtype=torch.complex64, device=dev)
+    lam = torch.empty((B, F), dtype=torch.float64, device=dev)
+    sweeps = torch.empty((B, F), dtype=torch.int32, device=dev)
+    _lib.check(_lib.timed('bf_eig', _lib.load().ptmi_bf_eig, target_psd.data_ptr(), _lib.ptr(noise_psd), B, F, C, 0 if gev else 1,
+                          int(ban), w.data_ptr(), lam.data_ptr(), sweeps.data_ptr(), _lib.stream(dev)), 'ptmi_bf_eig')
+    return w, lam, sweeps
+
+
+@_register('bf_ban(Tensor vector, Tensor noise_psd) -> Tensor')
+def bf_ban(vector, noise_psd):
+    """``vector [B, F, C]`` complex64, ``noise_psd [B, F, C, C]`` complex128 -> the blind analytic normalization of the vector
+    (``ptmi_bf_ban``)."""
+    B, F, C = _bf_vector(vector)
+    assert noise_psd.shape == (B, F, C, C) and noise_psd.dtype == torch.complex128 and noise_psd.is_contiguous(), \
+        (noise_psd.shape, noise_psd.dtype)
+    out = torch.empty_like(vector)
+    _lib.check(_lib.timed('bf_ban', _lib.load().ptmi_bf_ban, vector.data_ptr(), noise_psd.data_ptr(), B, F, C, out.data_ptr(),
+                          _lib.stream(vector.device)), 'ptmi_bf_ban')
+    return out
+
+
+@_register('bf_phase(Tensor vector) -> Tensor')
+def bf_phase(vector):
+    """``vector [B, F, C]`` complex64 -> the vector with the phase of every bin aligned to the bin before it (``ptmi_bf_phase``)."""
+    B, F, C = _bf_vector(vector)
+    out = torch.empty_like(vector)
+    _lib.check(_lib.timed('bf_phase', _lib.load().ptmi_bf_phase, vector.data_ptr(), B, F, C, out.data_ptr(),
+                          _lib.stream(vector.device)), 'ptmi_bf_phase')
     return out
 
 

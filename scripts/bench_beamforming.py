@@ -6,9 +6,12 @@
                    kernel), its partial-sum stage included;
   * ``bf_souden``  the solve per bin and the reference-channel stage (``ref_channel=None``);
   * ``bf_apply``   the vector applied to the observation;
-  * ``mask_beamforming``  the three together, as ``SimpleMaskEstimator.enhance`` calls them.
+  * ``mask_beamforming``  the three together, as ``SimpleMaskEstimator.enhance`` calls them;
+  * ``bf_eig gev+ban`` / ``bf_eig pca``  the eigen launch alone, ``bf_phase`` the phase correction alone, and
+    ``mask_beamforming gev+ban`` / ``mask_beamforming pca`` the chains beside the Souden chain of the same run; ``sweeps``: how many
+    bins took how many Jacobi sweeps.  The eigen and phase kernels are latency-bound fp64 on ``B F`` bins: times only.
 
-For every entry: the time per call and the algorithmic bytes (what the operation has to read and write once: inputs and outputs, no
+For every other entry: the time per call and the algorithmic bytes (what the operation has to read and write once: inputs and outputs, no
 workspace) over that time, as GB/s and as a fraction of the MI355X's 8 TB/s peak HBM bandwidth (a streaming copy reaches about 0.79
 of it).
 
@@ -86,6 +89,14 @@ def main():
             'bf_apply': (lambda i: torch.ops.ptmi.bf_apply(w[i % copies], Y[i % copies], None), n * 8 + B * T * F * 8 + B * F * C * 8),
             'mask_beamforming': (lambda i: ops.mask_beamforming(Y[i % copies], speech[i % copies], noise[i % copies]),
                                  in_bytes + n * 8 + B * T * F * 8),
+            # latency- and LDS-bound fp64 on B F bins (no bytes: a share of the HBM peak would say nothing about them)
+            'bf_eig gev+ban': (lambda i: torch.ops.ptmi.bf_eig(psd[i % copies][0], psd[i % copies][1], True, True), None),
+            'bf_eig pca': (lambda i: torch.ops.ptmi.bf_eig(psd[i % copies][0], None, False, False), None),
+            'bf_phase': (lambda i: torch.ops.ptmi.bf_phase(w[i % copies]), None),
+            'mask_beamforming gev+ban': (lambda i: ops.mask_beamforming(Y[i % copies], speech[i % copies], noise[i % copies],
+                                                                        beamformer='gev+ban'), in_bytes + n * 8 + B * T * F * 8),
+            'mask_beamforming pca': (lambda i: ops.mask_beamforming(Y[i % copies], speech[i % copies], noise[i % copies],
+                                                                    beamformer='pca'), in_bytes + n * 8 + B * T * F * 8),
         }
         graphs = {k: graph_of(fn, args.reps) for k, (fn, _) in series.items()}
         for graph, _ in graphs.values():
@@ -100,8 +111,12 @@ def main():
                         f'({copies * in_bytes / 1e6:.0f} MB)')
         for k, (_, nbytes) in series.items():
             us = statistics.median(times[k])
-            res[k] = dict(median_us=round(us, 2), min_us=round(min(times[k]), 2), max_us=round(max(times[k]), 2), bytes=nbytes,
-                          gb_per_s=round(nbytes / us / 1e3, 1), hbm_fraction=round(nbytes / us / 1e3 / HBM_GBS, 4))
+            res[k] = dict(median_us=round(us, 2), min_us=round(min(times[k]), 2), max_us=round(max(times[k]), 2))
+            if nbytes is not None:
+                res[k].update(bytes=nbytes, gb_per_s=round(nbytes / us / 1e3, 1), hbm_fraction=round(nbytes / us / 1e3 / HBM_GBS, 4))
+        for k, gev in (('gev', True), ('pca', False)):                    # the Jacobi sweeps the bins of the first input copy took
+            sweeps = torch.ops.ptmi.bf_eig(psd[0][0], psd[0][1], gev, False)[2].flatten().tolist()
+            res[f'sweeps {k}'] = {str(s): sweeps.count(s) for s in sorted(set(sweeps))}
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
         del graphs
