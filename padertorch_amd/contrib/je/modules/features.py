@@ -165,6 +165,37 @@ class MelTransform(nn.Module):
         return torch.max(x, torch.zeros_like(x))
 
 
+#: STFT size -> (R1, R2) of its FFT plan (csrc/stft.hip, dispatch_fwd)
+_PLANS = {64: (4, 8), 128: (8, 8), 256: (8, 16), 512: (16, 16), 1024: (16, 32), 2048: (32, 32)}
+_LDS_LIMIT = 160 * 1024
+
+
+def _plan_lds_bytes(stft_size):
+    """LDS of the forward kernel's own buffers at a plan size (csrc/stft.hip, ``WaveLds<Plan<R1, R2>>::bytes(4, 0)``)."""
+    r1, r2 = _PLANS[stft_size]
+    m = r1 * r2
+    f, lpf = m + 1, max(r1, r2)
+    fpw = 64 // lpf
+    fs = (max(r1 * (r2 + 1), f) + 1) & ~1
+    return 8 * (f + 1 + r1 * lpf + 4 * fpw * fs) + 4 * stft_size
+
+
+def _logmel_unsupported(stft_size, mel_M, mel_nnz):
+    """The error behind ``PTMI_E_UNSUPPORTED`` of ``ptmi_stft_logmel``: a size without an FFT plan; at a size that has one, a
+    filterbank whose band-compressed weights do not fit the workgroup's LDS next to the plan's own buffers (said only when the
+    bytes really exceed the limit); otherwise one of the launcher's index limits."""
+    if stft_size not in _PLANS:
+        return NotImplementedError(f'stft_logmel needs a power-of-two STFT size in 64..2048 (got {stft_size})')
+    plan, bank = _plan_lds_bytes(stft_size), 16 + 12 * mel_M + 4 * mel_nnz
+    if plan + bank > _LDS_LIMIT:
+        return NotImplementedError(
+            f'stft_logmel: the filterbank ({mel_M} filters, {mel_nnz} band-compressed weights: {bank} bytes) does not fit into the '
+            f'{_LDS_LIMIT} bytes of LDS of a workgroup next to the {plan} bytes of the STFT size {stft_size} plan')
+    return NotImplementedError(
+        f'stft_logmel: the batch is beyond the index range of the STFT size {stft_size} kernel (rows of more than 0x7ff00000 samples, '
+        f'more than 0x7ff00000 / (size + 2) frames per row, or more than 2^31 - 1 groups of frames in all); split it')
+
+
 def stft_logmel(x, stft: STFT, mel: MelTransform, num_samples=None, power: int = 2):
     """Waveforms ``[..., N]`` -> (log-)mel spectrogram ``[..., frames, M]`` in ONE kernel.
 
@@ -195,6 +226,6 @@ def stft_logmel(x, stft: STFT, mel: MelTransform, num_samples=None, power: int =
         mb['cnt'].data_ptr(), mb['off'].data_ptr(), mb['w'].data_ptr(), mel._bands.M, mel._bands.nnz, power,
         int(bool(mel.log)), float(mel.eps), out.data_ptr(), _lib.stream(dev))
     if rc == -2:
-        raise NotImplementedError(f'stft_logmel needs a power-of-two STFT size in 64..2048 (got {stft.size})')
+        raise _logmel_unsupported(stft.size, mel._bands.M, mel._bands.nnz)
     _lib.check(rc, 'ptmi_stft_logmel')
     return out.reshape(*lead, frames, mel._bands.M)

@@ -1204,6 +1204,8 @@ static int blocks_per_cu(int threads, size_t smem) {
 
 template <class PL>
 static int launch_fwd(FwdArgs& A, long long batch, bool features, hipStream_t st) {
+    // read at EVERY launch, by the plan kernels only: tests/test_gpu_spectral_gates.py (test_size_2048_forward_runs_its_plan) tells
+    // a plan kernel from the direct-DFT fallback by flipping bit 2 between two calls - do not cache it
     const char* dbg_env = getenv("PTMI_STFT_DBG");
     A.dbg = dbg_env ? atoi(dbg_env) : 0;
     A.aligned2 = (A.x_row_stride % 2 == 0) && (A.g.shift % 2 == 0) && (A.g.pad_left % 2 == 0) &&
@@ -1212,12 +1214,18 @@ static int launch_fwd(FwdArgs& A, long long batch, bool features, hipStream_t st
     if (!features) {
         const bool mel = A.mel_w != nullptr;
         const size_t smem = WaveLds<PL>::bytes(4, 0) + (mel ? 16 + sizeof(int32_t) * 3 * A.mel_M + sizeof(float) * A.mel_nnz : 0);
-        if (smem > kMaxSmem) return PTMI_E_UNSUPPORTED;
+        if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
         A.batch = batch;
         A.nchunks = (int)((A.out_frames + PL::FPW - 1) / PL::FPW);      // work items per row
         const long long items = batch * A.nchunks;
         if (items <= 0) return PTMI_OK;
         if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
+        if (smem > kMaxSmem) {   // the 2048-point plan (92 KB) and large filterbanks: opt in like the features branch and launch_inv
+            const void* fn = mel ? reinterpret_cast<const void*>(stft_fwd_kernel<PL, true>)
+                                 : reinterpret_cast<const void*>(stft_fwd_kernel<PL, false>);
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            if (e != hipSuccess) return (int)e;
+        }
         // persistent grid: as many workgroups as stay resident (LDS bound), never more than needed
         if (mel) {
             const long long resident = 256LL * blocks_per_cu<stft_fwd_kernel<PL, true>>(256, smem);
