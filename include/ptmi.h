@@ -620,6 +620,34 @@ int ptmi_orpit_flag_backward(const float* gflag, const float* gpre, const float*
                              float* dparams, float* dmask, float* dencoded, double* workspace, int64_t B, int32_t A, int64_t E, int32_t N,
                              int32_t K, int32_t k, int32_t weighted, ptmi_stream_t stream);
 
+/* ---- Mask estimator loss: pooled and power-weighted BCE on logits -------------------------------------
+ * Replaces, in padertorch/contrib/jensheit/mask_estimator_example/model.py, the per-example loop of add_losses (:128-237:
+ * binary_cross_entropy_with_logits(reduction='none'), TORCH_POOLING_FN_MAP[reduction], weight_loss) for one mask of the whole
+ * padded batch, forward and backward.  fp32 data, fp64 sums in one fixed order through per-workgroup partials in the caller's
+ * workspace (no floating-point atomics; the histograms of the selection count with integer atomics); bit-reproducible; no
+ * allocation, no synchronisation (capturable).  B <= 65535, C T F < 2^31.
+ *
+ * logits, target: logical [B, C, T, F], unit stride on F; strides[9] = {logits b, c, t, target b, c, t, power b, c, t} in elements
+ *   (HOST array; a complex power counts complex elements).  num_frames: device int32 [B] or NULL (all T frames); only frames
+ *   t < num_frames[b] (clamped to [0, T]) are read.  power_kind: 0 none, 1 real weights float32 [B, C, T, F], 2 complex64
+ *   [B, C, T, F] (the weight is re^2 + im^2).  reduction: 0 mean, 1 median (torch's lower median: rank (n - 1) / 2), 2 min, 3 max.
+ * Element loss l = max(x, 0) - x t + log1p(exp(-|x|)).
+ * ptmi_mask_loss_forward : pooled [B] (a NaN element makes it NaN), weighted [B] = sum l w / sum w (power given; else may be NULL),
+ *   and for the backward pass stat [B, 4] float64 = (sum l, sum l w, sum w, n) and sel [B, 2] int32 = (order-preserving key of the
+ *   pooled element, number m of elements with that key; zeros for the mean).
+ *   workspace: ptmi_mask_loss_workspace_elems(B, C, T, F) float64.
+ * ptmi_mask_loss_backward: dlogits [B, C, T, F] dense = (g_pooled[b] / n (mean) or g_pooled[b] / m on the elements whose loss has
+ *   the pooled key (median, min, max), + g_weighted[b] w / sum w) (sigmoid(x) - t); exact zeros behind num_frames[b].  g_pooled and
+ *   g_weighted [B] may each be NULL (= 0). */
+int64_t ptmi_mask_loss_workspace_elems(int64_t B, int32_t C, int32_t T, int32_t F);
+int ptmi_mask_loss_forward(const float* logits, const float* target, const void* power, int32_t power_kind, const int32_t* num_frames,
+                           const int64_t* strides, int64_t B, int32_t C, int32_t T, int32_t F, int32_t reduction, double* workspace,
+                           float* pooled, float* weighted, double* stat, int32_t* sel, ptmi_stream_t stream);
+int ptmi_mask_loss_backward(const float* logits, const float* target, const void* power, int32_t power_kind, const int32_t* num_frames,
+                            const int64_t* strides, const float* g_pooled, const float* g_weighted, const double* stat,
+                            const int32_t* sel, int64_t B, int32_t C, int32_t T, int32_t F, int32_t reduction, float* dlogits,
+                            ptmi_stream_t stream);
+
 /* ---- Mask-based MVDR beamforming --------------------------------------------------------------------
  * What the mask estimators are trained for (padertorch/contrib/examples/speech_enhancement/mask_estimator/evaluate.py:110-137,
  * contrib/jensheit/evaluation.py:14-45; there through pb_bss / paderbox on the host).  Y and X [B, C, T, F] complex64 as interleaved

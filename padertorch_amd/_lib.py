@@ -99,6 +99,11 @@ SIGNATURES = {
                                         c_int32, _P]),
     'ptmi_orpit_flag_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32,
                                          c_int32, c_int32, c_int32, _P]),
+    'ptmi_mask_loss_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    'ptmi_mask_loss_forward': (c_int, [_P, _P, _P, c_int32, _P, _I64P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                       _P]),
+    'ptmi_mask_loss_backward': (c_int, [_P, _P, _P, c_int32, _P, _I64P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P,
+                                        _P]),
     'ptmi_bf_psd_workspace_elems': (c_int64, [c_int64, c_int32, c_int64, c_int64, c_int32]),
     'ptmi_bf_psd': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P]),
     'ptmi_bf_souden': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),

@@ -26,3 +26,5 @@ from . import beamforming  # noqa: F401
 from .beamforming import (get_power_spectral_density_matrix, get_mvdr_vector_souden, apply_beamforming_vector,  # noqa: F401
                           mask_beamforming, get_gev_vector, get_pca_vector, blind_analytic_normalization, phase_correction,
                           get_bf_vector)
+from . import mask_loss  # noqa: F401
+from .mask_loss import mask_bce_loss  # noqa: F401

@@ -33,6 +33,7 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.dprnn_segment / dprnn_overlap_add   ptmi_dprnn_*, ptmi_chunk_lstm_*   (modules/dual_path_rnn.py)
     torch.ops.ptmi.bf_psd / bf_souden / bf_apply / bf_eig / bf_ban / bf_phase   ptmi_bf_*   (mask_estimator/evaluate.py:110-137,
                                                                               jensheit/evaluation.py:14-45)
+    torch.ops.ptmi.mask_loss_forward / _backward   ptmi_mask_loss_*          (jensheit/mask_estimator_example/model.py:128-237)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -571,6 +572,61 @@ def orpit_flag_backward(gflag, gpre, flag, stat, pre, w, additional, weight, mas
                           _lib.ptr(mask), _lib.ptr(encoded), dadd.data_ptr(), dparams.data_ptr(), _lib.ptr(dmask), _lib.ptr(denc),
                           ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev)), 'ptmi_orpit_flag_backward')
     return dadd, dparams, dmask, denc
+
+
+# ------------------------------------------------------------------------------------------------ mask loss (csrc/mask_loss.hip)
+def _mask_loss_args(logits, target, power, num_frames):
+    """``(B, C, T, F, power kind, the HOST stride array)`` of ``[B, C, T, F]`` operands with unit stride on ``F``."""
+    assert logits.dim() == 4 and logits.shape == target.shape and logits.dtype == target.dtype == torch.float32, \
+        (logits.shape, target.shape, logits.dtype, target.dtype)
+    B, C, T, F = logits.shape
+    kind = 0
+    if power is not None:
+        assert power.shape == logits.shape and power.dtype in (torch.float32, torch.complex64), (power.shape, power.dtype)
+        kind = 2 if power.dtype == torch.complex64 else 1
+    for t in (logits, target, power):
+        assert t is None or F == 1 or t.stride(3) == 1, t.stride()
+    assert num_frames is None or (num_frames.dtype == torch.int32 and num_frames.shape == (B,) and num_frames.is_contiguous()), \
+        (num_frames.dtype, num_frames.shape)
+    strides = (ctypes.c_int64 * 9)(*logits.stride()[:3], *target.stride()[:3], *(power.stride()[:3] if kind else (0, 0, 0)))
+    return B, C, T, F, kind, strides
+
+
+@_register('mask_loss_forward(Tensor logits, Tensor target, Tensor? power, Tensor? num_frames, int reduction) '
+           '-> (Tensor, Tensor?, Tensor, Tensor)')
+def mask_loss_forward(logits, target, power, num_frames, reduction):
+    """``(pooled [B], weighted [B] or None, stat [B, 4] float64, sel [B, 2] int32)`` of ``logits, target [B, C, T, F]`` (strided, unit
+    stride on ``F``), ``power`` float32 or complex64, ``num_frames`` int32 ``[B]``; ``reduction`` 0 mean, 1 median, 2 min, 3 max
+    (``ptmi_mask_loss_forward``)."""
+    lib = _lib.load()
+    B, C, T, F, kind, strides = _mask_loss_args(logits, target, power, num_frames)
+    dev = logits.device
+    pooled = torch.empty(B, dtype=torch.float32, device=dev)
+    weighted = torch.empty(B, dtype=torch.float32, device=dev) if kind else None
+    stat = _doubles(4 * B, dev).view(B, 4)
+    sel = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    ws = _doubles(lib.ptmi_mask_loss_workspace_elems(B, C, T, F), dev)
+    _lib.check(_lib.timed('mask_loss_forward', lib.ptmi_mask_loss_forward, logits.data_ptr(), target.data_ptr(), _lib.ptr(power), kind,
+                          _lib.ptr(num_frames), strides, B, C, T, F, reduction, ws.data_ptr(), pooled.data_ptr(), _lib.ptr(weighted),
+                          stat.data_ptr(), sel.data_ptr(), _lib.stream(dev)), 'ptmi_mask_loss_forward')
+    return pooled, weighted, stat, sel
+
+
+@_register('mask_loss_backward(Tensor logits, Tensor target, Tensor? power, Tensor? num_frames, Tensor? g_pooled, Tensor? g_weighted, '
+           'Tensor stat, Tensor sel, int reduction) -> Tensor')
+def mask_loss_backward(logits, target, power, num_frames, g_pooled, g_weighted, stat, sel, reduction):
+    """``d logits [B, C, T, F]`` (dense) from ``g_pooled`` / ``g_weighted [B]`` (either may be None) (``ptmi_mask_loss_backward``)."""
+    lib = _lib.load()
+    B, C, T, F, kind, strides = _mask_loss_args(logits, target, power, num_frames)
+    _f32c(g_pooled, g_weighted)
+    assert (g_pooled is None or g_pooled.shape == (B,)) and (g_weighted is None or g_weighted.shape == (B,))
+    assert stat.shape == (B, 4) and stat.dtype == torch.float64 and sel.shape == (B, 2) and sel.dtype == torch.int32
+    dev = logits.device
+    out = torch.empty((B, C, T, F), dtype=torch.float32, device=dev)
+    _lib.check(_lib.timed('mask_loss_backward', lib.ptmi_mask_loss_backward, logits.data_ptr(), target.data_ptr(), _lib.ptr(power), kind,
+                          _lib.ptr(num_frames), strides, _lib.ptr(g_pooled), _lib.ptr(g_weighted), stat.data_ptr(), sel.data_ptr(),
+                          B, C, T, F, reduction, out.data_ptr(), _lib.stream(dev)), 'ptmi_mask_loss_backward')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ beamforming (csrc/beamform.hip)
