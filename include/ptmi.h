@@ -840,6 +840,38 @@ int ptmi_adam_flat(float* flat_grad, float* exp_avg, float* exp_avg_sq, const in
                    const float* step, double lr, double beta1, double beta2, double eps, double weight_decay, const double* hyper,
                    int32_t zero_grad, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Fast Griffin-Lim phase retrieval (csrc/griffin_lim.hip, the fused update in csrc/stft.hip): replaces
+ * padertorch/contrib/mk/synthesis/parametric/griffin_lim.py:32-74 (griffin_lim_step) and :132-155 (the loop of fast_griffin_lim).
+ * Spectra are interleaved (re, im) fp32 of n bins; a [n] fp32 magnitudes.  angle(0) := 0 (np.angle): y == 0 projects to (a, 0); a bin
+ * whose |y|^2 lies below fp32's normal range projects to the correct unit phasor.
+ *
+ * Device state of one retrieval: state int32 [4] = done, num_iterations, nparts, reserved (zeroed by the caller before the first
+ * iteration); partials = ptmi_gl_partials_elems() doubles; rmse fp32 [iterations] (filled with NaN by the caller).
+ *
+ * ptmi_gl_project          : P = a y / |y|                                   (griffin_lim.py:55-56, :151-152)
+ * ptmi_gl_project_backward : da = Re(conj(y / |y|) g)                        (its adjoint in a; the phase is a constant)
+ * ptmi_gl_update           : y = xnew + alpha (xnew - x); x <- xnew; P <- a y / |y|; per-workgroup fp64 partials of (|xnew| - a)^2
+ *                            (griffin_lim.py:137-142 on a computed xnew = STFT(iSTFT(P)), :136).  y is never stored.
+ * ptmi_gl_stft_update      : the same with xnew = STFT(audio) computed by the launch itself and never stored (the forward STFT's third
+ *                            epilogue; x is updated in place); audio [batch, num_samples] whose STFT has exactly `frames` frames
+ *                            (PTMI_E_INVALID otherwise).  PTMI_E_UNSUPPORTED for sizes outside the powers of two 64..2048: use
+ *                            ptmi_stft_forward + ptmi_gl_update.
+ * ptmi_gl_finish           : rmse[iteration] = sqrt(sum of the partials / count) (fixed order, fp64), num_iterations = iteration + 1,
+ *                            done = 1 if rmse < atol (griffin_lim.py:139-142, :149; a NaN never stops).
+ * Once done is set, ptmi_gl_update / ptmi_gl_stft_update / ptmi_gl_finish return without writing: the loop needs no host read.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t ptmi_gl_partials_elems(void);
+int ptmi_gl_project(const float* a, const float* y, int64_t n, float* P, ptmi_stream_t stream);
+int ptmi_gl_project_backward(const float* g, const float* y, int64_t n, float* da, ptmi_stream_t stream);
+int ptmi_gl_update(const float* xnew, float* x, const float* a, int64_t n, float alpha, float* P, double* partials, int32_t* state,
+                   ptmi_stream_t stream);
+int ptmi_gl_stft_update(const float* audio, int64_t batch, int64_t row_stride, int64_t num_samples, const float* window,
+                        const float* twiddle, const ptmi_stft_geom* g, int64_t frames, float alpha, float* x, const float* a, float* P,
+                        double* partials, int32_t* state, ptmi_stream_t stream);
+int ptmi_gl_finish(const double* partials, int64_t count, double atol, int32_t iteration, float* rmse, int32_t* state,
+                   ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -104,6 +104,12 @@ SIGNATURES = {
                                        _P]),
     'ptmi_mask_loss_backward': (c_int, [_P, _P, _P, c_int32, _P, _I64P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P,
                                         _P]),
+    'ptmi_gl_partials_elems': (c_int64, []),
+    'ptmi_gl_project': (c_int, [_P, _P, c_int64, _P, _P]),
+    'ptmi_gl_project_backward': (c_int, [_P, _P, c_int64, _P, _P]),
+    'ptmi_gl_update': (c_int, [_P, _P, _P, c_int64, c_float, _P, _P, _P, _P]),
+    'ptmi_gl_stft_update': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _G, c_int64, c_float, _P, _P, _P, _P, _P, _P]),
+    'ptmi_gl_finish': (c_int, [_P, c_int64, c_double, c_int32, _P, _P, _P]),
     'ptmi_bf_psd_workspace_elems': (c_int64, [c_int64, c_int32, c_int64, c_int64, c_int32]),
     'ptmi_bf_psd': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P]),
     'ptmi_bf_souden': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),

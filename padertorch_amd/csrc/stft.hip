@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "fft_regs.h"
+#include "phasor.h"
 
 namespace ptmi {
 
@@ -587,25 +588,7 @@ __global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES
 // One wavefront owns FPW frames of one example for ALL K+1 signals: it transforms the mixture first
 // and keeps the unit phasors of Y in its private LDS slice, then each source, forming
 // cos(angle(Y) - angle(X)) = Re(y_hat conj x_hat)  (angle(0) := 0 like np.angle) on the way out.
-__device__ __forceinline__ void mag_phasor(cpx X, float& mag, cpx& ph) {
-    const float p = X.x * X.x + X.y * X.y;
-    const float r = __builtin_amdgcn_rsqf(p);            // 1/|X|; inf at 0 and for a DENORMAL p (the hardware flushes the operand)
-    mag = p * r;
-    ph = cpx{X.x * r, X.y * r};
-    // (a NaN bin - a NaN sample in the frame - fails the comparison and stays NaN in the magnitude and in the phasor like np.abs /
-    //  np.angle of the reference's features (pit/data.py:67-75), so that the loss and with it the Trainer's non-finite check see it)
-    if (__builtin_expect(p < 1.1754944e-38f, 0)) {
-        // zero or below the normal range (rare: a frame whose only samples meet window taps of ~1e-17 - a Blackman window's first tap
-        // - gives |X|^2 ~ 1e-38; `p * rsq(p)` was inf there, round 6): the same arithmetic on 2^64 X
-        const cpx Xs{X.x * 0x1p64f, X.y * 0x1p64f};
-        const float ps = Xs.x * Xs.x + Xs.y * Xs.y;
-        const float rs = __builtin_amdgcn_rsqf(ps);
-        const bool zero = ps < 1.1754944e-38f;           // |X| < 2^-127: zero like the exact zero (angle(0) := 0)
-        mag = zero ? 0.f : ps * rs * 0x1p-64f;
-        ph = zero ? cpx{1.f, 0.f} : cpx{Xs.x * rs, Xs.y * rs};
-    }
-}
-
+// (mag_phasor: phasor.h)
 template <class PL>
 __global__ __launch_bounds__(256, 2) void pit_features_kernel(const FwdArgs A) {
     constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
@@ -806,6 +789,130 @@ __global__ __launch_bounds__(256, 2) void pit_features_kernel(const FwdArgs A) {
             wave_sync();   // the next transposition reuses wbuf; yph is read by the following signals
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Griffin-Lim (griffin_lim.hip): the forward STFT of the audio with the WHOLE update of one iteration as its epilogue
+// (padertorch/contrib/mk/synthesis/parametric/griffin_lim.py:136-142).  The pipeline is stft_fwd_kernel's; where that one stores the
+// spectrum x_, each lane here reads x[k] and a[k] at the very address, forms y = x_ + alpha (x_ - x), P = a y / |y| and (|x_| - a)^2
+// from the spectrum still in LDS, and stores x_ over x (in place: the lane that reads a bin is the one that writes it, and no other
+// lane touches it) and P.  36 bytes per bin and iteration instead of the 64 of stft + gl_update_kernel.  Every wavefront adds its
+// work items' sums in item order (fp64) and leaves ONE partial at slot 4 * workgroup + wave; state[0] != 0 (stopped): nothing is written.
+struct GlArgs {
+    cpx* x;
+    const float* a;
+    cpx* P;
+    double* partials;
+    int32_t* state;
+    float alpha;
+};
+
+template <class PL>
+__global__ __launch_bounds__(256, PL::INV_WAVES > 2 ? 2 : PL::INV_WAVES) void gl_stft_update_kernel(const FwdArgs A, const GlArgs G) {
+    constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
+    constexpr int NP = M / 2 + 1;   // bin pairs (k, M-k) per frame
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (G.state[0] != 0) return;    // grid-uniform
+    const WaveLds<PL> S(smem, 4);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int fl = lane / LPF, l = lane - fl * LPF;
+    cpx* wbuf = S.buf + wave * FPW * FS;
+    const float alpha = G.alpha;
+
+    load_tables_w<PL>(S, A.window, A.twiddle, A.g.L, tid, 256);
+    __syncthreads();
+
+    struct Item {
+        int b, tw0;
+        const float* xrow;
+        bool interior;
+    };
+    const int n_b = (int)A.num_samples;
+    const unsigned items = (unsigned)(A.batch * A.nchunks);
+    auto decode = [&](unsigned item) {
+        Item it;
+        it.b = (int)(item / (unsigned)A.nchunks);
+        it.tw0 = (int)(item - (unsigned)it.b * (unsigned)A.nchunks) * FPW;
+        it.xrow = A.x + (long long)it.b * A.x_row_stride;
+        const int x_first = it.tw0 * A.g.shift - A.g.pad_left;
+        const int x_last = (it.tw0 + FPW - 1) * A.g.shift - A.g.pad_left + PL::SIZE;
+        it.interior = A.aligned2 && x_first >= 0 && x_last <= n_b;   // wave-uniform
+        return it;
+    };
+    float2 pre[PL::R1];
+    auto issue = [&](const Item& it) {
+        const float2* __restrict__ px =
+            reinterpret_cast<const float2*>(it.xrow + it.tw0 * A.g.shift - A.g.pad_left + fl * A.g.shift) + l;
+        if (l < PL::R2) {
+#pragma unroll
+            for (int n1 = 0; n1 < PL::R1; ++n1) pre[n1] = px[PL::R2 * n1];
+        }
+    };
+    // one bin: returns (|x_| - a)^2
+    auto update = [&](cpx xn, cpx xo, float av, cpx& Pv) {
+        const cpx y{xn.x + alpha * (xn.x - xo.x), xn.y + alpha * (xn.y - xo.y)};
+        float mag;
+        cpx u;
+        mag_phasor(y, mag, u);
+        Pv = cpx{av * u.x, av * u.y};
+        const float d = sqrtf(xn.x * xn.x + xn.y * xn.y) - av;
+        return d * d;
+    };
+    double wsum = 0.;
+    const unsigned stride = gridDim.x * 4;
+    unsigned item = blockIdx.x * 4 + wave;
+    Item cur = decode(item < items ? item : 0);
+    bool cur_pre = item < items && cur.interior;
+    if (cur_pre) issue(cur);
+    for (; item < items; item += stride) {
+        const int b = cur.b, tw0 = cur.tw0;
+        cpx a[PL::R1];
+        if (cur_pre) {
+            const cpx* pw = reinterpret_cast<const cpx*>(S.win) + l;
+            if (l < PL::R2) {
+#pragma unroll
+                for (int n1 = 0; n1 < PL::R1; ++n1) a[n1] = cpx{pre[n1].x, pre[n1].y} * pw[PL::R2 * n1];
+            }
+        } else {
+            load_frames<PL>(a, cur.xrow, n_b, tw0, fl, l, A.g, A.aligned2, S.win);
+        }
+        {
+            const unsigned nxt = item + stride;
+            cur = decode(nxt < items ? nxt : 0);
+            cur_pre = nxt < items && cur.interior;
+            if (cur_pre) issue(cur);
+        }
+        fft_to_lds_wave<PL, false>(a, wbuf + fl * FS, l, S.tw1t);
+
+        const int nfr = min(FPW, (int)A.out_frames - tw0);                  // frames of this item inside [0, out_frames)
+        const long long base = ((long long)b * A.out_frames + tw0) * F;     // first bin of the item in x / a / P
+        cpx* __restrict__ xr = G.x + base;
+        cpx* __restrict__ Pr = G.P + base;
+        const float* __restrict__ ar = G.a + base;
+        float acc = 0.f;
+        for (int p = lane; p < nfr * NP; p += 64) {
+            const int f = p / NP, k = p - f * NP, km = M - k;
+            const int ik = f * F + k, im = f * F + km;                      // < nfr * F: inside the tensors
+            const cpx xok = xr[ik], xom = xr[im];
+            const float ak = ar[ik], am = ar[im];
+            cpx Xk, Xm, Pk, Pm;
+            split_pair<PL>(wbuf + f * FS, S.tws, k, Xk, Xm);
+            acc += update(Xk, xok, ak, Pk);
+            xr[ik] = Xk;
+            Pr[ik] = Pk;
+            if (km != k) {
+                acc += update(Xm, xom, am, Pm);
+                xr[im] = Xm;
+                Pr[im] = Pm;
+            }
+        }
+        wsum += (double)acc;        // per lane, item order; the lanes are folded once at the end
+        wave_sync();   // the next item's transposition reuses wbuf
+    }
+    for (int o = 32; o >= 1; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
+    if (lane == 0) G.partials[blockIdx.x * 4 + wave] = wsum;
+    if (blockIdx.x == 0 && tid == 0) G.state[2] = (int32_t)(gridDim.x * 4);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1331,6 +1438,42 @@ static int dispatch_inv(InvArgs& A, long long batch, hipStream_t st) {
     }
 }
 
+constexpr int kGlMaxBlocks = 4096;   // 4 partials per workgroup <= ptmi_gl_partials_elems()
+
+template <class PL>
+static int launch_gl(FwdArgs& A, const GlArgs& G, long long batch, hipStream_t st) {
+    A.dbg = 0;
+    A.aligned2 = (A.x_row_stride % 2 == 0) && (A.g.shift % 2 == 0) && (A.g.pad_left % 2 == 0) &&
+                 (reinterpret_cast<uintptr_t>(A.x) % 8 == 0);
+    const size_t smem = WaveLds<PL>::bytes(4, 0);
+    if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
+    A.batch = batch;
+    A.nchunks = (int)((A.out_frames + PL::FPW - 1) / PL::FPW);
+    const long long items = batch * A.nchunks;
+    if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
+    if (smem > kMaxSmem) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gl_stft_update_kernel<PL>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return (int)e;
+    }
+    const long long resident = 256LL * blocks_per_cu<gl_stft_update_kernel<PL>>(256, smem);
+    const long long blocks = std::min(std::min((items + 3) / 4, resident), (long long)kGlMaxBlocks);
+    hipLaunchKernelGGL(gl_stft_update_kernel<PL>, dim3((unsigned)blocks), dim3(256), smem, st, A, G);
+    return launch_status();
+}
+
+static int dispatch_gl(FwdArgs& A, const GlArgs& G, long long batch, hipStream_t st) {
+    switch (A.g.size) {
+        case 64: return launch_gl<Plan<4, 8>>(A, G, batch, st);
+        case 128: return launch_gl<Plan<8, 8>>(A, G, batch, st);
+        case 256: return launch_gl<Plan<8, 16>>(A, G, batch, st);
+        case 512: return launch_gl<Plan<16, 16>>(A, G, batch, st);
+        case 1024: return launch_gl<Plan<16, 32>>(A, G, batch, st);
+        case 2048: return launch_gl<Plan<32, 32>>(A, G, batch, st);
+        default: return PTMI_E_UNSUPPORTED;
+    }
+}
+
 // Mel filterbank (+ log) of a given spectrogram [N, F] -> [N, M] (MelTransform.forward,
 // contrib/je/modules/features.py:297-330): 8 rows per workgroup staged in LDS, one thread per output.
 struct MelArgs {
@@ -1572,6 +1715,27 @@ int ptmi_pit_features_packed(const float* y, const float* s, int64_t batch, int3
     PTMI_RETURN_IF(smem > kMaxSmem, PTMI_E_UNSUPPORTED);
     hipLaunchKernelGGL(pit_features_generic_kernel, dim3((unsigned)blocks), dim3(256), smem, st, A);
     return launch_status();
+}
+
+int ptmi_gl_stft_update(const float* audio, int64_t batch, int64_t row_stride, int64_t num_samples, const float* window,
+                        const float* twiddle, const ptmi_stft_geom* g, int64_t frames, float alpha, float* x, const float* a, float* P,
+                        double* partials, int32_t* state, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!geom_ok(g) || !audio || !window || !twiddle || !x || !a || !P || !partials || !state, PTMI_E_INVALID);
+    PTMI_RETURN_IF(batch <= 0 || frames <= 0 || g->window_length > g->size, PTMI_E_INVALID);
+    PTMI_RETURN_IF(num_samples > 0x7ff00000LL || frames > 0x7ff00000LL / (g->size + 2), PTMI_E_UNSUPPORTED);
+    PTMI_RETURN_IF(row_frames_of(to_geo(g), num_samples) != frames, PTMI_E_INVALID);     // STFT(audio) must give `frames` frames again
+    FwdArgs A{};
+    A.x = audio;
+    A.window = window;
+    A.twiddle = reinterpret_cast<const cpx*>(twiddle);
+    A.x_row_stride = row_stride;
+    A.num_samples = num_samples;
+    A.out_frames = frames;
+    A.layout = PTMI_LAYOUT_INTERLEAVED;
+    A.edge_scale = 1.f;
+    A.g = to_geo(g);
+    const GlArgs G{reinterpret_cast<cpx*>(x), a, reinterpret_cast<cpx*>(P), partials, state, alpha};
+    return dispatch_gl(A, G, batch, static_cast<hipStream_t>(stream));   // PTMI_E_UNSUPPORTED: no register-FFT plan for this size
 }
 
 }  // extern "C"

@@ -28,3 +28,5 @@ from .beamforming import (get_power_spectral_density_matrix, get_mvdr_vector_sou
                           get_bf_vector)
 from . import mask_loss  # noqa: F401
 from .mask_loss import mask_bce_loss  # noqa: F401
+from . import griffin_lim  # noqa: F401
+from .griffin_lim import gl_project, gl_update, gl_iterations  # noqa: F401

@@ -34,6 +34,7 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.bf_psd / bf_souden / bf_apply / bf_eig / bf_ban / bf_phase   ptmi_bf_*   (mask_estimator/evaluate.py:110-137,
                                                                               jensheit/evaluation.py:14-45)
     torch.ops.ptmi.mask_loss_forward / _backward   ptmi_mask_loss_*          (jensheit/mask_estimator_example/model.py:128-237)
+    torch.ops.ptmi.gl_project / gl_project_backward / gl_update / gl_iterations   ptmi_gl_*   (contrib/mk/synthesis/parametric/griffin_lim.py:32-156)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1274,3 +1275,95 @@ def dprnn_overlap_add(seg, P, L_out, front):
     _lib.check(_lib.timed('dprnn_overlap_add', _lib.load().ptmi_dprnn_overlap_add, seg.data_ptr(), strides, out.data_ptr(), B, L_out, N, S,
                           K, P, front, _lib.stream(seg.device)), 'ptmi_dprnn_overlap_add')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ Griffin-Lim (csrc/griffin_lim.hip)
+#: the sizes the register-FFT plans of csrc/stft.hip cover: ``ptmi_gl_stft_update`` (the fused update) exists for these
+GL_PLAN_SIZES = (64, 128, 256, 512, 1024, 2048)
+
+
+def _gl_check(a, *specs):
+    assert a.dtype == torch.float32 and a.is_contiguous(), (a.dtype, a.is_contiguous())
+    for s in specs:
+        assert s.dtype == torch.float32 and s.is_contiguous() and tuple(s.shape) == (*a.shape, 2), (s.dtype, s.shape, a.shape)
+
+
+@_register('gl_project(Tensor a, Tensor y) -> Tensor')
+def gl_project(a, y):
+    """``P = a y / |y|`` (``angle(0) := 0``): ``a [...]`` fp32, ``y [..., 2]`` interleaved fp32 -> ``P [..., 2]`` (``ptmi_gl_project``;
+    griffin_lim.py:55-56, 151-152)."""
+    _gl_check(a, y)
+    P = torch.empty_like(y)
+    _lib.check(_lib.timed('gl_project', _lib.load().ptmi_gl_project, a.data_ptr(), y.data_ptr(), a.numel(), P.data_ptr(),
+                          _lib.stream(a.device)), 'ptmi_gl_project')
+    return P
+
+
+@_register('gl_project_backward(Tensor g, Tensor y) -> Tensor')
+def gl_project_backward(g, y):
+    """``d a = Re(conj(y / |y|) g)``: the adjoint of :func:`gl_project` in ``a`` (``ptmi_gl_project_backward``)."""
+    assert g.dtype == y.dtype == torch.float32 and g.is_contiguous() and y.is_contiguous() and g.shape == y.shape and g.shape[-1] == 2
+    da = torch.empty(g.shape[:-1], dtype=torch.float32, device=g.device)
+    _lib.check(_lib.timed('gl_project_backward', _lib.load().ptmi_gl_project_backward, g.data_ptr(), y.data_ptr(), da.numel(),
+                          da.data_ptr(), _lib.stream(g.device)), 'ptmi_gl_project_backward')
+    return da
+
+
+def gl_state(device, iterations):
+    """The device state of one retrieval: ``(state int32 [4] = done, num_iterations, nparts, reserved; partials fp64; rmse fp32
+    [iterations], NaN)``."""
+    state = torch.zeros(4, dtype=torch.int32, device=device)
+    partials = torch.zeros(int(_lib.load().ptmi_gl_partials_elems()), dtype=torch.float64, device=device)
+    rmse = torch.full((iterations,), float('nan'), dtype=torch.float32, device=device)
+    return state, partials, rmse
+
+
+@_register('gl_update(Tensor xnew, Tensor(a!) x, Tensor a, float alpha, Tensor(b!) P, Tensor(c!) partials, Tensor(d!) state) -> ()')
+def gl_update(xnew, x, a, alpha, P, partials, state):
+    """griffin_lim.py:137-142, unfused: ``y = xnew + alpha (xnew - x)``; ``x <- xnew`` in place; ``P <- a y / |y|``; the workgroups' fp64
+    partial sums of ``(|xnew| - a)^2`` into ``partials`` and their count into ``state[2]``.  Nothing is written once ``state[0]`` (done)
+    is set (``ptmi_gl_update``)."""
+    _gl_check(a, xnew, x, P)
+    assert partials.dtype == torch.float64 and partials.numel() >= _lib.load().ptmi_gl_partials_elems() and state.dtype == torch.int32
+    _lib.check(_lib.timed('gl_update', _lib.load().ptmi_gl_update, xnew.data_ptr(), x.data_ptr(), a.data_ptr(), a.numel(), alpha,
+                          P.data_ptr(), partials.data_ptr(), state.data_ptr(), _lib.stream(a.device)), 'ptmi_gl_update')
+
+
+@_register('gl_iterations(Tensor a, Tensor(a!) x, Tensor(b!) P, Tensor syn, Tensor window, Tensor twiddle, int[] geom, int samples, '
+           'float alpha, int iterations, float atol, bool fused, int poll, Tensor(c!) rmse, Tensor(d!) partials, Tensor(e!) state) -> ()')
+def gl_iterations(a, x, P, syn, window, twiddle, geom, samples, alpha, iterations, atol, fused, poll, rmse, partials, state):
+    """The loop of griffin_lim.py:135-150 on device state: per iteration ``audio = iSTFT(P)`` (``ptmi_istft_forward``), the update
+    (``fused``: ``ptmi_gl_stft_update``, one launch; otherwise ``ptmi_stft_forward`` + ``ptmi_gl_update``) and ``ptmi_gl_finish``
+    (``rmse[n]``, ``state[0]`` = done, ``state[1]`` = iterations run).  ``a [rows, frames, F]``; ``x``, ``P [rows, frames, F, 2]`` hold
+    the start on entry (``P = a y / |y|`` of the start ``y``) and the last live iteration's values on return.  No host read inside the
+    loop unless ``poll > 0``: then ``state[0]`` is read every ``poll`` iterations and the launches stop once it is set (they would
+    write nothing).  The audio and (unfused) spectrum buffers are allocated once, in front of the loop."""
+    lib = _lib.load()
+    _gl_check(a, x, P)
+    rows, frames, F = a.shape
+    assert F == geom[0] // 2 + 1 and rmse.numel() >= iterations and state.dtype == torch.int32
+    assert partials.dtype == torch.float64 and partials.numel() >= lib.ptmi_gl_partials_elems()
+    g = _geom(geom)
+    assert lib.ptmi_stft_num_frames(g, samples) == frames, (samples, frames)
+    if iterations <= 0:
+        return
+    dev, st = a.device, _lib.stream(a.device)
+    audio = torch.empty((rows, samples), dtype=torch.float32, device=dev)
+    xnew = None if fused else torch.empty_like(x)
+    n = a.numel()
+    for it in range(iterations):
+        _lib.check(_lib.timed('gl_istft', lib.ptmi_istft_forward, P.data_ptr(), rows, frames, None, syn.data_ptr(), twiddle.data_ptr(), g,
+                              0, 1.0, geom[3], samples, samples, audio.data_ptr(), st), 'ptmi_istft_forward')
+        if fused:
+            _lib.check(_lib.timed('gl_stft_update', lib.ptmi_gl_stft_update, audio.data_ptr(), rows, samples, samples, window.data_ptr(),
+                                  twiddle.data_ptr(), g, frames, alpha, x.data_ptr(), a.data_ptr(), P.data_ptr(), partials.data_ptr(),
+                                  state.data_ptr(), st), 'ptmi_gl_stft_update')
+        else:
+            _lib.check(_lib.timed('gl_stft', lib.ptmi_stft_forward, audio.data_ptr(), rows, samples, samples, None, window.data_ptr(),
+                                  twiddle.data_ptr(), g, frames, 0, 1.0, xnew.data_ptr(), st), 'ptmi_stft_forward')
+            _lib.check(_lib.timed('gl_update', lib.ptmi_gl_update, xnew.data_ptr(), x.data_ptr(), a.data_ptr(), n, alpha, P.data_ptr(),
+                                  partials.data_ptr(), state.data_ptr(), st), 'ptmi_gl_update')
+        _lib.check(_lib.timed('gl_finish', lib.ptmi_gl_finish, partials.data_ptr(), n, atol, it, rmse.data_ptr(), state.data_ptr(), st),
+                   'ptmi_gl_finish')
+        if poll > 0 and (it + 1) % poll == 0 and it + 1 < iterations and int(state[0].item()) != 0:
+            break
