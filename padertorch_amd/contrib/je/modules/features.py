@@ -165,7 +165,7 @@ class MelTransform(nn.Module):
         return torch.max(x, torch.zeros_like(x))
 
 
-#: STFT size -> (R1, R2) of its FFT plan (csrc/stft.hip, dispatch_fwd)
+#: STFT size -> (R1, R2) of its FFT plan (csrc/stft.hip, with_plan)
 _PLANS = {64: (4, 8), 128: (8, 8), 256: (8, 16), 512: (16, 16), 1024: (16, 32), 2048: (32, 32)}
 _LDS_LIMIT = 160 * 1024
 

@@ -4,9 +4,10 @@
 // padertorch/contrib/examples/source_separation/pit/data.py:49-77 (pre_batch_transform).
 //
 // Design:
-//  * one 256-thread workgroup owns FPB consecutive frames of one batch row; the samples those
-//    frames cover ((FPB-1)*shift + L floats) are staged ONCE into LDS with coalesced dword loads
-//    (fading / frame padding = predicated zero fill, bit-exact framing, no padded copy in HBM);
+//  * persistent wavefronts: one wavefront owns FPW consecutive frames of one batch row from the
+//    global loads to the stores (fading / frame padding = selects on clamped loads, bit-exact
+//    framing, no padded copy in HBM); the three forward kernels share ONE such pipeline
+//    (wave_pipeline: the plain / mel and the Griffin-Lim kernel; the features kernel has the same loop over K + 1 signals);
 //  * a real FFT of `size` points is a complex FFT of M = size/2 = R1*R2 points on packed
 //    even/odd samples, done as two in-register FFTs (R1 then R2 points per lane, LPF = max(R1,R2)
 //    lanes per frame, 64/LPF frames per wavefront) with ONE transposition through LDS
@@ -36,11 +37,9 @@ struct Plan {
     static constexpr int SIZE = 2 * M;     // real FFT length
     static constexpr int LPF = R1 > R2 ? R1 : R2;  // lanes per frame
     static constexpr int FPW = 64 / LPF;           // frames per wavefront
-    static constexpr int FPB = 4 * FPW;            // frames per 256-thread workgroup
     static constexpr int P = R2 + 1;               // transposition pitch (complex)
     static constexpr int FS0 = (R1 * P > F ? R1 * P : F);
     static constexpr int FS = (FS0 + 1) & ~1;      // per-frame LDS region (complex), even
-    static constexpr int NIT = (FPW * F + 63) / 64;  // epilogue items per lane
     // inverse kernel: waves per SIMD the register budget is sized for (its LDS footprint grows with M)
     static constexpr int INV_WAVES = M <= 256 ? 3 : (M <= 512 ? 2 : 1);
 };
@@ -92,114 +91,6 @@ __device__ __forceinline__ cpx tw_full(const cpx* tw, int j) {
     return tw[j];
 }
 
-// LDS carve-up shared by the forward kernels (all offsets multiples of 16 bytes):
-//   buf  [FPB][FS] cpx   per-frame transposition / natural-order spectrum
-//   tws  [F+1]     cpx   split twiddles W_size^k, k = 0..M
-//   tw1t [R1][LPF] cpx   inter-stage twiddles W_M^(l*k1), lane-contiguous
-//   win  [SIZE]    float analysis window, zero beyond window_length
-//   sig  [...]     float staged samples of the FPB frames, zero-filled tail up to SIZE
-template <class PL>
-struct FwdLds {
-    cpx* buf;
-    cpx* tws;
-    cpx* tw1t;
-    float* win;
-    float* sig;
-    __device__ __forceinline__ explicit FwdLds(char* smem) {
-        buf = reinterpret_cast<cpx*>(smem);
-        tws = buf + PL::FPB * PL::FS;
-        tw1t = tws + PL::F + 1;
-        win = reinterpret_cast<float*>(tw1t + PL::R1 * PL::LPF);
-        sig = win + PL::SIZE;
-    }
-    static size_t bytes(int shift) {
-        const size_t chunk = (size_t)(PL::FPB - 1) * shift + PL::SIZE;
-        return sizeof(cpx) * ((size_t)PL::FPB * PL::FS + PL::F + 1 + PL::R1 * PL::LPF) +
-               sizeof(float) * (PL::SIZE + chunk + 2 * PL::LPF + 8);
-    }
-};
-
-// Fill the constant tables (once per workgroup, coalesced; the tables are L2 resident).
-template <class PL>
-__device__ __forceinline__ void load_tables(const FwdLds<PL>& S, const float* __restrict__ window,
-                                            const cpx* __restrict__ twiddle, int L, int tid) {
-    for (int i = tid; i <= PL::M; i += 256) S.tws[i] = twiddle[i];
-    for (int i = tid; i < PL::SIZE; i += 256) S.win[i] = (i < L) ? window[i] : 0.f;
-    for (int i = tid; i < PL::R1 * PL::LPF; i += 256) {
-        const int k1 = i / PL::LPF, l = i - k1 * PL::LPF;
-        S.tw1t[i] = tw_full<PL::M>(twiddle, (2 * l * k1) % PL::SIZE);   // W_M^(l*k1) = W_size^(2*l*k1)
-    }
-}
-
-// Two-step complex FFT of one frame.  On entry lane l (< R2) holds a[i1] = in[R2*i1 + l].
-// On exit fbuf[k], k < M, holds the transform in natural order.  Contains block-wide barriers.
-template <class PL, bool INV>
-__device__ __forceinline__ void fft_to_lds(cpx (&a)[PL::R1], cpx* fbuf, int l, const cpx* tw1t) {
-    constexpr int R1 = PL::R1, R2 = PL::R2, P = PL::P;
-    if (l < R2) {
-        fft_dif<R1, INV>(a);
-#pragma unroll
-        for (int k1 = 0; k1 < R1; ++k1) {
-            const cpx v = a[bitrev<R1>(k1)];
-            const cpx w = tw1t[k1 * PL::LPF + l];
-            fbuf[k1 * P + l] = INV ? cmulc(v, w) : cmul(v, w);
-        }
-    }
-    __syncthreads();
-    cpx c[R2];
-    if (l < R1) {
-#pragma unroll
-        for (int n2 = 0; n2 < R2; ++n2) c[n2] = fbuf[l * P + n2];
-    }
-    __syncthreads();
-    if (l < R1) {
-        fft_dif<R2, INV>(c);
-#pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) fbuf[l + R1 * k2] = c[bitrev<R2>(k2)];
-    }
-    __syncthreads();
-}
-
-// Stage the samples of frames [t0, t0+FPB) of one row into LDS: zero outside [0, n_b) (fading and
-// frame padding) and zero up to SIZE past the last frame start (so the unpredicated window loads
-// below never see uninitialised LDS).  Row offsets fit in 32 bits (checked on the host).
-template <class PL>
-__device__ __forceinline__ void stage_signal(float* sig, const float* __restrict__ xrow, int n_b,
-                                             int t0, const Geo& g, int tid) {
-    const int chunk = (PL::FPB - 1) * g.shift + PL::SIZE;
-    const int v0 = t0 * g.shift - g.pad_left;
-    for (int i = tid; i < chunk; i += 256) {
-        const int xi = v0 + i;
-        float v = 0.f;
-        if (xi >= 0 && xi < n_b) v = xrow[xi];
-        sig[i] = v;
-    }
-}
-
-// Load the windowed, even/odd packed samples of this lane's frame into registers
-// (a[n1] = x_w[2 (R2 n1 + l)] + i x_w[2 (R2 n1 + l) + 1]).  No predicates: win is 0 beyond L.
-template <class PL>
-__device__ __forceinline__ void load_windowed(cpx (&a)[PL::R1], const float* sf, const float* win, int l) {
-#pragma unroll
-    for (int n1 = 0; n1 < PL::R1; ++n1) {
-        const int k = 2 * (PL::R2 * n1 + l);
-        a[n1] = cpx{sf[k] * win[k], sf[k + 1] * win[k + 1]};
-    }
-}
-
-// Hermitian split: bin k of the size-point real FFT from the natural-order M-point complex FFT.
-template <class PL>
-__device__ __forceinline__ cpx split_bin(const cpx* zb, const cpx* tws, int k) {
-    constexpr int M = PL::M;
-    const cpx z1 = zb[k & (M - 1)];
-    const cpx z2 = zb[(M - k) & (M - 1)];
-    const cpx w = tws[k];
-    const float ex = 0.5f * (z1.x + z2.x), ey = 0.5f * (z1.y - z2.y);  // E = (Z[k] + conj Z[M-k]) / 2
-    const float dx = 0.5f * (z1.x - z2.x), dy = 0.5f * (z1.y + z2.y);  // D = (Z[k] - conj Z[M-k]) / 2
-    // X = E + (-i D) * w,  -i D = (dy, -dx)
-    return cpx{ex + dy * w.x + dx * w.y, ey + dy * w.y - dx * w.x};
-}
-
 // ------------------------------------------------------------------------------------------------
 // Forward kernels, wave-private pipelines: every wavefront owns FPW frames of ONE signal from the
 // global loads to the stores (no workgroup barrier on the way), so the wavefronts of a CU drift
@@ -228,7 +119,7 @@ struct WaveLds {
         buf = reinterpret_cast<cpx*>(win + PL::SIZE);
         yph = buf + nwaves * PL::FPW * PL::FS;
     }
-    __host__ __device__ static size_t bytes(int nwaves, int nyph) {
+    __host__ __device__ static constexpr size_t bytes(int nwaves, int nyph) {
         return sizeof(cpx) * (PL::F + 1 + PL::R1 * PL::LPF + (size_t)nwaves * PL::FPW * PL::FS +
                               (size_t)nyph * PL::FPW * YS) + sizeof(float) * PL::SIZE;
     }
@@ -322,9 +213,11 @@ __device__ __forceinline__ void load_frames(cpx (&a)[PL::R1], const float* __res
     }
 }
 
-// Two-step complex FFT of the FPW frames of ONE wavefront (wave-level hand-offs only).
-template <class PL, bool INV>
-__device__ __forceinline__ void fft_to_lds_wave(cpx (&a)[PL::R1], cpx* fbuf, int l, const cpx* tw1t) {
+// Two-step complex FFT of the FPW frames of ONE wavefront (wave-level hand-offs only).  WIN: the last
+// stage multiplies z[n] = x[2n] + i x[2n+1] by the pair (w[2n], w[2n+1]) of win2 (the inverse's synthesis window).
+template <class PL, bool INV, bool WIN = false>
+__device__ __forceinline__ void fft_to_lds_wave(cpx (&a)[PL::R1], cpx* fbuf, int l, const cpx* tw1t,
+                                                const cpx* win2 = nullptr) {
     constexpr int R1 = PL::R1, R2 = PL::R2, P = PL::P;
     if (l < R2) {
         fft_dif<R1, INV>(a);
@@ -345,21 +238,19 @@ __device__ __forceinline__ void fft_to_lds_wave(cpx (&a)[PL::R1], cpx* fbuf, int
     if (l < R1) {
         fft_dif<R2, INV>(c);
 #pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) fbuf[l + R1 * k2] = c[bitrev<R2>(k2)];
+        for (int k2 = 0; k2 < R2; ++k2) {
+            const int n = l + R1 * k2;
+            if constexpr (WIN)
+                fbuf[n] = c[bitrev<R2>(k2)] * win2[n];
+            else
+                fbuf[n] = c[bitrev<R2>(k2)];
+        }
     }
     wave_sync();
 }
 
 // Hermitian split of the bin pair (k, M-k) from Z[k], Z[M-k]:  with E = (Z[k] + conj Z[M-k])/2 and
 // Q = W^k (Z[k] - conj Z[M-k]) / (2i):  X[k] = E + Q,  X[M-k] = conj(E - Q).
-__device__ __forceinline__ void split_vals(cpx z1, cpx z2, cpx w, cpx& Xk, cpx& Xm);
-
-template <class PL>
-__device__ __forceinline__ void split_pair(const cpx* zb, const cpx* tws, int k, cpx& Xk, cpx& Xm) {
-    constexpr int M = PL::M;
-    split_vals(zb[k & (M - 1)], zb[(M - k) & (M - 1)], tws[k], Xk, Xm);
-}
-
 __device__ __forceinline__ void split_vals(cpx z1, cpx z2, cpx w, cpx& Xk, cpx& Xm) {
     const cpx e2 = add_conj(z1, z2);                    // 2 E
     const cpx d = sub_conj(z1, z2) * cpx{0.5f, 0.5f};   // D
@@ -371,44 +262,30 @@ __device__ __forceinline__ void split_vals(cpx z1, cpx z2, cpx w, cpx& Xk, cpx& 
     asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1]" : "=v"(Xm) : "v"(e2), "s"(h2), "v"(q));    // conj(E - Q)
 }
 
-// MEL = false: spectrum out.  MEL = true: |X|^power -> band-compressed mel filterbank -> log(. + eps)
-// out [rows, frames, mel_M] (contrib/je/modules/features.py:171-176, 297-330): the spectrum never
-// leaves LDS, HBM traffic per frame drops from 512 + 2056 B to 512 + 4 * mel_M B.
-// (the fused (log-)mel instantiation of the 512-point plan needs 169 registers: at three workgroups per CU - a budget of 168 - it spilled ONE
-//  into scratch; it runs at two, the plain instantiation keeps three)
-template <class PL, bool MEL>
-__global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES) void stft_fwd_kernel(const FwdArgs A) {
-    constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
-    constexpr int NP = M / 2 + 1;   // bin pairs (k, M-k) per frame
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const WaveLds<PL> S(smem, 4);
-    // mel tables behind the wave buffers: lo | cnt | off [mel_M] int32, weights [mel_nnz] float
-    float* mw = reinterpret_cast<float*>(smem + ((WaveLds<PL>::bytes(4, 0) + 15) & ~(size_t)15));   // 16-byte aligned
-    int32_t* mlo = reinterpret_cast<int32_t*>(mw + A.mel_nnz);
-    int32_t* mcnt = mlo + A.mel_M;
-    int32_t* moff = mcnt + A.mel_M;
-    if (MEL) {
-        for (int i = threadIdx.x; i < A.mel_M; i += 256) {
-            mlo[i] = A.mel_lo[i];
-            mcnt[i] = A.mel_cnt[i];
-            moff[i] = A.mel_off[i];
-        }
-        for (int i = threadIdx.x; i < A.mel_nnz; i += 256) mw[i] = A.mel_w[i];
-    }
+template <class PL>
+__device__ __forceinline__ void split_pair(const cpx* zb, const cpx* tws, int k, cpx& Xk, cpx& Xm) {
+    constexpr int M = PL::M;
+    split_vals(zb[k & (M - 1)], zb[(M - k) & (M - 1)], tws[k], Xk, Xm);
+}
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+// ------------------------------------------------------------------------------------------------
+// The persistent loop of stft_fwd_kernel and gl_stft_update_kernel.  Work item = FPW consecutive frames of one row, row major;
+// wavefront w of workgroup g takes the items 4 g + w, + 4 gridDim.x, ...  The samples of the NEXT item are fetched into registers
+// before the current item's FFT and epilogue (interior items: one immediate-offset float2 load per FFT input), so that HBM latency
+// hides behind compute instead of heading every item; edge items (fading, a row's end, rows that are not 8-byte aligned) load in
+// place.  No workgroup barrier on the way.  RAGGED: rows have A.row_samples[b] samples where that is given (else all num_samples).
+// After each transform, epilogue(b, tw0, frames_b, wbuf) finds the natural-order M-point spectrum of frame tw0 + f of row b (which
+// has frames_b frames) at wbuf[f * FS ...]; wbuf is the wavefront's own and is reused by the next item.  The frame count is all
+// the epilogues want of the row's length n_b: taken before the loads, n_b does not stay live across the transform (an epilogue that
+// needs n_b itself reads it again).
+// dbg: the PTMI_STFT_DBG ablation bits 2 (no FFT: the windowed samples land in wbuf as they are) and 4 (no loads).
+// (pit_features_kernel keeps a loop of its own, see there.)
+template <class PL, bool RAGGED, class Epilogue>
+__device__ __forceinline__ void wave_pipeline(const FwdArgs& A, const WaveLds<PL>& S, int dbg, Epilogue&& epilogue) {
+    constexpr int FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fl = lane / LPF, l = lane - fl * LPF;
     cpx* wbuf = S.buf + wave * FPW * FS;
-    const float es = A.edge_scale;
-
-    load_tables_w<PL>(S, A.window, A.twiddle, A.g.L, tid, 256);
-    __syncthreads();
-
-    // persistent wavefronts: work item = FPW consecutive frames of one row; nchunks items per row.
-    // The samples of the NEXT item are fetched into registers before the current item's FFT and
-    // epilogue (interior items: one immediate-offset float2 load per FFT input), so that HBM
-    // latency hides behind compute instead of heading every item.
     struct Item {
         int b, tw0, n_b;
         const float* xrow;
@@ -419,11 +296,11 @@ __global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES
         Item it;
         it.b = (int)(item / (unsigned)A.nchunks);
         it.tw0 = (int)(item - (unsigned)it.b * (unsigned)A.nchunks) * FPW;
-        it.n_b = A.row_samples ? A.row_samples[it.b] : (int)A.num_samples;
+        it.n_b = (RAGGED && A.row_samples) ? A.row_samples[it.b] : (int)A.num_samples;
         it.xrow = A.x + (long long)it.b * A.x_row_stride;
         const int x_first = it.tw0 * A.g.shift - A.g.pad_left;
         const int x_last = (it.tw0 + FPW - 1) * A.g.shift - A.g.pad_left + PL::SIZE;
-        it.interior = A.aligned2 && x_first >= 0 && x_last <= it.n_b && !(A.dbg & 4);   // wave-uniform
+        it.interior = A.aligned2 && x_first >= 0 && x_last <= it.n_b && !(dbg & 4);   // wave-uniform
         return it;
     };
     float2 pre[PL::R1];
@@ -450,22 +327,58 @@ __global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES
 #pragma unroll
                 for (int n1 = 0; n1 < PL::R1; ++n1) a[n1] = cpx{pre[n1].x, pre[n1].y} * pw[PL::R2 * n1];
             }
-        } else if (!(A.dbg & 4)) {
+        } else if (!(dbg & 4)) {
             load_frames<PL>(a, cur.xrow, n_b, tw0, fl, l, A.g, A.aligned2, S.win);
         } else {
             for (int i = 0; i < PL::R1; ++i) a[i] = cpx{(float)(lane + i), 1.f};
         }
-        {
+        {   // the wavefront's next item (past the last item: nothing)
             const unsigned nxt = item + stride;
             cur = decode(nxt < items ? nxt : 0);
             cur_pre = nxt < items && cur.interior;
             if (cur_pre) issue(cur);
         }
-        if (!(A.dbg & 2))
+        if (!(dbg & 2))
             fft_to_lds_wave<PL, false>(a, wbuf + fl * FS, l, S.tw1t);
         else
             for (int i = 0; i < PL::R1; ++i) wbuf[fl * FS + i * LPF + l] = a[i];
+        epilogue(b, tw0, frames_b, wbuf);
+        wave_sync();   // the next item's transposition reuses wbuf
+    }
+}
 
+// MEL = false: spectrum out.  MEL = true: |X|^power -> band-compressed mel filterbank -> log(. + eps)
+// out [rows, frames, mel_M] (contrib/je/modules/features.py:171-176, 297-330): the spectrum never
+// leaves LDS, HBM traffic per frame drops from 512 + 2056 B to 512 + 4 * mel_M B.
+// (the fused (log-)mel instantiation of the 512-point plan needs 169 registers: at three workgroups per CU - a budget of 168 - it spilled ONE
+//  into scratch; it runs at two, the plain instantiation keeps three)
+template <class PL, bool MEL>
+__global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES) void stft_fwd_kernel(const FwdArgs A) {
+    constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS;
+    constexpr int NP = M / 2 + 1;   // bin pairs (k, M-k) per frame
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const WaveLds<PL> S(smem, 4);
+    // mel tables behind the wave buffers: lo | cnt | off [mel_M] int32, weights [mel_nnz] float
+    float* mw = reinterpret_cast<float*>(smem + ((WaveLds<PL>::bytes(4, 0) + 15) & ~(size_t)15));   // 16-byte aligned
+    int32_t* mlo = reinterpret_cast<int32_t*>(mw + A.mel_nnz);
+    int32_t* mcnt = mlo + A.mel_M;
+    int32_t* moff = mcnt + A.mel_M;
+    if (MEL) {
+        for (int i = threadIdx.x; i < A.mel_M; i += 256) {
+            mlo[i] = A.mel_lo[i];
+            mcnt[i] = A.mel_cnt[i];
+            moff[i] = A.mel_off[i];
+        }
+        for (int i = threadIdx.x; i < A.mel_nnz; i += 256) mw[i] = A.mel_w[i];
+    }
+
+    const int lane = threadIdx.x & 63;
+    const float es = A.edge_scale;
+
+    load_tables_w<PL>(S, A.window, A.twiddle, A.g.L, threadIdx.x, 256);
+    __syncthreads();
+
+    wave_pipeline<PL, true>(A, S, A.dbg, [&](int b, int tw0, int frames_b, cpx* wbuf) {
         const int nfr = min(FPW, (int)A.out_frames - tw0);
         if (MEL) {
             // |X[k]|^power of all pairs into registers, then written DENSELY (frame f at float offset
@@ -525,8 +438,7 @@ __global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES
                 }
                 orow[o] = A.mel_log ? logf(acc + A.mel_eps) : acc;
             }
-            wave_sync();   // the next item's transposition reuses wbuf
-            continue;
+            return;
         }
         float* __restrict__ orow = A.out + ((long long)b * A.out_frames + tw0) * (2 * F);
         const bool fast = nfr == FPW && tw0 + FPW <= frames_b && es == 1.f &&
@@ -579,8 +491,7 @@ __global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES
                 }
             }
         }
-        wave_sync();   // the next item's transposition reuses wbuf
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -589,6 +500,10 @@ __global__ __launch_bounds__(256, (MEL && PL::INV_WAVES > 2) ? 2 : PL::INV_WAVES
 // and keeps the unit phasors of Y in its private LDS slice, then each source, forming
 // cos(angle(Y) - angle(X)) = Re(y_hat conj x_hat)  (angle(0) := 0 like np.angle) on the way out.
 // (mag_phasor: phasor.h)
+// The loop is wave_pipeline's with K + 1 signals per item and frame-group major items, written out here: with this epilogue handed
+// to wave_pipeline as a callable the compiler optimises it as a function of its own before it is inlined, and the 512-point
+// instantiation came out with 174 registers for 169, 36 more instructions and 3.5 % more time (measured; wrapping this epilogue in a
+// lambda inside the kernel alone does it).  Under PTMI_STFT_DBG bit 2 this kernel skips the FFT and writes nothing into wbuf.
 template <class PL>
 __global__ __launch_bounds__(256, 2) void pit_features_kernel(const FwdArgs A) {
     constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
@@ -793,7 +708,7 @@ __global__ __launch_bounds__(256, 2) void pit_features_kernel(const FwdArgs A) {
 
 // ------------------------------------------------------------------------------------------------
 // Griffin-Lim (griffin_lim.hip): the forward STFT of the audio with the WHOLE update of one iteration as its epilogue
-// (padertorch/contrib/mk/synthesis/parametric/griffin_lim.py:136-142).  The pipeline is stft_fwd_kernel's; where that one stores the
+// (padertorch/contrib/mk/synthesis/parametric/griffin_lim.py:136-142).  Where stft_fwd_kernel's epilogue stores the
 // spectrum x_, each lane here reads x[k] and a[k] at the very address, forms y = x_ + alpha (x_ - x), P = a y / |y| and (|x_| - a)^2
 // from the spectrum still in LDS, and stores x_ over x (in place: the lane that reads a bin is the one that writes it, and no other
 // lane touches it) and P.  36 bytes per bin and iteration instead of the 64 of stft + gl_update_kernel.  Every wavefront adds its
@@ -809,46 +724,18 @@ struct GlArgs {
 
 template <class PL>
 __global__ __launch_bounds__(256, PL::INV_WAVES > 2 ? 2 : PL::INV_WAVES) void gl_stft_update_kernel(const FwdArgs A, const GlArgs G) {
-    constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
+    constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS;
     constexpr int NP = M / 2 + 1;   // bin pairs (k, M-k) per frame
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (G.state[0] != 0) return;    // grid-uniform
     const WaveLds<PL> S(smem, 4);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    const int fl = lane / LPF, l = lane - fl * LPF;
-    cpx* wbuf = S.buf + wave * FPW * FS;
     const float alpha = G.alpha;
 
     load_tables_w<PL>(S, A.window, A.twiddle, A.g.L, tid, 256);
     __syncthreads();
 
-    struct Item {
-        int b, tw0;
-        const float* xrow;
-        bool interior;
-    };
-    const int n_b = (int)A.num_samples;
-    const unsigned items = (unsigned)(A.batch * A.nchunks);
-    auto decode = [&](unsigned item) {
-        Item it;
-        it.b = (int)(item / (unsigned)A.nchunks);
-        it.tw0 = (int)(item - (unsigned)it.b * (unsigned)A.nchunks) * FPW;
-        it.xrow = A.x + (long long)it.b * A.x_row_stride;
-        const int x_first = it.tw0 * A.g.shift - A.g.pad_left;
-        const int x_last = (it.tw0 + FPW - 1) * A.g.shift - A.g.pad_left + PL::SIZE;
-        it.interior = A.aligned2 && x_first >= 0 && x_last <= n_b;   // wave-uniform
-        return it;
-    };
-    float2 pre[PL::R1];
-    auto issue = [&](const Item& it) {
-        const float2* __restrict__ px =
-            reinterpret_cast<const float2*>(it.xrow + it.tw0 * A.g.shift - A.g.pad_left + fl * A.g.shift) + l;
-        if (l < PL::R2) {
-#pragma unroll
-            for (int n1 = 0; n1 < PL::R1; ++n1) pre[n1] = px[PL::R2 * n1];
-        }
-    };
     // one bin: returns (|x_| - a)^2
     auto update = [&](cpx xn, cpx xo, float av, cpx& Pv) {
         const cpx y{xn.x + alpha * (xn.x - xo.x), xn.y + alpha * (xn.y - xo.y)};
@@ -860,31 +747,7 @@ __global__ __launch_bounds__(256, PL::INV_WAVES > 2 ? 2 : PL::INV_WAVES) void gl
         return d * d;
     };
     double wsum = 0.;
-    const unsigned stride = gridDim.x * 4;
-    unsigned item = blockIdx.x * 4 + wave;
-    Item cur = decode(item < items ? item : 0);
-    bool cur_pre = item < items && cur.interior;
-    if (cur_pre) issue(cur);
-    for (; item < items; item += stride) {
-        const int b = cur.b, tw0 = cur.tw0;
-        cpx a[PL::R1];
-        if (cur_pre) {
-            const cpx* pw = reinterpret_cast<const cpx*>(S.win) + l;
-            if (l < PL::R2) {
-#pragma unroll
-                for (int n1 = 0; n1 < PL::R1; ++n1) a[n1] = cpx{pre[n1].x, pre[n1].y} * pw[PL::R2 * n1];
-            }
-        } else {
-            load_frames<PL>(a, cur.xrow, n_b, tw0, fl, l, A.g, A.aligned2, S.win);
-        }
-        {
-            const unsigned nxt = item + stride;
-            cur = decode(nxt < items ? nxt : 0);
-            cur_pre = nxt < items && cur.interior;
-            if (cur_pre) issue(cur);
-        }
-        fft_to_lds_wave<PL, false>(a, wbuf + fl * FS, l, S.tw1t);
-
+    wave_pipeline<PL, false>(A, S, 0, [&](int b, int tw0, int, cpx* wbuf) {
         const int nfr = min(FPW, (int)A.out_frames - tw0);                  // frames of this item inside [0, out_frames)
         const long long base = ((long long)b * A.out_frames + tw0) * F;     // first bin of the item in x / a / P
         cpx* __restrict__ xr = G.x + base;
@@ -908,8 +771,7 @@ __global__ __launch_bounds__(256, PL::INV_WAVES > 2 ? 2 : PL::INV_WAVES) void gl
             }
         }
         wsum += (double)acc;        // per lane, item order; the lanes are folded once at the end
-        wave_sync();   // the next item's transposition reuses wbuf
-    }
+    });
     for (int o = 32; o >= 1; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
     if (lane == 0) G.partials[blockIdx.x * 4 + wave] = wsum;
     if (blockIdx.x == 0 && tid == 0) G.state[2] = (int32_t)(gridDim.x * 4);
@@ -947,32 +809,6 @@ struct InvArgs {
 // (deterministic, no atomics).  Spectra of interior groups are fetched one group AHEAD into
 // registers (FPW consecutive rows = one contiguous chunk), hiding HBM latency behind FFT + OLA.
 template <class PL>
-__device__ __forceinline__ void ifft_windowed_to_lds_wave(cpx (&a)[PL::R1], cpx* fbuf, int l,
-                                                          const cpx* tw1t, const cpx* wsyn2) {
-    constexpr int R1 = PL::R1, R2 = PL::R2, P = PL::P;
-    if (l < R2) {
-        fft_dif<R1, true>(a);
-#pragma unroll
-        for (int k1 = 0; k1 < R1; ++k1) fbuf[k1 * P + l] = cmulc(a[bitrev<R1>(k1)], tw1t[k1 * PL::LPF + l]);
-    }
-    wave_sync();
-    cpx c[R2];
-    if (l < R1) {
-#pragma unroll
-        for (int n2 = 0; n2 < R2; ++n2) c[n2] = fbuf[l * P + n2];
-    }
-    wave_sync();
-    if (l < R1) {
-        fft_dif<R2, true>(c);
-#pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) {   // z[n] = x[2n] + i x[2n+1], times the window pair
-            fbuf[l + R1 * k2] = c[bitrev<R2>(k2)] * wsyn2[l + R1 * k2];
-        }
-    }
-    wave_sync();
-}
-
-template <class PL>
 __global__ __launch_bounds__(256, PL::INV_WAVES) void istft_kernel(const InvArgs A) {
     constexpr int M = PL::M, F = PL::F, FPW = PL::FPW, FS = PL::FS, LPF = PL::LPF;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -990,12 +826,7 @@ __global__ __launch_bounds__(256, PL::INV_WAVES) void istft_kernel(const InvArgs
     cpx* wbuf = bufs + wave * FPW * FS;
     float* ring0 = rings + wave * 2 * plen_pad;
 
-    for (int i = tid; i <= M; i += 256) tws[i] = A.twiddle[i];
-    for (int i = tid; i < PL::SIZE; i += 256) wsyn[i] = (i < L) ? A.syn_window[i] : 0.f;
-    for (int i = tid; i < PL::R1 * LPF; i += 256) {
-        const int k1 = i / LPF, ll = i - k1 * LPF;
-        tw1t[i] = tw_full<M>(A.twiddle, (2 * ll * k1) % PL::SIZE);
-    }
+    load_tables_w<PL>(WaveLds<PL>(smem, 4), A.syn_window, A.twiddle, L, tid, 256);
     __syncthreads();
 
     const int span = (FPW - 1) * shift + L;             // samples a group of FPW frames touches
@@ -1088,7 +919,7 @@ __global__ __launch_bounds__(256, PL::INV_WAVES) void istft_kernel(const InvArgs
                     a[i1] = v;
                 }
                 wave_sync();   // every lane has consumed raw before the transposition overwrites it
-                ifft_windowed_to_lds_wave<PL>(a, wbuf + fl * FS, l, tw1t, reinterpret_cast<const cpx*>(wsyn));
+                fft_to_lds_wave<PL, true, true>(a, wbuf + fl * FS, l, tw1t, reinterpret_cast<const cpx*>(wsyn));
             }
             // (c) overlap-add: wbuf viewed as floats holds windowed frame f at [f * 2 FS, f * 2 FS + size).
             // Frame f reaches group position p with its sample j = p - f * shift if 0 <= j < L.  Positions
@@ -1291,8 +1122,6 @@ __global__ __launch_bounds__(256) void istft_generic_kernel(const InvArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
-
-
 constexpr size_t kMaxSmem = 64 * 1024;  // keep >= 2 workgroups per CU (160 KiB LDS)
 
 // Workgroups of `Kernel` that stay resident per CU (registers AND LDS), cached per thread.
@@ -1309,71 +1138,78 @@ static int blocks_per_cu(int threads, size_t smem) {
     return blocks;
 }
 
+// The opt-in to more than kMaxSmem of LDS (the 2048-point plans at 92 KB, large filterbanks), then the resident workgroups per CU.
+template <auto Kernel>
+static hipError_t persistent_residency(size_t smem, int& per_cu) {
+    if (smem > kMaxSmem) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return e;
+    }
+    per_cu = blocks_per_cu<Kernel>(256, smem);
+    return hipSuccess;
+}
+
+// One launch of a persistent wavefront kernel (256 threads; every wavefront takes one work item at a time).  In this order: the LDS
+// bytes against the CU's 160 KB, nothing to do, an item count beyond `int`, the residency (per_cu: what the caller has asked for
+// already, else 0), and a grid of as many workgroups as stay resident - never more than needed, or than `cap`.
+constexpr long long kNoCap = 0x7fffffffLL;
+
+template <auto Kernel, class... Args>
+static int launch_persistent(long long items, size_t smem, long long cap, int per_cu, hipStream_t st, const Args&... args) {
+    if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
+    if (items <= 0) return PTMI_OK;
+    if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
+    if (per_cu < 1) {
+        hipError_t e = persistent_residency<Kernel>(smem, per_cu);
+        if (e != hipSuccess) return (int)e;
+    }
+    const long long blocks = std::min(std::min((items + 3) / 4, 256LL * per_cu), cap);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(256), smem, st, args...);
+    return launch_status();
+}
+
+// size -> fn(Plan<R1, R2>{}) for the sizes that have a register-FFT plan
+template <class Fn>
+static int with_plan(int size, Fn&& fn) {
+    switch (size) {
+        case 64: return fn(Plan<4, 8>{});
+        case 128: return fn(Plan<8, 8>{});
+        case 256: return fn(Plan<8, 16>{});
+        case 512: return fn(Plan<16, 16>{});
+        case 1024: return fn(Plan<16, 32>{});
+        case 2048: return fn(Plan<32, 32>{});
+        default: return PTMI_E_UNSUPPORTED;
+    }
+}
+
+// What every forward launch derives from its arguments: whether every frame start is 8-byte aligned, and the work items
+// (FPW frames of one row each); returns their number.
 template <class PL>
-static int launch_fwd(FwdArgs& A, long long batch, bool features, hipStream_t st) {
-    // read at EVERY launch, by the plan kernels only: tests/test_gpu_spectral_gates.py (test_size_2048_forward_runs_its_plan) tells
-    // a plan kernel from the direct-DFT fallback by flipping bit 2 between two calls - do not cache it
-    const char* dbg_env = getenv("PTMI_STFT_DBG");
-    A.dbg = dbg_env ? atoi(dbg_env) : 0;
+static long long plan_items(FwdArgs& A, long long batch) {
     A.aligned2 = (A.x_row_stride % 2 == 0) && (A.g.shift % 2 == 0) && (A.g.pad_left % 2 == 0) &&
                  (reinterpret_cast<uintptr_t>(A.x) % 8 == 0) &&
                  (!A.s || reinterpret_cast<uintptr_t>(A.s) % 8 == 0);
-    if (!features) {
-        const bool mel = A.mel_w != nullptr;
-        const size_t smem = WaveLds<PL>::bytes(4, 0) + (mel ? 16 + sizeof(int32_t) * 3 * A.mel_M + sizeof(float) * A.mel_nnz : 0);
-        if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
-        A.batch = batch;
-        A.nchunks = (int)((A.out_frames + PL::FPW - 1) / PL::FPW);      // work items per row
-        const long long items = batch * A.nchunks;
-        if (items <= 0) return PTMI_OK;
-        if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
-        if (smem > kMaxSmem) {   // the 2048-point plan (92 KB) and large filterbanks: opt in like the features branch and launch_inv
-            const void* fn = mel ? reinterpret_cast<const void*>(stft_fwd_kernel<PL, true>)
-                                 : reinterpret_cast<const void*>(stft_fwd_kernel<PL, false>);
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        // persistent grid: as many workgroups as stay resident (LDS bound), never more than needed
-        if (mel) {
-            const long long resident = 256LL * blocks_per_cu<stft_fwd_kernel<PL, true>>(256, smem);
-            hipLaunchKernelGGL((stft_fwd_kernel<PL, true>), dim3((unsigned)std::min((items + 3) / 4, resident)),
-                               dim3(256), smem, st, A);
-        } else {
-            const long long resident = 256LL * blocks_per_cu<stft_fwd_kernel<PL, false>>(256, smem);
-            hipLaunchKernelGGL((stft_fwd_kernel<PL, false>), dim3((unsigned)std::min((items + 3) / 4, resident)),
-                               dim3(256), smem, st, A);
-        }
-        return launch_status();
-    }
-    const size_t smem = WaveLds<PL>::bytes(4, 4);
     A.batch = batch;
-    A.nchunks = (int)((A.out_frames + PL::FPW - 1) / PL::FPW);          // work items per example
-    const long long items = batch * A.nchunks;
-    if (items <= 0) return PTMI_OK;
-    if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
-    if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
-    if (smem > kMaxSmem) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pit_features_kernel<PL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
-    const long long resident = 256LL * blocks_per_cu<pit_features_kernel<PL>>(256, smem);
-    const long long blocks = std::min((items + 3) / 4, resident);
-    hipLaunchKernelGGL(pit_features_kernel<PL>, dim3((unsigned)blocks), dim3(256), smem, st, A);
-    return launch_status();
+    A.nchunks = (int)((A.out_frames + PL::FPW - 1) / PL::FPW);
+    return batch * A.nchunks;
 }
 
 static int dispatch_fwd(FwdArgs& A, long long batch, bool features, hipStream_t st) {
     if (A.g.L > A.g.size) return PTMI_E_INVALID;
-    switch (A.g.size) {
-        case 64: return launch_fwd<Plan<4, 8>>(A, batch, features, st);
-        case 128: return launch_fwd<Plan<8, 8>>(A, batch, features, st);
-        case 256: return launch_fwd<Plan<8, 16>>(A, batch, features, st);
-        case 512: return launch_fwd<Plan<16, 16>>(A, batch, features, st);
-        case 1024: return launch_fwd<Plan<16, 32>>(A, batch, features, st);
-        case 2048: return launch_fwd<Plan<32, 32>>(A, batch, features, st);
-        default: return PTMI_E_UNSUPPORTED;
-    }
+    // read at EVERY launch, by the plan kernels only: tests/test_gpu_spectral_gates.py (test_size_2048_forward_runs_its_plan) tells
+    // a plan kernel from the direct-DFT fallback by flipping bit 2 between two calls - do not cache it
+    const char* dbg_env = getenv("PTMI_STFT_DBG");
+    A.dbg = dbg_env ? atoi(dbg_env) : 0;
+    return with_plan(A.g.size, [&](auto pl) {
+        using PL = decltype(pl);
+        const long long items = plan_items<PL>(A, batch);
+        // (the helper looks at the LDS bytes before the item count; here no plan exceeds them, so nothing is reordered)
+        static_assert(WaveLds<PL>::bytes(4, 4) <= 160 * 1024, "features: LDS of this plan");
+        if (features) return launch_persistent<pit_features_kernel<PL>>(items, WaveLds<PL>::bytes(4, 4), kNoCap, 0, st, A);
+        if (!A.mel_w) return launch_persistent<stft_fwd_kernel<PL, false>>(items, WaveLds<PL>::bytes(4, 0), kNoCap, 0, st, A);
+        const size_t smem = WaveLds<PL>::bytes(4, 0) + 16 + sizeof(int32_t) * 3 * A.mel_M + sizeof(float) * A.mel_nnz;
+        return launch_persistent<stft_fwd_kernel<PL, true>>(items, smem, kNoCap, 0, st, A);
+    });
 }
 
 template <class PL>
@@ -1381,14 +1217,10 @@ static int launch_inv(InvArgs& A, long long batch, hipStream_t st) {
     const int shift = A.g.shift, L = A.g.L;
     A.halo = (L + shift - 1) / shift - 1;
     const int plen_pad = std::max((std::max(L - shift, 0) + 3) & ~3, 4);
-    const size_t smem = sizeof(cpx) * (PL::F + 1 + PL::R1 * PL::LPF + (size_t)4 * PL::FPW * PL::FS) +
-                        sizeof(float) * (PL::SIZE + (size_t)4 * 2 * plen_pad);
+    const size_t smem = WaveLds<PL>::bytes(4, 0) + sizeof(float) * ((size_t)4 * 2 * plen_pad);    // + the wavefronts' rings
     if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
-    if (smem > kMaxSmem &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(istft_kernel<PL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return PTMI_E_UNSUPPORTED;
-    const int per_cu = blocks_per_cu<istft_kernel<PL>>(256, smem);
+    int per_cu = 0;
+    if (persistent_residency<istft_kernel<PL>>(smem, per_cu) != hipSuccess) return PTMI_E_UNSUPPORTED;
     const long long resident_waves = 256LL * per_cu * 4;
     // a run owns `run_hops` hops; it walks halo frames before them (their tails reach into the run)
     // and is done when its last owned hop is final (frames past the row's end read as zeros, which
@@ -1396,9 +1228,8 @@ static int launch_inv(InvArgs& A, long long batch, hipStream_t st) {
     // would otherwise not fill the chip.
     const long long total = A.cut_left + A.out_samples;                 // OLA samples needed
     const int min_hops = std::max(2 * PL::FPW, 2 * A.halo);
-    // the run length with the smallest (rounds of the resident wavefronts) x (frames a run walks = its hops + the halo): round 6 -
-    // until then 64 hops unless the call did not fill the chip; 1536 x 64000 samples took 4 rounds of 67 frames where 1 round of
-    // 259 does (-3 %)
+    // the run length with the smallest (rounds of the resident wavefronts) x (frames a run walks = its hops + the halo): a fixed
+    // 64 hops took 4 rounds of 67 frames for 1536 x 64000 samples where 1 round of 259 does (-3 %)
     int run_hops = min_hops;
     long long best = -1;
     for (int rh = min_hops; rh <= 1024; rh *= 2) {
@@ -1417,61 +1248,23 @@ static int launch_inv(InvArgs& A, long long batch, hipStream_t st) {
     A.dbg = dbg_env ? atoi(dbg_env) : 0;
     A.batch = batch;
     A.nchunks = (int)((total + (long long)A.run_hops * shift - 1) / ((long long)A.run_hops * shift));
-    const long long items = batch * A.nchunks;
-    if (items <= 0) return PTMI_OK;
-    if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
-    const long long blocks = std::min((items + 3) / 4, 256LL * per_cu);
-    hipLaunchKernelGGL(istft_kernel<PL>, dim3((unsigned)blocks), dim3(256), smem, st, A);
-    return launch_status();
+    return launch_persistent<istft_kernel<PL>>(batch * A.nchunks, smem, kNoCap, per_cu, st, A);
 }
 
 static int dispatch_inv(InvArgs& A, long long batch, hipStream_t st) {
     if (A.g.L > A.g.size) return PTMI_E_INVALID;
-    switch (A.g.size) {
-        case 64: return launch_inv<Plan<4, 8>>(A, batch, st);
-        case 128: return launch_inv<Plan<8, 8>>(A, batch, st);
-        case 256: return launch_inv<Plan<8, 16>>(A, batch, st);
-        case 512: return launch_inv<Plan<16, 16>>(A, batch, st);
-        case 1024: return launch_inv<Plan<16, 32>>(A, batch, st);
-        case 2048: return launch_inv<Plan<32, 32>>(A, batch, st);
-        default: return PTMI_E_UNSUPPORTED;
-    }
+    return with_plan(A.g.size, [&](auto pl) { return launch_inv<decltype(pl)>(A, batch, st); });
 }
 
 constexpr int kGlMaxBlocks = 4096;   // 4 partials per workgroup <= ptmi_gl_partials_elems()
 
-template <class PL>
-static int launch_gl(FwdArgs& A, const GlArgs& G, long long batch, hipStream_t st) {
-    A.dbg = 0;
-    A.aligned2 = (A.x_row_stride % 2 == 0) && (A.g.shift % 2 == 0) && (A.g.pad_left % 2 == 0) &&
-                 (reinterpret_cast<uintptr_t>(A.x) % 8 == 0);
-    const size_t smem = WaveLds<PL>::bytes(4, 0);
-    if (smem > 160 * 1024) return PTMI_E_UNSUPPORTED;
-    A.batch = batch;
-    A.nchunks = (int)((A.out_frames + PL::FPW - 1) / PL::FPW);
-    const long long items = batch * A.nchunks;
-    if (items > 0x7fffffffLL) return PTMI_E_UNSUPPORTED;
-    if (smem > kMaxSmem) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gl_stft_update_kernel<PL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
-    const long long resident = 256LL * blocks_per_cu<gl_stft_update_kernel<PL>>(256, smem);
-    const long long blocks = std::min(std::min((items + 3) / 4, resident), (long long)kGlMaxBlocks);
-    hipLaunchKernelGGL(gl_stft_update_kernel<PL>, dim3((unsigned)blocks), dim3(256), smem, st, A, G);
-    return launch_status();
-}
-
 static int dispatch_gl(FwdArgs& A, const GlArgs& G, long long batch, hipStream_t st) {
-    switch (A.g.size) {
-        case 64: return launch_gl<Plan<4, 8>>(A, G, batch, st);
-        case 128: return launch_gl<Plan<8, 8>>(A, G, batch, st);
-        case 256: return launch_gl<Plan<8, 16>>(A, G, batch, st);
-        case 512: return launch_gl<Plan<16, 16>>(A, G, batch, st);
-        case 1024: return launch_gl<Plan<16, 32>>(A, G, batch, st);
-        case 2048: return launch_gl<Plan<32, 32>>(A, G, batch, st);
-        default: return PTMI_E_UNSUPPORTED;
-    }
+    A.dbg = 0;
+    return with_plan(A.g.size, [&](auto pl) {
+        using PL = decltype(pl);
+        const long long items = plan_items<PL>(A, batch);
+        return launch_persistent<gl_stft_update_kernel<PL>>(items, WaveLds<PL>::bytes(4, 0), kGlMaxBlocks, 0, st, A, G);
+    });
 }
 
 // Mel filterbank (+ log) of a given spectrogram [N, F] -> [N, M] (MelTransform.forward,
@@ -1531,6 +1324,23 @@ __global__ __launch_bounds__(256) void mel_apply_kernel(const MelArgs A) {
     }
 }
 
+// What the forward entry points share of the kernel arguments
+static FwdArgs fwd_args(const float* x, const int32_t* row_samples, const float* window, const float* twiddle, int64_t x_row_stride,
+                        int64_t num_samples, int64_t out_frames, int32_t layout, float edge_scale, const ptmi_stft_geom* g) {
+    FwdArgs A{};
+    A.x = x;
+    A.row_samples = row_samples;
+    A.window = window;
+    A.twiddle = reinterpret_cast<const cpx*>(twiddle);
+    A.x_row_stride = x_row_stride;
+    A.num_samples = num_samples;
+    A.out_frames = out_frames;
+    A.layout = layout;
+    A.edge_scale = edge_scale;
+    A.g = to_geo(g);
+    return A;
+}
+
 static bool geom_ok(const ptmi_stft_geom* g) {
     return g && g->size >= 2 && (g->size % 2 == 0) && g->shift >= 1 && g->window_length >= 1 &&
            g->pad_left >= 0 && g->pad_right >= 0;
@@ -1562,18 +1372,8 @@ int ptmi_stft_forward(const float* x, int64_t batch, int64_t x_row_stride, int64
     PTMI_RETURN_IF(g->window_length > g->size, PTMI_E_INVALID);
     PTMI_RETURN_IF(num_samples > 0x7ff00000LL || out_frames > 0x7ff00000LL / (g->size + 2), PTMI_E_UNSUPPORTED);
     if (batch == 0 || out_frames == 0) return PTMI_OK;
-    FwdArgs A{};
-    A.x = x;
-    A.row_samples = row_samples;
-    A.window = window;
-    A.twiddle = reinterpret_cast<const cpx*>(twiddle);
+    FwdArgs A = fwd_args(x, row_samples, window, twiddle, x_row_stride, num_samples, out_frames, layout, edge_scale, g);
     A.out = out;
-    A.x_row_stride = x_row_stride;
-    A.num_samples = num_samples;
-    A.out_frames = out_frames;
-    A.layout = layout;
-    A.edge_scale = edge_scale;
-    A.g = to_geo(g);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = dispatch_fwd(A, batch, false, st);
     if (rc != PTMI_E_UNSUPPORTED) return rc;
@@ -1596,18 +1396,8 @@ int ptmi_stft_logmel(const float* x, int64_t batch, int64_t x_row_stride, int64_
     PTMI_RETURN_IF(g->window_length > g->size, PTMI_E_INVALID);
     PTMI_RETURN_IF(num_samples > 0x7ff00000LL || out_frames > 0x7ff00000LL / (g->size + 2), PTMI_E_UNSUPPORTED);
     if (batch == 0 || out_frames == 0) return PTMI_OK;
-    FwdArgs A{};
-    A.x = x;
-    A.row_samples = row_samples;
-    A.window = window;
-    A.twiddle = reinterpret_cast<const cpx*>(twiddle);
+    FwdArgs A = fwd_args(x, row_samples, window, twiddle, x_row_stride, num_samples, out_frames, PTMI_LAYOUT_INTERLEAVED, 1.f, g);
     A.out = out;
-    A.x_row_stride = x_row_stride;
-    A.num_samples = num_samples;
-    A.out_frames = out_frames;
-    A.layout = PTMI_LAYOUT_INTERLEAVED;
-    A.edge_scale = 1.f;
-    A.g = to_geo(g);
     A.mel_lo = mel_lo;
     A.mel_cnt = mel_cnt;
     A.mel_off = mel_off;
@@ -1685,21 +1475,12 @@ int ptmi_pit_features_packed(const float* y, const float* s, int64_t batch, int3
     PTMI_RETURN_IF(batch < 0 || out_frames < 0, PTMI_E_INVALID);
     PTMI_RETURN_IF(num_samples > 0x7ff00000LL || out_frames > 0x7ff00000LL / (g->size + 2), PTMI_E_UNSUPPORTED);
     if (batch == 0 || out_frames == 0) return PTMI_OK;
-    FwdArgs A{};
-    A.x = y;
+    FwdArgs A = fwd_args(y, row_samples, window, twiddle, row_stride, num_samples, out_frames, PTMI_LAYOUT_INTERLEAVED, 1.f, g);
     A.s = s;
     A.K = K;
-    A.row_samples = row_samples;
-    A.window = window;
-    A.twiddle = reinterpret_cast<const cpx*>(twiddle);
     A.out = Y_abs;
     A.X_abs = X_abs;
     A.cos_pd = cos_pd;
-    A.x_row_stride = row_stride;
-    A.num_samples = num_samples;
-    A.out_frames = out_frames;
-    A.edge_scale = 1.f;
-    A.g = to_geo(g);
     A.lp_out = log1p_packed;
     A.lp_planes = reinterpret_cast<_Float16*>(log1p_planes);
     A.lp_offs = reinterpret_cast<const long long*>(packed_offsets);
@@ -1724,16 +1505,7 @@ int ptmi_gl_stft_update(const float* audio, int64_t batch, int64_t row_stride, i
     PTMI_RETURN_IF(batch <= 0 || frames <= 0 || g->window_length > g->size, PTMI_E_INVALID);
     PTMI_RETURN_IF(num_samples > 0x7ff00000LL || frames > 0x7ff00000LL / (g->size + 2), PTMI_E_UNSUPPORTED);
     PTMI_RETURN_IF(row_frames_of(to_geo(g), num_samples) != frames, PTMI_E_INVALID);     // STFT(audio) must give `frames` frames again
-    FwdArgs A{};
-    A.x = audio;
-    A.window = window;
-    A.twiddle = reinterpret_cast<const cpx*>(twiddle);
-    A.x_row_stride = row_stride;
-    A.num_samples = num_samples;
-    A.out_frames = frames;
-    A.layout = PTMI_LAYOUT_INTERLEAVED;
-    A.edge_scale = 1.f;
-    A.g = to_geo(g);
+    FwdArgs A = fwd_args(audio, nullptr, window, twiddle, row_stride, num_samples, frames, PTMI_LAYOUT_INTERLEAVED, 1.f, g);
     const GlArgs G{reinterpret_cast<cpx*>(x), a, reinterpret_cast<cpx*>(P), partials, state, alpha};
     return dispatch_gl(A, G, batch, static_cast<hipStream_t>(stream));   // PTMI_E_UNSUPPORTED: no register-FFT plan for this size
 }

@@ -18,6 +18,9 @@ Measured on an MI355X (``max r / max r32``, the worst case of each kernel; every
     features     2.61  (direct DFT, size 100, ``X_abs``; FFT plans: 1.41 at 2048; the weighted cosine: 1.11)
     fused mel    1.48  (64/16 with a hann window of 50 samples and 256/64 ragged, power 1; log outputs: 0.38 of their bound at most)
     mel_apply    0.48 of the derived bound at most
+    several items per wavefront (section 8: 64/16, 4 ragged rows of 655 377 samples, 20 484 work items):
+        forward 1.17;  features (K = 1) 1.23 (``X_abs``; ``Y_abs`` 1.11, the weighted cosine 0.38);  fused mel 1.08 (power 1; log
+        outputs 0.34 of their bound);  one fused Griffin-Lim step against the composed path: 0 of its gate (bit-identical ``x``)
 The one thing these tests found beside the 2048-point plan that never ran (its 92 KB of LDS needed the opt-in the launcher now
 makes): the device ``logf`` is not correctly rounded, see :func:`_log_eps`.
 """
@@ -262,13 +265,19 @@ def _cos_figure(cos, cos_want, Y_abs, X_abs):
 @pytest.mark.parametrize('K', [1, 3])
 @pytest.mark.parametrize('size', [64, 512, 2048, 100])
 def test_pit_features_ragged_with_nan_behind_the_rows(size, K):
-    from padertorch_amd.ops import pit_features
     shift = size // 4
     N = 5 * size + 17
     lens = [N, N - 1, size + 1]
     rng = np.random.RandomState(size + K)
     s = rng.standard_normal((3, K, N)).astype(np.float32)
     y = (s.sum(1) + 0.5 * rng.standard_normal((3, N))).astype(np.float32)
+    _check_features(y, s, lens, size, shift, f'features {size}/{shift} K={K}')
+
+
+def _check_features(y, s, lens, size, shift, what):
+    """``pit_features`` of the mixtures ``y [B, W]`` and sources ``s [B, K, W]`` with ``lens`` live samples per row, NaN behind them."""
+    from padertorch_amd.ops import pit_features
+    (B, K, W) = s.shape
     sf, yf = s.copy(), y.copy()
     for b, n in enumerate(lens):
         sf[b, :, n:] = np.nan
@@ -276,9 +285,9 @@ def test_pit_features_ragged_with_nan_behind_the_rows(size, K):
     kw = _kw()
     f = pit_features(_dev(yf), _dev(sf), num_samples=lens, stft=_stft(size, shift, kw))
     Yg, Xg, Cg = (f[k].padded.cpu().numpy() for k in ('Y_abs', 'X_abs', 'cos_phase_difference'))
-    T = stft_np.num_frames(N, size, shift, 'full', True)
+    T = stft_np.num_frames(max(lens), size, shift, 'full', True)
     F = size // 2 + 1
-    assert Yg.shape == (3, T, F) and Xg.shape == Cg.shape == (3, T, K, F)
+    assert W >= max(lens) and Yg.shape == (B, T, F) and Xg.shape == Cg.shape == (B, T, K, F)
     Yw, Y32 = np.zeros(Yg.shape), np.zeros(Yg.shape, np.float32)
     Xw, X32 = np.zeros(Xg.shape), np.zeros(Xg.shape, np.float32)
     q = q32 = 0.
@@ -296,9 +305,9 @@ def test_pit_features_ragged_with_nan_behind_the_rows(size, K):
         assert np.isfinite(Cg[b]).all() and (Cg[b, Tb:] == 0).all()
         q = max(q, _cos_figure(Cg[b, :Tb], r['cos_phase_difference'], r['Y_abs'], r['X_abs']))
         q32 = max(q32, _cos_figure(cos32, r['cos_phase_difference'], r['Y_abs'], r['X_abs']))
-    G.check(Yg, Yw, Y32, f'features {size}/{shift} K={K} Y_abs')
-    G.check(Xg, Xw, X32, f'features {size}/{shift} K={K} X_abs')
-    print(f'gate features {size}/{shift} K={K} cos: max q {q:.3e}  max q32 {q32:.3e}  ratio {q / q32:.2f} (margin {G.MARGIN})')
+    G.check(Yg, Yw, Y32, f'{what} Y_abs')
+    G.check(Xg, Xw, X32, f'{what} X_abs')
+    print(f'gate {what} cos: max q {q:.3e}  max q32 {q32:.3e}  ratio {q / q32:.2f} (margin {G.MARGIN})')
     assert q <= G.MARGIN * q32, (q, q32)
 
 
@@ -399,9 +408,10 @@ def test_mel_transform_dense_user_filterbank(stft_size):
 
 
 # ------------------------------------------------------------------------------------------------ 7. fused stft_logmel
-def _check_logmel(x, lens, size, shift, kw, mel_kw, what, xd=None):
+def _check_logmel(x, lens, size, shift, kw, mel_kw, what, xd=None, spectra=None):
     """All of ``power`` in (1, 2) x ``log`` on / off of one (signal, STFT, filterbank) case; ``lens``: ragged lengths or None;
-    ``xd``: the device tensor to feed (default: a fresh copy of the signal)."""
+    ``xd``: the device tensor to feed (default: a fresh copy of the signal); ``spectra``: the case's (fp64 oracle, fp32 restatement)
+    where a test has them already."""
     from padertorch_amd.contrib.je.modules.features import MelTransform, stft_logmel
     st = _stft(size, shift, kw)
     B, N = x.shape
@@ -411,8 +421,11 @@ def _check_logmel(x, lens, size, shift, kw, mel_kw, what, xd=None):
         X64, X32 = stft_np.stft(x, size, shift, **kw), G.stft32(x, size, shift, **kw)
         xf, live = x, np.ones((B, T), bool)
     else:
-        X64 = _ragged_rows(lambda r: stft_np.stft(r, size, shift, **kw), x, lens, T, (F,), np.complex128)
-        X32 = _ragged_rows(lambda r: G.stft32(r, size, shift, **kw), x, lens, T, (F,), np.complex64)
+        if spectra is not None:
+            X64, X32 = spectra
+        else:
+            X64 = _ragged_rows(lambda r: stft_np.stft(r, size, shift, **kw), x, lens, T, (F,), np.complex128)
+            X32 = _ragged_rows(lambda r: G.stft32(r, size, shift, **kw), x, lens, T, (F,), np.complex64)
         xf = x.copy()
         live = np.zeros((B, T), bool)
         for b, n in enumerate(lens):
@@ -498,7 +511,106 @@ def test_logmel_dense_user_filterbank(size):
     _check_logmel(x, None, size, shift, kw, dict(number_of_filters=16, fbanks=dense), f'{size}/{shift} dense')
 
 
-# ------------------------------------------------------------------------------------------------ 8. what cannot fit says so
+# ------------------------------------------------------------------------------------------------ 8. a wavefront that takes several items
+# The cases above give every wavefront of the forward kernels at most one work item (FPW frames of one row).  A CU holds at most 8
+# wavefronts per SIMD, 256 CUs at most 8192 whatever a kernel's occupancy, so the 20 484 items of these shapes give every wavefront
+# two or three: the prefetch carried from item to item, the hand-over between interior and edge items and the run past the last
+# item.  Size 64 / shift 16 (8 frames per item); 4 rows of N = 655 377 samples (odd) in N + 1 columns (an even stride: the 8-byte
+# loads and the separately fetched last sample), NaN behind every row's end; the lengths make interior, edge and all-past-the-end
+# items alternate within a wavefront's stride.
+MULTI = dict(size=64, shift=16, N=655377)
+
+
+def _multi_lengths():
+    N = MULTI['N']
+    return [N, N - 1, N // 2 + 3, 5]
+
+
+@pytest.fixture(scope='module')
+def multi_case():
+    """(x float32 [4, N + 1], lengths, frames of the buffer, want complex128, ref32 complex64): computed once for this module's
+    cases, read-only, released with the module (about 130 MB)."""
+    size, shift, N = MULTI['size'], MULTI['shift'], MULTI['N']
+    lens = _multi_lengths()
+    kw = _kw()
+    x = np.random.RandomState(N).standard_normal((len(lens), N + 1)).astype(np.float32)
+    T = stft_np.num_frames(N + 1, size, shift, 'full', True)
+    F = size // 2 + 1
+    want = _ragged_rows(lambda r: stft_np.stft(r, size, shift, **kw), x, lens, T, (F,), np.complex128)
+    ref32 = _ragged_rows(lambda r: G.stft32(r, size, shift, **kw), x, lens, T, (F,), np.complex64)
+    assert len(lens) * ((T + 7) // 8) > 2 * 8192
+    for a in (x, want, ref32):
+        a.setflags(write=False)
+    return x, lens, T, want, ref32
+
+
+def _nan_behind(x, lens):
+    xf = x.copy()
+    for b, n in enumerate(lens):
+        xf[b, n:] = np.nan
+    return xf
+
+
+def test_multi_item_forward(multi_case):
+    size, shift = MULTI['size'], MULTI['shift']
+    x, lens, T, want, ref32 = multi_case
+    v = _dev(_nan_behind(x, lens))
+    assert v.data_ptr() % 8 == 0 and v.stride(0) % 2 == 0 and lens[0] % 2 == 1
+    X = _stft(size, shift, _kw())(v, num_samples=torch.tensor(lens, dtype=torch.int32, device=DEV)).cpu().numpy()
+    assert X.shape == want.shape and not np.isnan(X).any()
+    for b, n in enumerate(lens):
+        assert (X[b, stft_np.num_frames(n, size, shift, 'full', True):] == 0).all(), b
+    G.check(X, want, ref32, f'forward {size}/{shift} multi-item')
+
+
+def test_multi_item_pit_features(multi_case):
+    """K = 1: the same rows as mixtures, one array of sources.  The items go frame-group major, so the same lengths interleave
+    otherwise than in the forward kernel."""
+    size, shift = MULTI['size'], MULTI['shift']
+    x, lens, _, _, _ = multi_case
+    s = np.random.RandomState(MULTI['N'] + 1).standard_normal((len(lens), 1, x.shape[1])).astype(np.float32)
+    _check_features(x, s, lens, size, shift, f'features {size}/{shift} K=1 multi-item')
+
+
+def test_multi_item_logmel(multi_case):
+    size, shift = MULTI['size'], MULTI['shift']
+    x, lens, _, want, ref32 = multi_case
+    _check_logmel(x, lens, size, shift, _kw(), dict(number_of_filters=min(80, size // 4)), f'{size}/{shift} multi-item',
+                  spectra=(want, ref32))
+
+
+def test_multi_item_griffin_lim_step():
+    """One fused iteration (``gl_stft_update_kernel``) against the composed path, as ``tests/test_gpu_griffin_lim.py``
+    (``test_fused_against_composed``) compares them: 2e-4 max(a), the floor of its gate (one step is the forward and the inverse
+    STFT gate taken together), and the RMSE (the fp64 sum in item order over every wavefront's items) to 1e-4.  Both paths take
+    their STFT through the same ``wave_pipeline``, so an error in the carried prefetch or the interior / edge hand-over would cancel
+    here (``x`` comes out bit-identical): this case gates the Griffin-Lim epilogue and its item-order sum over several items only;
+    the pipeline itself is held against the fp64 oracle by ``test_multi_item_forward``."""
+    from padertorch_amd.contrib.mk.synthesis import fast_griffin_lim
+    from padertorch_amd.ops import griffin_lim as gl
+    size, shift, B, T = MULTI['size'], MULTI['shift'], 4, 40962
+    F = size // 2 + 1
+    rng = np.random.RandomState(T)
+    a = _dev(np.abs(rng.standard_normal((B, T, F))).astype(np.float32))
+    x0 = _dev((rng.standard_normal((B, T, F)) + 1j * rng.standard_normal((B, T, F))).astype(np.complex64))
+    st = _stft(size, shift, _kw())
+    out = {}
+    before = gl.PATH
+    try:
+        for path in ('fused', 'composed'):
+            gl.PATH = path
+            out[path] = fast_griffin_lim(a, st, alpha=0.99, iterations=1, atol=0., x=x0, return_info=True)[1]
+    finally:
+        gl.PATH = before
+    f, c = out['fused'], out['composed']
+    assert int(f.num_iterations) == int(c.num_iterations) == 1 and bool(torch.isfinite(f.x.abs()).all())
+    dev = float((f.x - c.x).abs().max()) / float(a.max())
+    rel = float(((f.rmse - c.rmse).abs() / c.rmse).max())
+    print(f'gate griffin-lim {size}/{shift} multi-item: fused vs composed {dev:.3g} (gate 2e-4), ratio {dev / 2e-4:.2f}; rmse {rel:.3g}')
+    assert dev <= 2e-4 and rel <= 1e-4
+
+
+# ------------------------------------------------------------------------------------------------ 9. what cannot fit says so
 def test_logmel_request_beyond_lds_names_lds():
     from padertorch_amd.contrib.je.modules.features import MelTransform, stft_logmel
     x, kw, _, _ = _case(1024, 256)
