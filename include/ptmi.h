@@ -872,6 +872,39 @@ int ptmi_gl_stft_update(const float* audio, int64_t batch, int64_t row_stride, i
 int ptmi_gl_finish(const double* partials, int64_t count, double atol, int32_t iteration, float* rmse, int32_t* state,
                    ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * BigVGAN's anti-aliased periodic activation (csrc/anti_alias.hip): replaces Activation1d, UpSample1d, DownSample1d, LowPassFilter1d of
+ * padertorch/contrib/mk/synthesis/vocoder/nvidia_bigvgan/alias_free_activation/torch/ and Snake / SnakeBeta of .../activations.py.
+ * x [B, C, T] fp32 contiguous -> y [B, C, M]; one pass: the up-sampled signal stays on chip.
+ *
+ *   up   (up_filter [up_taps] != NULL)    u[n] = r sum_j x[clamp(j - p)] f[n + pl - j r], n < r T; p = k / r - 1, pl = p r + (k - r) / 2
+ *   act  (act = 1; alpha, beta [C])       a = u + sin^2(alpha' u) / (beta' + 1e-9); alpha' = exp(alpha) if logscale
+ *   down (down_filter [down_taps] != NULL) y[m] = sum_i g[i] a[clamp(m d + i - left)]; padding: left = k / 2 - (k even), M = ceil(U / d);
+ *                                         padding = 0: left = 0, no clamp, M = (U - k) / d + 1
+ * A NULL filter switches its stage off (its ratio and taps are ignored); act = 0 makes a = u.  Snake passes beta = alpha.
+ * Limits: ratios 1 .. 8, 1 .. 64 taps, up_taps >= up_ratio, r T < 2^30 (PTMI_E_UNSUPPORTED beyond).
+ *
+ * ptmi_anti_alias_tile            : outputs (forward) / input samples (backward) one workgroup owns: the default geometry (2, 12, 2, 12,
+ *                                   padded) is a compile-time specialisation with a tile of its own
+ * ptmi_anti_alias_out_len         : M (-1: unsupported geometry)
+ * ptmi_anti_alias_workspace_elems : doubles of `workspace` (per-workgroup partials of the parameter gradients)
+ * ptmi_anti_alias_backward        : dx [B, C, T] (gather form, u recomputed from x); dalpha / dbeta [C] fp32 when dalpha != NULL: summed in
+ *                                   fp64 in one fixed order, no atomics; dbeta == NULL adds both sums into dalpha (Snake).  dalpha == NULL
+ *                                   skips the parameter gradients and the workspace.
+ * The launches neither allocate nor synchronise.
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_anti_alias_tile(int32_t default_geometry);
+int64_t ptmi_anti_alias_out_len(int64_t T, int32_t up_ratio, int32_t up_taps, int32_t down_ratio, int32_t down_taps, int32_t padding);
+int64_t ptmi_anti_alias_workspace_elems(int64_t B, int32_t C, int64_t T, int32_t up_ratio, int32_t up_taps, int32_t down_ratio,
+                                        int32_t down_taps, int32_t padding);
+int ptmi_anti_alias_forward(const float* x, const float* up_filter, const float* down_filter, const float* alpha, const float* beta,
+                            int64_t B, int32_t C, int64_t T, int32_t up_ratio, int32_t up_taps, int32_t down_ratio, int32_t down_taps,
+                            int32_t padding, int32_t act, int32_t logscale, float* y, ptmi_stream_t stream);
+int ptmi_anti_alias_backward(const float* dy, const float* x, const float* up_filter, const float* down_filter, const float* alpha,
+                             const float* beta, int64_t B, int32_t C, int64_t T, int32_t up_ratio, int32_t up_taps, int32_t down_ratio,
+                             int32_t down_taps, int32_t padding, int32_t act, int32_t logscale, float* dx, float* dalpha, float* dbeta,
+                             double* workspace, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -110,6 +110,13 @@ SIGNATURES = {
     'ptmi_gl_update': (c_int, [_P, _P, _P, c_int64, c_float, _P, _P, _P, _P]),
     'ptmi_gl_stft_update': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _G, c_int64, c_float, _P, _P, _P, _P, _P, _P]),
     'ptmi_gl_finish': (c_int, [_P, c_int64, c_double, c_int32, _P, _P, _P]),
+    'ptmi_anti_alias_tile': (c_int32, [c_int32]),
+    'ptmi_anti_alias_out_len': (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'ptmi_anti_alias_workspace_elems': (c_int64, [c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'ptmi_anti_alias_forward': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_int32, c_int32, _P, _P]),
+    'ptmi_anti_alias_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         c_int32, c_int32, _P, _P, _P, _P, _P]),
     'ptmi_bf_psd_workspace_elems': (c_int64, [c_int64, c_int32, c_int64, c_int64, c_int32]),
     'ptmi_bf_psd': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P]),
     'ptmi_bf_souden': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),

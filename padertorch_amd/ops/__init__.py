@@ -30,3 +30,5 @@ from . import mask_loss  # noqa: F401
 from .mask_loss import mask_bce_loss  # noqa: F401
 from . import griffin_lim  # noqa: F401
 from .griffin_lim import gl_project, gl_update, gl_iterations  # noqa: F401
+from . import anti_alias  # noqa: F401
+from .anti_alias import anti_alias_activation, kaiser_sinc_filter1d  # noqa: F401

@@ -35,6 +35,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                                               jensheit/evaluation.py:14-45)
     torch.ops.ptmi.mask_loss_forward / _backward   ptmi_mask_loss_*          (jensheit/mask_estimator_example/model.py:128-237)
     torch.ops.ptmi.gl_project / gl_project_backward / gl_update / gl_iterations   ptmi_gl_*   (contrib/mk/synthesis/parametric/griffin_lim.py:32-156)
+    torch.ops.ptmi.anti_alias_forward / _backward  ptmi_anti_alias_*         (contrib/mk/synthesis/vocoder/nvidia_bigvgan/alias_free_activation/torch,
+                                                                              nvidia_bigvgan/activations.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1367,3 +1369,58 @@ def gl_iterations(a, x, P, syn, window, twiddle, geom, samples, alpha, iteration
                    'ptmi_gl_finish')
         if poll > 0 and (it + 1) % poll == 0 and it + 1 < iterations and int(state[0].item()) != 0:
             break
+
+
+# ------------------------------------------------------------------------------------------------ anti-aliased activation (BigVGAN)
+def _aa_args(x, up_filter, down_filter, alpha, beta):
+    assert x.dim() == 3 and x.dtype == torch.float32 and x.is_contiguous(), (x.shape, x.dtype, x.is_contiguous())
+    C = x.shape[1]
+    for f in (up_filter, down_filter):
+        assert f is None or (f.dim() == 1 and f.dtype == torch.float32 and f.is_contiguous() and f.device == x.device), f
+    assert (alpha is None) == (beta is None)
+    for p in (alpha, beta):
+        assert p is None or (tuple(p.shape) == (C,) and p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device), p
+    return x.shape[0], C, x.shape[2], 0 if up_filter is None else up_filter.numel(), 0 if down_filter is None else down_filter.numel()
+
+
+@_register('anti_alias_forward(Tensor x, Tensor? up_filter, Tensor? down_filter, Tensor? alpha, Tensor? beta, int up_ratio, '
+           'int down_ratio, bool padding, bool logscale) -> Tensor')
+def anti_alias_forward(x, up_filter, down_filter, alpha, beta, up_ratio, down_ratio, padding, logscale):
+    """``x [B, C, T]`` -> ``[B, C, M]``: up-sampling by ``up_filter`` (None: off), Snake with ``alpha`` / ``beta [C]`` (None: off), low-pass
+    and decimation by ``down_filter`` (None: off), one launch (``ptmi_anti_alias_forward``; alias_free_activation/torch/act.py:25-30)."""
+    B, C, T, k, dk = _aa_args(x, up_filter, down_filter, alpha, beta)
+    lib = _lib.load()
+    M = lib.ptmi_anti_alias_out_len(T, up_ratio, k, down_ratio, dk, int(padding))
+    assert M >= 0, (T, up_ratio, k, down_ratio, dk, padding)
+    y = torch.empty((B, C, M), dtype=torch.float32, device=x.device)
+    if y.numel():
+        _lib.check(_lib.timed('anti_alias_forward', lib.ptmi_anti_alias_forward, x.data_ptr(), _lib.ptr(up_filter), _lib.ptr(down_filter),
+                              _lib.ptr(alpha), _lib.ptr(beta), B, C, T, up_ratio, k, down_ratio, dk, int(padding), int(alpha is not None),
+                              int(logscale), y.data_ptr(), _lib.stream(x.device)), 'ptmi_anti_alias_forward')
+    return y
+
+
+@_register('anti_alias_backward(Tensor dy, Tensor x, Tensor? up_filter, Tensor? down_filter, Tensor? alpha, Tensor? beta, int up_ratio, '
+           'int down_ratio, bool padding, bool logscale, int param_grads) -> (Tensor, Tensor, Tensor)')
+def anti_alias_backward(dy, x, up_filter, down_filter, alpha, beta, up_ratio, down_ratio, padding, logscale, param_grads):
+    """The adjoint of :func:`anti_alias_forward`: ``(dx, dalpha, dbeta)``.  ``param_grads`` 0: none (both empty), 1: one shared parameter
+    (Snake: both sums in ``dalpha``, ``dbeta`` empty), 2: ``alpha`` and ``beta`` (``ptmi_anti_alias_backward``)."""
+    B, C, T, k, dk = _aa_args(x, up_filter, down_filter, alpha, beta)
+    lib = _lib.load()
+    M = lib.ptmi_anti_alias_out_len(T, up_ratio, k, down_ratio, dk, int(padding))
+    assert dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (B, C, M), (dy.shape, dy.dtype, (B, C, M))
+    assert param_grads in (0, 1, 2) and (param_grads == 0 or alpha is not None)
+    dx = torch.empty_like(x)
+    dalpha = torch.empty(C if param_grads >= 1 else 0, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(C if param_grads == 2 else 0, dtype=torch.float32, device=x.device)
+    if M == 0 or dx.numel() == 0:
+        return dx.zero_(), dalpha.zero_(), dbeta.zero_()
+    ws = None
+    if param_grads:
+        ws = torch.empty(lib.ptmi_anti_alias_workspace_elems(B, C, T, up_ratio, k, down_ratio, dk, int(padding)), dtype=torch.float64,
+                         device=x.device)
+    _lib.check(_lib.timed('anti_alias_backward', lib.ptmi_anti_alias_backward, dy.data_ptr(), x.data_ptr(), _lib.ptr(up_filter),
+                          _lib.ptr(down_filter), _lib.ptr(alpha), _lib.ptr(beta), B, C, T, up_ratio, k, down_ratio, dk, int(padding),
+                          int(alpha is not None), int(logscale), dx.data_ptr(), dalpha.data_ptr() if param_grads >= 1 else None,
+                          dbeta.data_ptr() if param_grads == 2 else None, _lib.ptr(ws), _lib.stream(x.device)), 'ptmi_anti_alias_backward')
+    return dx, dalpha, dbeta
