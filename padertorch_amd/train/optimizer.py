@@ -172,9 +172,13 @@ class Adam(Optimizer):
         fg, opt = self.flat_grads, self.optimizer
         keys = tuple(p.data_ptr() for p in fg.params)
         b = self._bound
+        # (a zero-element view has a null data_ptr() wherever it sits: such a parameter's moments are told by their storage alone)
         if b is not None and b[4] == keys and b[0].device == fg.flat.device and all(
-                (st := opt.state.get(p)) is not None and st['exp_avg'].data_ptr() == b[0].data_ptr() + 4 * off
-                and st['exp_avg_sq'].data_ptr() == b[1].data_ptr() + 4 * off and st['step'].data_ptr() == b[2].data_ptr() + 4 * i
+                (st := opt.state.get(p)) is not None and st['step'].data_ptr() == b[2].data_ptr() + 4 * i and (
+                    st['exp_avg'].data_ptr() == b[0].data_ptr() + 4 * off and st['exp_avg_sq'].data_ptr() == b[1].data_ptr() + 4 * off
+                    if p.numel() else
+                    st['exp_avg'].untyped_storage().data_ptr() == b[0].untyped_storage().data_ptr()
+                    and st['exp_avg_sq'].untyped_storage().data_ptr() == b[1].untyped_storage().data_ptr())
                 for i, (p, off) in enumerate(zip(fg.params, b[5]))):
             return b
         dev = fg.flat.device
