@@ -6,183 +6,36 @@ MI355X device, the ops raise instead of silently computing something else.
 import ctypes
 import os
 import threading
-from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p, POINTER
+from ctypes import c_int, c_int32, c_int64, c_void_p
 from pathlib import Path
 
 import torch
+
+from . import _capi
 
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / 'libptmi.so'
 if os.environ.get('PTMI_LIB'):            # A/B runs against another build of the same ABI (experiments only)
     LIB_PATH = Path(os.environ['PTMI_LIB'])
 
+HEADER_PATH = _PKG.parent / 'include' / 'ptmi.h'
+if not HEADER_PATH.exists():
+    raise ImportError(f'{HEADER_PATH} is missing: the ctypes signatures of libptmi.so are read from the header that declares them.')
+_HEADER = HEADER_PATH.read_text()
+
 
 class StftGeom(ctypes.Structure):
     """``ptmi_stft_geom`` (include/ptmi.h)."""
-    _fields_ = [('size', c_int32), ('shift', c_int32), ('window_length', c_int32),
-                ('pad_left', c_int32), ('pad_right', c_int32), ('pad', c_int32)]
+    _fields_ = _capi.struct_fields(_HEADER, 'ptmi_stft_geom')
 
 
 class NormGeom(ctypes.Structure):
     """``ptmi_norm_geom`` (include/ptmi.h)."""
-    _fields_ = [('rank', c_int32), ('size', c_int64 * 5), ('stat_group_stride', c_int64 * 5),
-                ('indep_stride', c_int64 * 5), ('batch_dim', c_int32), ('seq_dim', c_int32)]
+    _fields_ = _capi.struct_fields(_HEADER, 'ptmi_norm_geom')
 
 
-_P = c_void_p   # device pointers travel as integers
-_G = POINTER(StftGeom)
-_I64P = POINTER(c_int64)
-
-#: name -> (restype, argtypes); must list every symbol include/ptmi.h declares
-SIGNATURES = {
-    'ptmi_version': (c_char_p, []),
-    'ptmi_error_string': (c_char_p, [c_int]),
-    'ptmi_stft_num_frames': (c_int64, [_G, c_int64]),
-    'ptmi_istft_num_samples': (c_int64, [_G, c_int64]),
-    'ptmi_stft_forward': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _G, c_int64, c_int32,
-                                  c_float, _P, _P]),
-    'ptmi_istft_forward': (c_int, [_P, c_int64, c_int64, _P, _P, _P, _G, c_int32, c_float, c_int64,
-                                   c_int64, c_int64, _P, _P]),
-    'ptmi_pit_features': (c_int, [_P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P, _G, c_int64,
-                                  _P, _P, _P, _P]),
-    'ptmi_pit_features_packed': (c_int, [_P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P, _G, c_int64,
-                                         _P, _P, _P, _P, _P, _P, _P]),
-    'ptmi_pit_workspace_elems': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    'ptmi_pit_pairwise_sse': (c_int, [_P, _P, _P, _P, c_int64, c_int64, _I64P, c_int32, c_int32, _P,
-                                      _P, _P, _P]),
-    'ptmi_pit_assign': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P]),
-    'ptmi_pit_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _I64P, c_int32, c_int32,
-                                  c_int32, _P, _P, _P]),
-    'ptmi_dc_workspace_elems': (c_int64, [c_int64, c_int64, c_int32]),
-    'ptmi_dc_loss_forward': (c_int, [_P, _P, c_int64, c_int64, _I64P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
-    'ptmi_dc_loss_backward': (c_int, [_P, _P, _P, _P, c_int64, c_int64, _I64P, c_int32, c_int32, c_int32, _P, _P, _P]),
-    'ptmi_stft_logmel': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _G, c_int64, _P, _P, _P, _P,
-                                 c_int32, c_int32, c_int32, c_int32, c_float, _P, _P]),
-    'ptmi_mel_apply': (c_int, [_P, c_int64, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P]),
-    'ptmi_norm_workspace_elems': (c_int64, [POINTER(NormGeom), c_int32]),
-    'ptmi_norm_reduce': (c_int, [c_int32, _P, _P, _P, _P, _P, _P, POINTER(NormGeom), c_int32, _P, _P, _P]),
-    'ptmi_norm_elementwise': (c_int, [c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(NormGeom), c_int32,
-                                      c_int32, _P, _P]),
-    'ptmi_td_stats_elems': (c_int64, [c_int32]),
-    'ptmi_td_workspace_elems': (c_int64, [c_int64, c_int32, c_int64]),
-    'ptmi_td_pair_stats': (c_int, [_P, _P, _P, c_int64, c_int32, c_int64, _I64P, _P, _P, _P]),
-    'ptmi_td_lincomb': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _I64P, _P, _P]),
-    'ptmi_tas_analysis': (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, c_int32, _P]),
-    'ptmi_tas_synthesis': (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64, _P]),
-    'ptmi_tas_masked_decode_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32,
-                                                c_int64, _P]),
-    'ptmi_tas_wgrad_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int64]),
-    'ptmi_tas_wgrad': (c_int, [_P, _P, _P, _P, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, _P, _P, _P]),
-    'ptmi_tcn_depthwise_workspace_elems': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    'ptmi_tcn_depthwise_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_float, _P]),
-    'ptmi_tcn_depthwise_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P]),
-    'ptmi_tcn_norm_workspace_elems': (c_int64, [c_int64, c_int64, c_int32]),
-    'ptmi_tcn_norm_stats': (c_int, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_float, _P]),
-    'ptmi_tcn_norm_apply': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P]),
-    'ptmi_tcn_norm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P]),
-    'ptmi_tasnet_entry_norm_workspace_elems': (c_int64, [c_int64, c_int32, c_int64]),
-    'ptmi_tasnet_entry_norm_forward': (c_int, [_P, _P, _P, _P, c_int32, _P, _P, c_int64, c_int32, c_int64, c_float, _P]),
-    'ptmi_tasnet_entry_norm_backward': (c_int, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
-    'ptmi_tasnet_prelu_workspace_elems': (c_int64, [c_int64]),
-    'ptmi_tasnet_prelu_forward': (c_int, [_P, _P, _P, c_int64, _P]),
-    'ptmi_tasnet_prelu_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, _P]),
-    'ptmi_tasnet_mask_head_forward': (c_int, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_tasnet_mask_head_backward': (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_tasnet_center_workspace_elems': (c_int64, [c_int64, c_int64, c_int64, c_int64]),
-    'ptmi_tasnet_center': (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int32, _P]),
-    'ptmi_td_rect_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int64]),
-    'ptmi_td_rect_stats': (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int64, _I64P, _P, _P, _P, _P]),
-    'ptmi_orpit_select': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
-    'ptmi_td_rect_lincomb': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int64, _I64P, _P, _P]),
-    'ptmi_orpit_flag_workspace_elems': (c_int64, [c_int64, c_int32, c_int64]),
-    'ptmi_orpit_flag_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
-                                        c_int32, _P]),
-    'ptmi_orpit_flag_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32,
-                                         c_int32, c_int32, c_int32, _P]),
-    'ptmi_mask_loss_workspace_elems': (c_int64, [c_int64, c_int32, c_int32, c_int32]),
-    'ptmi_mask_loss_forward': (c_int, [_P, _P, _P, c_int32, _P, _I64P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
-                                       _P]),
-    'ptmi_mask_loss_backward': (c_int, [_P, _P, _P, c_int32, _P, _I64P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P,
-                                        _P]),
-    'ptmi_gl_partials_elems': (c_int64, []),
-    'ptmi_gl_project': (c_int, [_P, _P, c_int64, _P, _P]),
-    'ptmi_gl_project_backward': (c_int, [_P, _P, c_int64, _P, _P]),
-    'ptmi_gl_update': (c_int, [_P, _P, _P, c_int64, c_float, _P, _P, _P, _P]),
-    'ptmi_gl_stft_update': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _G, c_int64, c_float, _P, _P, _P, _P, _P, _P]),
-    'ptmi_gl_finish': (c_int, [_P, c_int64, c_double, c_int32, _P, _P, _P]),
-    'ptmi_anti_alias_tile': (c_int32, [c_int32]),
-    'ptmi_anti_alias_out_len': (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_anti_alias_workspace_elems': (c_int64, [c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_anti_alias_forward': (c_int, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                        c_int32, c_int32, _P, _P]),
-    'ptmi_anti_alias_backward': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                         c_int32, c_int32, _P, _P, _P, _P, _P]),
-    'ptmi_bf_psd_workspace_elems': (c_int64, [c_int64, c_int32, c_int64, c_int64, c_int32]),
-    'ptmi_bf_psd': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P]),
-    'ptmi_bf_souden': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
-    'ptmi_bf_apply': (c_int, [_P, _P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P]),
-    'ptmi_bf_eig': (c_int, [_P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
-    'ptmi_bf_ban': (c_int, [_P, _P, c_int64, c_int64, c_int32, _P, _P]),
-    'ptmi_bf_phase': (c_int, [_P, c_int64, c_int64, c_int32, _P, _P]),
-    'ptmi_dprnn_num_chunks': (c_int64, [c_int64, c_int32, c_int32]),
-    'ptmi_dprnn_tables': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
-    'ptmi_chunk_lstm_max_hidden': (c_int32, []),
-    'ptmi_chunk_lstm_max_resident_hidden': (c_int32, []),
-    'ptmi_chunk_lstm_tile': (c_int32, []),
-    'ptmi_chunk_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_chunk_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_dprnn_colsum_workspace_elems': (c_int64, [c_int64, c_int32]),
-    'ptmi_dprnn_colsum': (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int32, _P]),
-    'ptmi_dprnn_norm_residual_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, _P]),
-    'ptmi_dprnn_norm_residual_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P]),
-    'ptmi_dprnn_segment': (c_int, [_P, _I64P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_dprnn_overlap_add': (c_int, [_P, _I64P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_lstm_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_lstm_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_unit_norm_forward': (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),
-    'ptmi_unit_norm_backward': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_float, c_void_p]),
-    'ptmi_lstm_flags_elems': (c_int64, [c_int32, c_int32, c_int32]),
-    'ptmi_lstm_scratch_elems': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_lstm_weight_prep': (c_int, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P, _P, _P]),
-    'ptmi_lstm_set_error_sink': (c_int, [_P]),
-    'ptmi_lstm_split_enabled': (c_int, []),
-    'ptmi_lstm_handoff_cols': (c_int32, [c_int32, c_int32]),
-    'ptmi_lstm_forward_persistent': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32, c_int32,
-                                             c_int32, c_int32, _P, _P]),
-    'ptmi_lstm_forward_fills': (c_int, [c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_lstm_backward_planes_ok': (c_int32, [c_int32, c_int32, c_int32, c_int64, c_int32]),
-    'ptmi_lstm_backward_persistent': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int64, c_int32,
-                                              c_int32, c_int32, c_int32, c_int32, _P]),
-    'ptmi_absmax': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
-    'ptmi_absmax_accumulate': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
-    'ptmi_planes_elems': (c_int64, [c_int64, c_int64]),
-    'ptmi_pack_planes_t': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P]),
-    'ptmi_gemm_planes_workspace_elems': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_pack_planes_n': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P]),
-    'ptmi_gemm_planes': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
-    'ptmi_gemm_planes_relu': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, _P]),
-    'ptmi_relu_backward_absmax': (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int32, _P]),
-    'ptmi_pack_planes_t_bf16': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
-    'ptmi_pack_planes_n_bf16': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
-    'ptmi_pack_planes_into': (c_int, [_P, c_int64, c_int64, c_int64, c_int32, c_int32, _P, _P, c_int64, c_int64, c_int64, _P]),
-    'ptmi_gemm_planes_bf16': (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
-    'ptmi_gemm_planes_bf16_two': (c_int, [_P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
-    'ptmi_gemm_planes_plan': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
-    'ptmi_gemm_planes_bf16_group': (c_int, [_P, c_int32, c_int32, _P, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
-    'ptmi_gemm_planes_group_workspace_elems': (c_int64, [c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32]),
-    'ptmi_gemm_planes_group_plan': (c_int32, [c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32]),
-    'ptmi_pack_planes_t_bf16_list': (c_int, [_P, _P, _P, _P, c_int32, c_int64, _P]),
-    'ptmi_comm_rccl_version': (c_int32, []),
-    'ptmi_comm_unique_id': (c_int, [_P]),
-    'ptmi_comm_create': (c_int, [_P, c_int32, c_int32, _P]),
-    'ptmi_allreduce_sum': (c_int, [_P, _P, c_int64, _P]),
-    'ptmi_comm_destroy': (c_int, [_P]),
-    'ptmi_lstm_bias_grad_add': (c_int, [_P, c_int32, c_int32, _P, _P, _P]),
-    'ptmi_grad_norm_workspace_elems': (c_int64, []),
-    'ptmi_grad_norm': (c_int32, [_P, c_int64, _P, _P, _P]),
-    'ptmi_adam_flat': (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P, c_float, _P, _P, _P, _P, c_double, c_double, c_double,
-                                 c_double, c_double, _P, c_int32, _P]),
-}
+#: name -> (restype, argtypes) of every function include/ptmi.h declares, by the type mapping at the top of ``_capi``
+SIGNATURES = _capi.signatures(_HEADER, {'ptmi_stft_geom': StftGeom, 'ptmi_norm_geom': NormGeom})
 
 _lib = None
 
@@ -218,7 +71,7 @@ def test_hooks():
             raise ImportError(f'{path} is missing: python -m padertorch_amd.build')
         lib = ctypes.CDLL(str(path))
         lib.ptmi_test_occupy.restype = c_int
-        lib.ptmi_test_occupy.argtypes = [c_int32, c_int32, c_int32, c_int64, _P]
+        lib.ptmi_test_occupy.argtypes = [c_int32, c_int32, c_int32, c_int64, c_void_p]
         _hooks = lib
     return _hooks
 
@@ -281,6 +134,17 @@ def timed(name, fn, *args):
     return rc
 
 
+def call(symbol, *args, timer=None, accept=()):
+    """Launch the C-ABI entry point ``symbol`` (``'ptmi_...'``) with ``args``, under :func:`timed` as ``timer`` when one is given, and
+    :func:`check` its return code with the symbol as the label.  A code listed in ``accept`` is returned instead of raised: ``(-2,)``
+    where PTMI_E_UNSUPPORTED - nothing was enqueued - sends the caller another route."""
+    fn = getattr(load(), symbol)
+    rc = timed(timer, fn, *args) if timer else fn(*args)
+    if rc and rc not in accept:
+        check(rc, symbol)
+    return rc
+
+
 class _Staging:
     """Pinned staging memory for small host -> device copies: two halves used in turn.  One event per half (recorded when the half is
     left) says when the copies out of it have run; a half is written again only behind its event - long fired by then.  (A fresh
@@ -340,16 +204,9 @@ def host_to_device(values, dtype, device):
     return st.put(t.contiguous(), torch.device('cuda', idx))
 
 
-def strides4(*vals):
-    return (c_int64 * 4)(*vals)
-
-
-def strides6(*vals):
-    return (c_int64 * 6)(*vals)
-
-
-def strides8(*vals):
-    return (c_int64 * 8)(*vals)
+def int64s(*vals):
+    """A HOST ``int64_t`` array argument (the stride arrays of include/ptmi.h)."""
+    return (c_int64 * len(vals))(*vals)
 
 
 #: PTMI_STRICT=1 (or ``padertorch_amd._lib.STRICT = True``): a request that would leave the hand-written HIP path - an LSTM the

@@ -137,17 +137,15 @@ class MelTransform(nn.Module):
         if x.requires_grad:
             raise NotImplementedError('MelTransform is a feature front-end (the reference runs it under '
                                       'no_grad, features.py:156); no backward is provided')
-        lib = _lib.load()
         lead, F = x.shape[:-1], x.shape[-1]
         assert F == self._bands.F, (F, self._bands.F)
         spec = x.to(torch.float32).reshape(-1, F).contiguous()
         out = torch.empty((spec.shape[0], self._bands.M), dtype=torch.float32, device=x.device)
         tb = self._bands.get(x.device)
         if spec.shape[0] > 0:           # (an empty tensor has no device pointer)
-            _lib.check(_lib.timed(
-                'mel_apply', lib.ptmi_mel_apply, spec.data_ptr(), spec.shape[0], F, tb['lo'].data_ptr(),
-                tb['cnt'].data_ptr(), tb['off'].data_ptr(), tb['w'].data_ptr(), self._bands.M, self._bands.nnz,
-                int(bool(self.log)), float(self.eps), out.data_ptr(), _lib.stream(x.device)), 'ptmi_mel_apply')
+            _lib.call('ptmi_mel_apply', spec.data_ptr(), spec.shape[0], F, tb['lo'].data_ptr(), tb['cnt'].data_ptr(), tb['off'].data_ptr(),
+                      tb['w'].data_ptr(), self._bands.M, self._bands.nnz, int(bool(self.log)), float(self.eps), out.data_ptr(),
+                      _lib.stream(x.device), timer='mel_apply')
         out = out.reshape(*lead, self._bands.M)
         if return_maxima:
             fb = self.fbanks
@@ -220,12 +218,11 @@ def stft_logmel(x, stft: STFT, mel: MelTransform, num_samples=None, power: int =
         assert ns.numel() == rows.shape[0], (ns.shape, rows.shape)
     out = torch.empty((rows.shape[0], frames, mel._bands.M), dtype=torch.float32, device=dev)
     tb, mb = stft._tables.get(dev), mel._bands.get(dev)
-    rc = _lib.timed(
-        'stft_logmel', lib.ptmi_stft_logmel, rows.data_ptr(), rows.shape[0], N, N, _lib.ptr(ns),
+    rc = _lib.call(
+        'ptmi_stft_logmel', rows.data_ptr(), rows.shape[0], N, N, _lib.ptr(ns),
         tb['window'].data_ptr(), tb['twiddle'].data_ptr(), stft._geom, frames, mb['lo'].data_ptr(),
         mb['cnt'].data_ptr(), mb['off'].data_ptr(), mb['w'].data_ptr(), mel._bands.M, mel._bands.nnz, power,
-        int(bool(mel.log)), float(mel.eps), out.data_ptr(), _lib.stream(dev))
+        int(bool(mel.log)), float(mel.eps), out.data_ptr(), _lib.stream(dev), timer='stft_logmel', accept=(-2,))
     if rc == -2:
         raise _logmel_unsupported(stft.size, mel._bands.M, mel._bands.nnz)
-    _lib.check(rc, 'ptmi_stft_logmel')
     return out.reshape(*lead, frames, mel._bands.M)

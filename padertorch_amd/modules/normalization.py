@@ -57,20 +57,16 @@ def _reduce(mode, x, gy, lengths, mean, rstd, gamma, geom, shift, n_groups):
     lib = _lib.load()
     ws = torch.empty(int(lib.ptmi_norm_workspace_elems(geom, int(mode == 2))), dtype=torch.float64, device=x.device)
     out = torch.empty((n_groups, 3), dtype=torch.float64, device=x.device)
-    _lib.check(_lib.timed(
-        'norm_reduce', lib.ptmi_norm_reduce, mode, x.data_ptr(), _lib.ptr(gy), _lib.ptr(lengths), _lib.ptr(mean),
-        _lib.ptr(rstd), _lib.ptr(gamma), geom, int(shift), ws.data_ptr(), out.data_ptr(), _lib.stream(x.device)),
-        'ptmi_norm_reduce')
+    _lib.call('ptmi_norm_reduce', mode, x.data_ptr(), _lib.ptr(gy), _lib.ptr(lengths), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma),
+              geom, int(shift), ws.data_ptr(), out.data_ptr(), _lib.stream(x.device), timer='norm_reduce')
     return out
 
 
 def _elementwise(backward, x, gy, lengths, mean, rstd, gamma, beta, c0, c1, geom, shift, scale):
-    lib = _lib.load()
     out = torch.empty_like(x)
-    _lib.check(_lib.timed(
-        'norm_elementwise', lib.ptmi_norm_elementwise, int(backward), x.data_ptr(), _lib.ptr(gy), _lib.ptr(lengths),
-        _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(c0), _lib.ptr(c1), geom,
-        int(shift), int(scale), out.data_ptr(), _lib.stream(x.device)), 'ptmi_norm_elementwise')
+    _lib.call('ptmi_norm_elementwise', int(backward), x.data_ptr(), _lib.ptr(gy), _lib.ptr(lengths), _lib.ptr(mean), _lib.ptr(rstd),
+              _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(c0), _lib.ptr(c1), geom, int(shift), int(scale), out.data_ptr(),
+              _lib.stream(x.device), timer='norm_elementwise')
     return out
 
 

@@ -68,30 +68,23 @@ def _geom(g: List[int]):
 @_register('stft_forward(Tensor x, Tensor? row_samples, Tensor window, Tensor twiddle, int[] geom, int frames, int layout, '
            'float edge_scale, str timer) -> Tensor')
 def stft_forward(x, row_samples, window, twiddle, geom, frames, layout, edge_scale, timer):
-    lib = _lib.load()
     rows, T = x.shape
     F = geom[0] // 2 + 1
     shape = (rows, frames, F, 2) if layout == 0 else (rows, frames, 2 * F)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    g = _geom(geom)
-    args = (x.data_ptr(), rows, x.stride(0), T, _lib.ptr(row_samples), window.data_ptr(), twiddle.data_ptr(), g, frames,
-            layout, edge_scale, out.data_ptr(), _lib.stream(x.device))
-    rc = _lib.timed(timer, lib.ptmi_stft_forward, *args) if timer else lib.ptmi_stft_forward(*args)
-    _lib.check(rc, 'ptmi_stft_forward')
+    _lib.call('ptmi_stft_forward', x.data_ptr(), rows, x.stride(0), T, _lib.ptr(row_samples), window.data_ptr(), twiddle.data_ptr(),
+              _geom(geom), frames, layout, edge_scale, out.data_ptr(), _lib.stream(x.device), timer=timer)      # '': not timed
     return out
 
 
 @_register('istft_forward(Tensor spec, Tensor window, Tensor twiddle, int[] geom, int layout, float edge_scale, int cut_left, '
            'int out_samples, str timer) -> Tensor')
 def istft_forward(spec, window, twiddle, geom, layout, edge_scale, cut_left, out_samples, timer):
-    lib = _lib.load()
     rows, frames = spec.shape[0], spec.shape[1]
     out = torch.empty((rows, max(out_samples, 0)), dtype=torch.float32, device=spec.device)
     if out_samples > 0:
-        args = (spec.data_ptr(), rows, frames, None, window.data_ptr(), twiddle.data_ptr(), _geom(geom), layout, edge_scale,
-                cut_left, out_samples, out_samples, out.data_ptr(), _lib.stream(spec.device))
-        rc = _lib.timed(timer, lib.ptmi_istft_forward, *args) if timer else lib.ptmi_istft_forward(*args)
-        _lib.check(rc, 'ptmi_istft_forward')
+        _lib.call('ptmi_istft_forward', spec.data_ptr(), rows, frames, None, window.data_ptr(), twiddle.data_ptr(), _geom(geom), layout,
+                  edge_scale, cut_left, out_samples, out_samples, out.data_ptr(), _lib.stream(spec.device), timer=timer)
     return out
 
 
@@ -110,7 +103,6 @@ def pit_features_packed(y, s, num_samples, window, twiddle, geom, frames, log1p_
 
 
 def _pit_features(y, s, num_samples, window, twiddle, geom, frames, log1p_packed, log1p_planes, packed_offsets):
-    lib = _lib.load()
     B, N = y.shape
     K = s.shape[1] if s is not None else 0
     F = geom[0] // 2 + 1
@@ -120,12 +112,11 @@ def _pit_features(y, s, num_samples, window, twiddle, geom, frames, log1p_packed
     if K:
         X_abs = torch.empty((B, frames, K, F), dtype=torch.float32, device=dev)
         cos_pd = torch.empty((B, frames, K, F), dtype=torch.float32, device=dev)
-    rc = _lib.timed('pit_features', lib.ptmi_pit_features_packed, y.data_ptr(), _lib.ptr(s), B, K, N, N, _lib.ptr(num_samples),
-                    window.data_ptr(), twiddle.data_ptr(), _geom(geom), frames, Y_abs.data_ptr(), _lib.ptr(X_abs),
-                    _lib.ptr(cos_pd), _lib.ptr(log1p_packed), _lib.ptr(log1p_planes), _lib.ptr(packed_offsets), _lib.stream(dev))
+    rc = _lib.call('ptmi_pit_features_packed', y.data_ptr(), _lib.ptr(s), B, K, N, N, _lib.ptr(num_samples), window.data_ptr(),
+                   twiddle.data_ptr(), _geom(geom), frames, Y_abs.data_ptr(), _lib.ptr(X_abs), _lib.ptr(cos_pd), _lib.ptr(log1p_packed),
+                   _lib.ptr(log1p_planes), _lib.ptr(packed_offsets), _lib.stream(dev), timer='pit_features', accept=(-2,))
     if rc == -2:
         raise NotImplementedError(f'pit_features: STFT size {geom[0]} / window {geom[2]} beyond what the direct-DFT kernel stages in LDS')
-    _lib.check(rc, 'ptmi_pit_features')
     return Y_abs, X_abs, cos_pd
 
 
@@ -139,27 +130,24 @@ def pit_loss_forward(est, obs, tgt, scale, row_frames, B, T, K, F, strides):
     ws = torch.empty(int(lib.ptmi_pit_workspace_elems(B, T, K, F)), dtype=torch.float64, device=dev)
     sse = torch.empty((B, nvar, K, K), dtype=torch.float64, device=dev)
     st = _lib.stream(dev)
-    _lib.check(_lib.timed('pit_pairwise_sse', lib.ptmi_pit_pairwise_sse, est.data_ptr(), _lib.ptr(obs), tgt.data_ptr(),
-                          _lib.ptr(scale), B, T, _lib.strides6(*strides), K, F, _lib.ptr(row_frames), ws.data_ptr(),
-                          sse.data_ptr(), st), 'ptmi_pit_pairwise_sse')
+    _lib.call('ptmi_pit_pairwise_sse', est.data_ptr(), _lib.ptr(obs), tgt.data_ptr(), _lib.ptr(scale), B, T, _lib.int64s(*strides), K, F,
+              _lib.ptr(row_frames), ws.data_ptr(), sse.data_ptr(), st, timer='pit_pairwise_sse')
     loss = torch.empty(nvar, dtype=torch.float32, device=dev)
     perm = torch.empty((B, nvar, K), dtype=torch.int32, device=dev)
     ex_loss = torch.empty((B, nvar), dtype=torch.float32, device=dev)
-    _lib.check(lib.ptmi_pit_assign(sse.data_ptr(), B, nvar, K, F, T, _lib.ptr(row_frames), loss.data_ptr(), perm.data_ptr(),
-                                   ex_loss.data_ptr(), st), 'ptmi_pit_assign')
+    _lib.call('ptmi_pit_assign', sse.data_ptr(), B, nvar, K, F, T, _lib.ptr(row_frames), loss.data_ptr(), perm.data_ptr(),
+              ex_loss.data_ptr(), st)
     return loss, perm, ex_loss, sse
 
 
 @_register('pit_loss_backward(Tensor est, Tensor? obs, Tensor tgt, Tensor? scale, Tensor perm, Tensor g_loss, Tensor? row_frames, '
            'int B, int T, int K, int F, int[] strides) -> Tensor')
 def pit_loss_backward(est, obs, tgt, scale, perm, g_loss, row_frames, B, T, K, F, strides):
-    lib = _lib.load()
     nvar = 2 if scale is not None else 1
     # the kernel writes every (b, t < T) row, zero for the padded frames t >= T_b
     grad = torch.empty_strided(est.shape, est.stride(), dtype=est.dtype, device=est.device)
-    _lib.check(_lib.timed('pit_backward', lib.ptmi_pit_backward, est.data_ptr(), _lib.ptr(obs), tgt.data_ptr(), _lib.ptr(scale),
-                          perm.data_ptr(), g_loss.data_ptr(), B, T, _lib.strides6(*strides), K, F, nvar, _lib.ptr(row_frames),
-                          grad.data_ptr(), _lib.stream(est.device)), 'ptmi_pit_backward')
+    _lib.call('ptmi_pit_backward', est.data_ptr(), _lib.ptr(obs), tgt.data_ptr(), _lib.ptr(scale), perm.data_ptr(), g_loss.data_ptr(), B, T,
+              _lib.int64s(*strides), K, F, nvar, _lib.ptr(row_frames), grad.data_ptr(), _lib.stream(est.device), timer='pit_backward')
     return grad
 
 
@@ -172,21 +160,18 @@ def dc_loss_forward(x, t, row_frames, B, T, E, K, F, strides):
     gram = torch.empty((B, 32, 32), dtype=torch.float64, device=dev)
     ex_loss = torch.empty(B, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
-    _lib.check(_lib.timed('dc_loss_forward', lib.ptmi_dc_loss_forward, x.data_ptr(), t.data_ptr(), B, T, _lib.strides8(*strides),
-                          E, K, F, _lib.ptr(row_frames), ws.data_ptr(), gram.data_ptr(), ex_loss.data_ptr(), loss.data_ptr(),
-                          _lib.stream(dev)), 'ptmi_dc_loss_forward')
+    _lib.call('ptmi_dc_loss_forward', x.data_ptr(), t.data_ptr(), B, T, _lib.int64s(*strides), E, K, F, _lib.ptr(row_frames),
+              ws.data_ptr(), gram.data_ptr(), ex_loss.data_ptr(), loss.data_ptr(), _lib.stream(dev), timer='dc_loss_forward')
     return loss, ex_loss, gram
 
 
 @_register('dc_loss_backward(Tensor x, Tensor t, Tensor gram, Tensor g_loss, Tensor? row_frames, int B, int T, int E, int K, int F, '
            'int[] strides, bool zero_fill) -> Tensor')
 def dc_loss_backward(x, t, gram, g_loss, row_frames, B, T, E, K, F, strides, zero_fill):
-    lib = _lib.load()
     dx = torch.zeros_like(x, memory_format=torch.preserve_format) if zero_fill \
         else torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
-    _lib.check(_lib.timed('dc_loss_backward', lib.ptmi_dc_loss_backward, x.data_ptr(), t.data_ptr(), gram.data_ptr(),
-                          g_loss.data_ptr(), B, T, _lib.strides8(*strides), E, K, F, _lib.ptr(row_frames), dx.data_ptr(),
-                          _lib.stream(x.device)), 'ptmi_dc_loss_backward')
+    _lib.call('ptmi_dc_loss_backward', x.data_ptr(), t.data_ptr(), gram.data_ptr(), g_loss.data_ptr(), B, T, _lib.int64s(*strides), E, K,
+              F, _lib.ptr(row_frames), dx.data_ptr(), _lib.stream(x.device), timer='dc_loss_backward')
     return dx
 
 
@@ -206,8 +191,8 @@ def tas_analysis(x, weight, bias, stride, frames, relu):
     L = weight.numel() // N
     assert x.is_contiguous() and weight.is_contiguous()
     out = torch.empty((B, N, frames), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.timed('tas_analysis', _lib.load().ptmi_tas_analysis, x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), out.data_ptr(),
-                          B, T, N, L, stride, frames, int(relu), _lib.stream(x.device)), 'ptmi_tas_analysis')
+    _lib.call('ptmi_tas_analysis', x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), out.data_ptr(), B, T, N, L, stride, frames, int(relu),
+              _lib.stream(x.device), timer='tas_analysis')
     return out
 
 
@@ -222,8 +207,8 @@ def tas_synthesis(p, mask, gate, weight, bias, stride, samples):
         assert mask.shape == (K, B, N, E) and mask.is_contiguous(), mask.shape
     assert gate is None or (gate.shape == p.shape and gate.is_contiguous())
     y = torch.empty((B, samples) if mask is None else (K, B, samples), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.timed('tas_synthesis', _lib.load().ptmi_tas_synthesis, p.data_ptr(), _lib.ptr(mask), _lib.ptr(gate), weight.data_ptr(),
-                          _lib.ptr(bias), y.data_ptr(), K, B, N, L, stride, E, samples, _lib.stream(p.device)), 'ptmi_tas_synthesis')
+    _lib.call('ptmi_tas_synthesis', p.data_ptr(), _lib.ptr(mask), _lib.ptr(gate), weight.data_ptr(), _lib.ptr(bias), y.data_ptr(), K, B, N,
+              L, stride, E, samples, _lib.stream(p.device), timer='tas_synthesis')
     return y
 
 
@@ -234,9 +219,8 @@ def tas_masked_decode_backward(gy, mask, encoded, weight, stride):
     K, _, T = gy.shape
     assert mask.shape == (K, B, N, E) and gy.shape[1] == B and mask.is_contiguous() and gy.is_contiguous(), (mask.shape, gy.shape)
     dmask, denc = torch.empty_like(mask), torch.empty_like(encoded)
-    _lib.check(_lib.timed('tas_masked_decode_backward', _lib.load().ptmi_tas_masked_decode_backward, gy.data_ptr(), mask.data_ptr(),
-                          encoded.data_ptr(), weight.data_ptr(), dmask.data_ptr(), denc.data_ptr(), K, B, T, N, L, stride, E,
-                          _lib.stream(gy.device)), 'ptmi_tas_masked_decode_backward')
+    _lib.call('ptmi_tas_masked_decode_backward', gy.data_ptr(), mask.data_ptr(), encoded.data_ptr(), weight.data_ptr(), dmask.data_ptr(),
+              denc.data_ptr(), K, B, T, N, L, stride, E, _lib.stream(gy.device), timer='tas_masked_decode_backward')
     return dmask, denc
 
 
@@ -253,8 +237,8 @@ def tas_wgrad(g, mask, gate, x, stride, window_length):
     assert gate is None or (gate.shape == g.shape and gate.is_contiguous())
     ws = torch.empty(int(lib.ptmi_tas_wgrad_workspace_elems(B, N, L, stride, E)), dtype=torch.float32, device=g.device)
     out = torch.empty(N * L + N + 1, dtype=torch.float32, device=g.device)
-    _lib.check(_lib.timed('tas_wgrad', lib.ptmi_tas_wgrad, g.data_ptr(), _lib.ptr(mask), _lib.ptr(gate), x.data_ptr(), K, B, x.shape[-1],
-                          N, L, stride, E, ws.data_ptr(), out.data_ptr(), _lib.stream(g.device)), 'ptmi_tas_wgrad')
+    _lib.call('ptmi_tas_wgrad', g.data_ptr(), _lib.ptr(mask), _lib.ptr(gate), x.data_ptr(), K, B, x.shape[-1], N, L, stride, E,
+              ws.data_ptr(), out.data_ptr(), _lib.stream(g.device), timer='tas_wgrad')
     return out
 
 
@@ -282,9 +266,9 @@ def tcn_depthwise_forward(u, slope_in, weight, bias, slope_out, dilation, eps):
     v = torch.empty_like(u)
     stats = torch.empty((B, 2), dtype=torch.float32, device=u.device)
     ws = _doubles(lib.ptmi_tcn_depthwise_workspace_elems(B, T, H, K), u.device)
-    _lib.check(_lib.timed('tcn_depthwise_forward', lib.ptmi_tcn_depthwise_forward, u.data_ptr(), slope_in.data_ptr(), weight.data_ptr(),
-                          _lib.ptr(bias), slope_out.data_ptr(), v.data_ptr(), stats.data_ptr(), ws.data_ptr(), B, T, H, K, dilation, eps,
-                          _lib.stream(u.device)), 'ptmi_tcn_depthwise_forward')
+    _lib.call('ptmi_tcn_depthwise_forward', u.data_ptr(), slope_in.data_ptr(), weight.data_ptr(), _lib.ptr(bias), slope_out.data_ptr(),
+              v.data_ptr(), stats.data_ptr(), ws.data_ptr(), B, T, H, K, dilation, eps, _lib.stream(u.device),
+              timer='tcn_depthwise_forward')
     return v, stats
 
 
@@ -299,9 +283,9 @@ def tcn_depthwise_backward(gv, u, slope_in, weight, bias, slope_out, dilation):
     gz, gu = torch.empty_like(u), torch.empty_like(u)
     dparams = torch.empty(H * K + H + 2, dtype=torch.float32, device=u.device)
     ws = _doubles(lib.ptmi_tcn_depthwise_workspace_elems(B, T, H, K), u.device)
-    _lib.check(_lib.timed('tcn_depthwise_backward', lib.ptmi_tcn_depthwise_backward, gv.data_ptr(), u.data_ptr(), slope_in.data_ptr(),
-                          weight.data_ptr(), _lib.ptr(bias), slope_out.data_ptr(), gz.data_ptr(), gu.data_ptr(), dparams.data_ptr(),
-                          ws.data_ptr(), B, T, H, K, dilation, _lib.stream(u.device)), 'ptmi_tcn_depthwise_backward')
+    _lib.call('ptmi_tcn_depthwise_backward', gv.data_ptr(), u.data_ptr(), slope_in.data_ptr(), weight.data_ptr(), _lib.ptr(bias),
+              slope_out.data_ptr(), gz.data_ptr(), gu.data_ptr(), dparams.data_ptr(), ws.data_ptr(), B, T, H, K, dilation,
+              _lib.stream(u.device), timer='tcn_depthwise_backward')
     return gu, dparams
 
 
@@ -312,8 +296,8 @@ def tcn_norm_stats(x, rows, eps):
     B, T, C = _tcn_dims(x)
     stats = torch.empty((B * T if rows else B, 2), dtype=torch.float32, device=x.device)
     ws = None if rows else _doubles(lib.ptmi_tcn_norm_workspace_elems(B, T, C), x.device)
-    _lib.check(_lib.timed('tcn_norm_stats', lib.ptmi_tcn_norm_stats, x.data_ptr(), stats.data_ptr(), _lib.ptr(ws), B, T, C, int(rows), eps,
-                          _lib.stream(x.device)), 'ptmi_tcn_norm_stats')
+    _lib.call('ptmi_tcn_norm_stats', x.data_ptr(), stats.data_ptr(), _lib.ptr(ws), B, T, C, int(rows), eps, _lib.stream(x.device),
+              timer='tcn_norm_stats')
     return stats
 
 
@@ -325,8 +309,8 @@ def tcn_norm_apply(x, stats, gamma, beta, rows):
     assert stats.shape == (B * T if rows else B, 2) and stats.is_contiguous() and stats.dtype == torch.float32, stats.shape
     assert gamma.numel() == C and beta.numel() == C and gamma.is_contiguous() and beta.is_contiguous()
     y = torch.empty_like(x)
-    _lib.check(_lib.timed('tcn_norm_apply', _lib.load().ptmi_tcn_norm_apply, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
-                          beta.data_ptr(), y.data_ptr(), B, T, C, int(rows), _lib.stream(x.device)), 'ptmi_tcn_norm_apply')
+    _lib.call('ptmi_tcn_norm_apply', x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), B, T, C, int(rows),
+              _lib.stream(x.device), timer='tcn_norm_apply')
     return y
 
 
@@ -341,9 +325,8 @@ def tcn_norm_backward(gy, x, stats, gamma, rows):
     dparams = torch.empty(2 * C, dtype=torch.float32, device=x.device)
     gsum = torch.empty_like(stats)
     ws = _doubles(lib.ptmi_tcn_norm_workspace_elems(B, T, C), x.device)
-    _lib.check(_lib.timed('tcn_norm_backward', lib.ptmi_tcn_norm_backward, gy.data_ptr(), x.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
-                          dx.data_ptr(), dparams.data_ptr(), gsum.data_ptr(), ws.data_ptr(), B, T, C, int(rows), _lib.stream(x.device)),
-               'ptmi_tcn_norm_backward')
+    _lib.call('ptmi_tcn_norm_backward', gy.data_ptr(), x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), dx.data_ptr(), dparams.data_ptr(),
+              gsum.data_ptr(), ws.data_ptr(), B, T, C, int(rows), _lib.stream(x.device), timer='tcn_norm_backward')
     return dx, dparams
 
 
@@ -375,9 +358,8 @@ def tasnet_entry_norm_forward(w, gamma, beta, lengths, eps):
     lengths, is64 = _lengths(lengths, B)
     y = torch.empty((B, E, N), dtype=torch.float32, device=w.device)
     stats = torch.empty((B * E, 2), dtype=torch.float32, device=w.device)
-    _lib.check(_lib.timed('tasnet_entry_norm_forward', _lib.load().ptmi_tasnet_entry_norm_forward, w.data_ptr(), gamma.data_ptr(),
-                          beta.data_ptr(), _lib.ptr(lengths), is64, y.data_ptr(), stats.data_ptr(), B, N, E, eps, _lib.stream(w.device)),
-               'ptmi_tasnet_entry_norm_forward')
+    _lib.call('ptmi_tasnet_entry_norm_forward', w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _lib.ptr(lengths), is64, y.data_ptr(),
+              stats.data_ptr(), B, N, E, eps, _lib.stream(w.device), timer='tasnet_entry_norm_forward')
     return y, stats
 
 
@@ -392,9 +374,8 @@ def tasnet_entry_norm_backward(gy, w, stats, gamma, lengths):
     dw = torch.empty_like(w)
     dparams = torch.empty(2 * N, dtype=torch.float32, device=w.device)
     ws = _doubles(lib.ptmi_tasnet_entry_norm_workspace_elems(B, N, E), w.device)
-    _lib.check(_lib.timed('tasnet_entry_norm_backward', lib.ptmi_tasnet_entry_norm_backward, gy.data_ptr(), w.data_ptr(), stats.data_ptr(),
-                          gamma.data_ptr(), _lib.ptr(lengths), is64, dw.data_ptr(), dparams.data_ptr(), ws.data_ptr(), B, N, E,
-                          _lib.stream(w.device)), 'ptmi_tasnet_entry_norm_backward')
+    _lib.call('ptmi_tasnet_entry_norm_backward', gy.data_ptr(), w.data_ptr(), stats.data_ptr(), gamma.data_ptr(), _lib.ptr(lengths), is64,
+              dw.data_ptr(), dparams.data_ptr(), ws.data_ptr(), B, N, E, _lib.stream(w.device), timer='tasnet_entry_norm_backward')
     return dw, dparams
 
 
@@ -404,8 +385,8 @@ def tasnet_prelu_forward(x, slope):
     _f32c(x, slope)
     assert slope.numel() == 1
     y = torch.empty_like(x)
-    _lib.check(_lib.timed('tasnet_prelu_forward', _lib.load().ptmi_tasnet_prelu_forward, x.data_ptr(), slope.data_ptr(), y.data_ptr(),
-                          x.numel(), _lib.stream(x.device)), 'ptmi_tasnet_prelu_forward')
+    _lib.call('ptmi_tasnet_prelu_forward', x.data_ptr(), slope.data_ptr(), y.data_ptr(), x.numel(), _lib.stream(x.device),
+              timer='tasnet_prelu_forward')
     return y
 
 
@@ -418,8 +399,8 @@ def tasnet_prelu_backward(g, x, slope):
     gx = torch.empty_like(x)
     dslope = torch.empty(1, dtype=torch.float32, device=x.device)
     ws = _doubles(lib.ptmi_tasnet_prelu_workspace_elems(x.numel()), x.device)
-    _lib.check(_lib.timed('tasnet_prelu_backward', lib.ptmi_tasnet_prelu_backward, g.data_ptr(), x.data_ptr(), slope.data_ptr(),
-                          gx.data_ptr(), dslope.data_ptr(), ws.data_ptr(), x.numel(), _lib.stream(x.device)), 'ptmi_tasnet_prelu_backward')
+    _lib.call('ptmi_tasnet_prelu_backward', g.data_ptr(), x.data_ptr(), slope.data_ptr(), gx.data_ptr(), dslope.data_ptr(), ws.data_ptr(),
+              x.numel(), _lib.stream(x.device), timer='tasnet_prelu_backward')
     return gx, dslope
 
 
@@ -431,8 +412,8 @@ def tasnet_mask_head_forward(z, K, N, A, activation):
     assert C == A + K * N, (z.shape, K, N, A)
     m = torch.empty((K, B, N, E), dtype=torch.float32, device=z.device)
     add = torch.empty((B, A, E), dtype=torch.float32, device=z.device)
-    _lib.check(_lib.timed('tasnet_mask_head_forward', _lib.load().ptmi_tasnet_mask_head_forward, z.data_ptr(), m.data_ptr(),
-                          add.data_ptr() if A else None, B, E, N, K, A, activation, _lib.stream(z.device)), 'ptmi_tasnet_mask_head_forward')
+    _lib.call('ptmi_tasnet_mask_head_forward', z.data_ptr(), m.data_ptr(), add.data_ptr() if A else None, B, E, N, K, A, activation,
+              _lib.stream(z.device), timer='tasnet_mask_head_forward')
     return m, add
 
 
@@ -443,9 +424,8 @@ def tasnet_mask_head_backward(gm, m, g_additional, A, activation):
     K, B, N, E = m.shape
     assert gm.shape == m.shape and (g_additional is None or g_additional.shape == (B, A, E))
     gz = torch.empty((B, E, A + K * N), dtype=torch.float32, device=m.device)
-    _lib.check(_lib.timed('tasnet_mask_head_backward', _lib.load().ptmi_tasnet_mask_head_backward, gm.data_ptr(), m.data_ptr(),
-                          _lib.ptr(g_additional) if A else None, gz.data_ptr(), B, E, N, K, A, activation, _lib.stream(m.device)),
-               'ptmi_tasnet_mask_head_backward')
+    _lib.call('ptmi_tasnet_mask_head_backward', gm.data_ptr(), m.data_ptr(), _lib.ptr(g_additional) if A else None, gz.data_ptr(), B, E, N,
+              K, A, activation, _lib.stream(m.device), timer='tasnet_mask_head_backward')
     return gz
 
 
@@ -458,8 +438,8 @@ def tasnet_center(x, K, B, T_in, T_out, backward):
     assert x.shape == ((B, K, T_out) if backward else (K, B, T_in)), (x.shape, K, B, T_in, T_out, backward)
     out = torch.empty((K, B, T_in) if backward else (B, K, T_out), dtype=torch.float32, device=x.device)
     ws = _doubles(lib.ptmi_tasnet_center_workspace_elems(K, B, T_in, T_out), x.device)
-    _lib.check(_lib.timed('tasnet_center', lib.ptmi_tasnet_center, x.data_ptr(), out.data_ptr(), ws.data_ptr(), K, B, T_in, T_out,
-                          int(backward), _lib.stream(x.device)), 'ptmi_tasnet_center')
+    _lib.call('ptmi_tasnet_center', x.data_ptr(), out.data_ptr(), ws.data_ptr(), K, B, T_in, T_out, int(backward), _lib.stream(x.device),
+              timer='tasnet_center')
     return out
 
 
@@ -480,10 +460,9 @@ def td_rect_stats(est, tgt, want_gram):
     stats = _doubles(B * (M * K + M), est.device).view(B, M * K + M)
     gram = _doubles(B * K * K if want_gram else 0, est.device).view(B if want_gram else 0, K, K)
     ws = _doubles(lib.ptmi_td_rect_workspace_elems(B, M, K, T), est.device)
-    strides = _lib.strides4(est.stride(0), est.stride(1), *((tgt.stride(0), tgt.stride(1)) if K else (0, 0)))
-    _lib.check(_lib.timed('td_rect_stats', lib.ptmi_td_rect_stats, est.data_ptr(), tgt.data_ptr() if K else None, B, M, K, T, strides,
-                          ws.data_ptr(), stats.data_ptr(), gram.data_ptr() if want_gram and K else None, _lib.stream(est.device)),
-               'ptmi_td_rect_stats')
+    strides = _lib.int64s(est.stride(0), est.stride(1), *((tgt.stride(0), tgt.stride(1)) if K else (0, 0)))
+    _lib.call('ptmi_td_rect_stats', est.data_ptr(), tgt.data_ptr() if K else None, B, M, K, T, strides, ws.data_ptr(), stats.data_ptr(),
+              gram.data_ptr() if want_gram and K else None, _lib.stream(est.device), timer='td_rect_stats')
     return stats, gram
 
 
@@ -502,8 +481,8 @@ def orpit_select(stats, gram, alive, n):
     coef_a = torch.empty((B, 2), dtype=torch.float32, device=dev)
     coef_b = torch.empty((B, 2, K), dtype=torch.float32, device=dev)
     none = (lambda t: t.data_ptr() if K else None)
-    _lib.check(_lib.timed('orpit_select', _lib.load().ptmi_orpit_select, stats.data_ptr(), none(gram), none(alive), none(alive_out),
-                          loss.data_ptr(), choice.data_ptr(), coef_a.data_ptr(), none(coef_b), B, K, n, _lib.stream(dev)), 'ptmi_orpit_select')
+    _lib.call('ptmi_orpit_select', stats.data_ptr(), none(gram), none(alive), none(alive_out), loss.data_ptr(), choice.data_ptr(),
+              coef_a.data_ptr(), none(coef_b), B, K, n, _lib.stream(dev), timer='orpit_select')
     return loss, choice, alive_out, coef_a, coef_b
 
 
@@ -516,10 +495,9 @@ def td_rect_lincomb(est, tgt, g, coef_a, coef_b):
     _f32c(g, coef_a, coef_b)
     assert coef_a.shape == (B, M) and coef_b.shape == (B, M, K) and (g is None or g.shape == (B,)), (coef_a.shape, coef_b.shape)
     out = torch.empty((B, M, T), dtype=torch.float32, device=est.device)
-    strides = _lib.strides6(est.stride(0), est.stride(1), *((tgt.stride(0), tgt.stride(1)) if K else (0, 0)), out.stride(0), out.stride(1))
-    _lib.check(_lib.timed('td_rect_lincomb', _lib.load().ptmi_td_rect_lincomb, est.data_ptr(), tgt.data_ptr() if K else None, _lib.ptr(g),
-                          coef_a.data_ptr(), coef_b.data_ptr() if K else None, B, M, K, T, strides, out.data_ptr(),
-                          _lib.stream(est.device)), 'ptmi_td_rect_lincomb')
+    strides = _lib.int64s(est.stride(0), est.stride(1), *((tgt.stride(0), tgt.stride(1)) if K else (0, 0)), out.stride(0), out.stride(1))
+    _lib.call('ptmi_td_rect_lincomb', est.data_ptr(), tgt.data_ptr() if K else None, _lib.ptr(g), coef_a.data_ptr(),
+              coef_b.data_ptr() if K else None, B, M, K, T, strides, out.data_ptr(), _lib.stream(est.device), timer='td_rect_lincomb')
     return out
 
 
@@ -550,9 +528,9 @@ def orpit_flag_forward(additional, weight, bias, mask, encoded, k):
     flag = torch.empty(B, dtype=torch.float32, device=dev)
     stat = _doubles(2 * B, dev).view(B, 2)
     ws = _doubles(lib.ptmi_orpit_flag_workspace_elems(B, A, E), dev)
-    _lib.check(_lib.timed('orpit_flag_forward', lib.ptmi_orpit_flag_forward, additional.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                          _lib.ptr(mask), _lib.ptr(encoded), pre.data_ptr(), w.data_ptr() if K else None, flag.data_ptr(), stat.data_ptr(),
-                          ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev)), 'ptmi_orpit_flag_forward')
+    _lib.call('ptmi_orpit_flag_forward', additional.data_ptr(), weight.data_ptr(), bias.data_ptr(), _lib.ptr(mask), _lib.ptr(encoded),
+              pre.data_ptr(), w.data_ptr() if K else None, flag.data_ptr(), stat.data_ptr(), ws.data_ptr(), B, A, E, N, K, k, int(K > 0),
+              _lib.stream(dev), timer='orpit_flag_forward')
     return pre, flag, w, stat
 
 
@@ -570,10 +548,10 @@ def orpit_flag_backward(gflag, gpre, flag, stat, pre, w, additional, weight, mas
     dmask = torch.empty_like(mask) if K else None
     denc = torch.empty_like(encoded) if encoded is not None else None
     ws = _doubles(lib.ptmi_orpit_flag_workspace_elems(B, A, E), dev)
-    _lib.check(_lib.timed('orpit_flag_backward', lib.ptmi_orpit_flag_backward, gflag.data_ptr(), _lib.ptr(gpre), flag.data_ptr(),
-                          stat.data_ptr(), pre.data_ptr(), w.data_ptr() if K else None, additional.data_ptr(), weight.data_ptr(),
-                          _lib.ptr(mask), _lib.ptr(encoded), dadd.data_ptr(), dparams.data_ptr(), _lib.ptr(dmask), _lib.ptr(denc),
-                          ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev)), 'ptmi_orpit_flag_backward')
+    _lib.call('ptmi_orpit_flag_backward', gflag.data_ptr(), _lib.ptr(gpre), flag.data_ptr(), stat.data_ptr(), pre.data_ptr(),
+              w.data_ptr() if K else None, additional.data_ptr(), weight.data_ptr(), _lib.ptr(mask), _lib.ptr(encoded), dadd.data_ptr(),
+              dparams.data_ptr(), _lib.ptr(dmask), _lib.ptr(denc), ws.data_ptr(), B, A, E, N, K, k, int(K > 0), _lib.stream(dev),
+              timer='orpit_flag_backward')
     return dadd, dparams, dmask, denc
 
 
@@ -591,7 +569,7 @@ def _mask_loss_args(logits, target, power, num_frames):
         assert t is None or F == 1 or t.stride(3) == 1, t.stride()
     assert num_frames is None or (num_frames.dtype == torch.int32 and num_frames.shape == (B,) and num_frames.is_contiguous()), \
         (num_frames.dtype, num_frames.shape)
-    strides = (ctypes.c_int64 * 9)(*logits.stride()[:3], *target.stride()[:3], *(power.stride()[:3] if kind else (0, 0, 0)))
+    strides = _lib.int64s(*logits.stride()[:3], *target.stride()[:3], *(power.stride()[:3] if kind else (0, 0, 0)))
     return B, C, T, F, kind, strides
 
 
@@ -609,9 +587,9 @@ def mask_loss_forward(logits, target, power, num_frames, reduction):
     stat = _doubles(4 * B, dev).view(B, 4)
     sel = torch.empty((B, 2), dtype=torch.int32, device=dev)
     ws = _doubles(lib.ptmi_mask_loss_workspace_elems(B, C, T, F), dev)
-    _lib.check(_lib.timed('mask_loss_forward', lib.ptmi_mask_loss_forward, logits.data_ptr(), target.data_ptr(), _lib.ptr(power), kind,
-                          _lib.ptr(num_frames), strides, B, C, T, F, reduction, ws.data_ptr(), pooled.data_ptr(), _lib.ptr(weighted),
-                          stat.data_ptr(), sel.data_ptr(), _lib.stream(dev)), 'ptmi_mask_loss_forward')
+    _lib.call('ptmi_mask_loss_forward', logits.data_ptr(), target.data_ptr(), _lib.ptr(power), kind, _lib.ptr(num_frames), strides, B, C, T,
+              F, reduction, ws.data_ptr(), pooled.data_ptr(), _lib.ptr(weighted), stat.data_ptr(), sel.data_ptr(), _lib.stream(dev),
+              timer='mask_loss_forward')
     return pooled, weighted, stat, sel
 
 
@@ -619,16 +597,15 @@ def mask_loss_forward(logits, target, power, num_frames, reduction):
            'Tensor stat, Tensor sel, int reduction) -> Tensor')
 def mask_loss_backward(logits, target, power, num_frames, g_pooled, g_weighted, stat, sel, reduction):
     """``d logits [B, C, T, F]`` (dense) from ``g_pooled`` / ``g_weighted [B]`` (either may be None) (``ptmi_mask_loss_backward``)."""
-    lib = _lib.load()
     B, C, T, F, kind, strides = _mask_loss_args(logits, target, power, num_frames)
     _f32c(g_pooled, g_weighted)
     assert (g_pooled is None or g_pooled.shape == (B,)) and (g_weighted is None or g_weighted.shape == (B,))
     assert stat.shape == (B, 4) and stat.dtype == torch.float64 and sel.shape == (B, 2) and sel.dtype == torch.int32
     dev = logits.device
     out = torch.empty((B, C, T, F), dtype=torch.float32, device=dev)
-    _lib.check(_lib.timed('mask_loss_backward', lib.ptmi_mask_loss_backward, logits.data_ptr(), target.data_ptr(), _lib.ptr(power), kind,
-                          _lib.ptr(num_frames), strides, _lib.ptr(g_pooled), _lib.ptr(g_weighted), stat.data_ptr(), sel.data_ptr(),
-                          B, C, T, F, reduction, out.data_ptr(), _lib.stream(dev)), 'ptmi_mask_loss_backward')
+    _lib.call('ptmi_mask_loss_backward', logits.data_ptr(), target.data_ptr(), _lib.ptr(power), kind, _lib.ptr(num_frames), strides,
+              _lib.ptr(g_pooled), _lib.ptr(g_weighted), stat.data_ptr(), sel.data_ptr(), B, C, T, F, reduction, out.data_ptr(),
+              _lib.stream(dev), timer='mask_loss_backward')
     return out
 
 
@@ -661,8 +638,8 @@ def bf_psd(observation, mask0, mask1, frames, normalize):
     dev = observation.device
     psd = _doubles(M * B * F * C * C * 2, dev).view(M, B, F, C, C, 2)
     ws = _doubles(lib.ptmi_bf_psd_workspace_elems(B, C, T, F, M), dev)
-    _lib.check(_lib.timed('bf_psd', lib.ptmi_bf_psd, observation.data_ptr(), _lib.ptr(mask0), _lib.ptr(mask1), _bf_frames(frames, B),
-                          B, C, T, F, M, mode, int(normalize), ws.data_ptr(), psd.data_ptr(), _lib.stream(dev)), 'ptmi_bf_psd')
+    _lib.call('ptmi_bf_psd', observation.data_ptr(), _lib.ptr(mask0), _lib.ptr(mask1), _bf_frames(frames, B), B, C, T, F, M, mode,
+              int(normalize), ws.data_ptr(), psd.data_ptr(), _lib.stream(dev), timer='bf_psd')
     return torch.view_as_complex(psd)
 
 
@@ -679,9 +656,8 @@ def bf_souden(target_psd, noise_psd, ref_channel):
     w = torch.empty((B, F, C), dtype=torch.complex64, device=dev)
     ref = torch.empty(B, dtype=torch.int32, device=dev)
     numden = _doubles(B * F * C * 2 if ref_channel < 0 else 0, dev)
-    _lib.check(_lib.timed('bf_souden', _lib.load().ptmi_bf_souden, target_psd.data_ptr(), noise_psd.data_ptr(), B, F, C,
-                          max(int(ref_channel), -1), w_all.data_ptr(), numden.data_ptr() if ref_channel < 0 else None, w.data_ptr(),
-                          ref.data_ptr(), _lib.stream(dev)), 'ptmi_bf_souden')
+    _lib.call('ptmi_bf_souden', target_psd.data_ptr(), noise_psd.data_ptr(), B, F, C, max(int(ref_channel), -1), w_all.data_ptr(),
+              numden.data_ptr() if ref_channel < 0 else None, w.data_ptr(), ref.data_ptr(), _lib.stream(dev), timer='bf_souden')
     return w, w_all, ref
 
 
@@ -691,8 +667,8 @@ def bf_apply(vector, mix, frames):
     B, C, T, F = _bf_spectrum(mix)
     assert vector.shape == (B, F, C) and vector.dtype == torch.complex64 and vector.is_contiguous(), (vector.shape, vector.dtype)
     out = torch.empty((B, T, F), dtype=torch.complex64, device=mix.device)
-    _lib.check(_lib.timed('bf_apply', _lib.load().ptmi_bf_apply, vector.data_ptr(), mix.data_ptr(), _bf_frames(frames, B), B, C, T, F,
-                          out.data_ptr(), _lib.stream(mix.device)), 'ptmi_bf_apply')
+    _lib.call('ptmi_bf_apply', vector.data_ptr(), mix.data_ptr(), _bf_frames(frames, B), B, C, T, F, out.data_ptr(),
+              _lib.stream(mix.device), timer='bf_apply')
     return out
 
 
@@ -717,8 +693,8 @@ def bf_eig(target_psd, noise_psd, gev, ban):
     w = torch.empty((B, F, C), dtype=torch.complex64, device=dev)
     lam = torch.empty((B, F), dtype=torch.float64, device=dev)
     sweeps = torch.empty((B, F), dtype=torch.int32, device=dev)
-    _lib.check(_lib.timed('bf_eig', _lib.load().ptmi_bf_eig, target_psd.data_ptr(), _lib.ptr(noise_psd), B, F, C, 0 if gev else 1,
-                          int(ban), w.data_ptr(), lam.data_ptr(), sweeps.data_ptr(), _lib.stream(dev)), 'ptmi_bf_eig')
+    _lib.call('ptmi_bf_eig', target_psd.data_ptr(), _lib.ptr(noise_psd), B, F, C, 0 if gev else 1, int(ban), w.data_ptr(), lam.data_ptr(),
+              sweeps.data_ptr(), _lib.stream(dev), timer='bf_eig')
     return w, lam, sweeps
 
 
@@ -730,8 +706,7 @@ def bf_ban(vector, noise_psd):
     assert noise_psd.shape == (B, F, C, C) and noise_psd.dtype == torch.complex128 and noise_psd.is_contiguous(), \
         (noise_psd.shape, noise_psd.dtype)
     out = torch.empty_like(vector)
-    _lib.check(_lib.timed('bf_ban', _lib.load().ptmi_bf_ban, vector.data_ptr(), noise_psd.data_ptr(), B, F, C, out.data_ptr(),
-                          _lib.stream(vector.device)), 'ptmi_bf_ban')
+    _lib.call('ptmi_bf_ban', vector.data_ptr(), noise_psd.data_ptr(), B, F, C, out.data_ptr(), _lib.stream(vector.device), timer='bf_ban')
     return out
 
 
@@ -740,8 +715,7 @@ def bf_phase(vector):
     """``vector [B, F, C]`` complex64 -> the vector with the phase of every bin aligned to the bin before it (``ptmi_bf_phase``)."""
     B, F, C = _bf_vector(vector)
     out = torch.empty_like(vector)
-    _lib.check(_lib.timed('bf_phase', _lib.load().ptmi_bf_phase, vector.data_ptr(), B, F, C, out.data_ptr(),
-                          _lib.stream(vector.device)), 'ptmi_bf_phase')
+    _lib.call('ptmi_bf_phase', vector.data_ptr(), B, F, C, out.data_ptr(), _lib.stream(vector.device), timer='bf_phase')
     return out
 
 
@@ -768,7 +742,7 @@ def _zero_word(device):
 @_register('absmax(Tensor x, int rows, int cols, int ld) -> Tensor')
 def absmax(x, rows, cols, ld):
     out = _zero_word(x.device)
-    _lib.check(_lib.load().ptmi_absmax_accumulate(x.data_ptr(), rows, cols, ld, out.data_ptr(), _lib.stream(x.device)), 'ptmi_absmax')
+    _lib.call('ptmi_absmax_accumulate', x.data_ptr(), rows, cols, ld, out.data_ptr(), _lib.stream(x.device))
     return out
 
 
@@ -777,14 +751,10 @@ def _lstm_backward_persistent(gates, c, c0, dhy, w_hh_t, dg, dg_t, scratch, dc_c
     """The one call of ``ptmi_lstm_backward_persistent`` (include/ptmi.h has its contract).  False: the configuration cannot be kept
     resident, or the call does not support the combination of arguments - nothing was enqueued, the caller takes another route;
     every other refusal raises."""
-    rc = _lib.timed('lstm_backward', _lib.load().ptmi_lstm_backward_persistent, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0),
-                    dhy.data_ptr(), _lib.ptr(dc_n), w_hh_t.data_ptr(), _lib.ptr(dg), _lib.ptr(dg_t), bs_dev.data_ptr(), offs_dev.data_ptr(),
-                    _lib.ptr(step_masks), scratch.data_ptr(), _lib.ptr(dc_carry), T, max_batch, rows, H, ndir, s_begin, s_end,
-                    int(prefilled), _lib.stream(gates.device))
-    if rc == -2:
-        return False
-    _lib.check(rc, 'ptmi_lstm_backward_persistent')
-    return True
+    return 0 == _lib.call('ptmi_lstm_backward_persistent', gates.data_ptr(), c.data_ptr(), _lib.ptr(c0), dhy.data_ptr(), _lib.ptr(dc_n),
+                          w_hh_t.data_ptr(), _lib.ptr(dg), _lib.ptr(dg_t), bs_dev.data_ptr(), offs_dev.data_ptr(), _lib.ptr(step_masks),
+                          scratch.data_ptr(), _lib.ptr(dc_carry), T, max_batch, rows, H, ndir, s_begin, s_end, int(prefilled),
+                          _lib.stream(gates.device), timer='lstm_backward', accept=(-2,))
 
 
 @_register('lstm_recurrence_backward_range(Tensor gates, Tensor c, Tensor? c0, Tensor dhy, Tensor w_hh_t, Tensor(a!) dg, '
@@ -824,7 +794,7 @@ def lstm_bias_grad_add_(db, bias_ih_grad, bias_hh_grad):
     assert all(t.is_contiguous() and t.numel() == n and t.dtype == torch.float32 for t in list(bias_ih_grad) + list(bias_hh_grad))
     ih = (ctypes.c_void_p * ndir)(*[t.data_ptr() for t in bias_ih_grad])
     hh = (ctypes.c_void_p * ndir)(*[t.data_ptr() for t in bias_hh_grad])
-    _lib.check(_lib.load().ptmi_lstm_bias_grad_add(db.data_ptr(), ndir, n, ih, hh, _lib.stream(db.device)), 'ptmi_lstm_bias_grad_add')
+    _lib.call('ptmi_lstm_bias_grad_add', db.data_ptr(), ndir, n, ih, hh, _lib.stream(db.device))
 
 
 # ------------------------------------------------------------------------------------------------ LSTM parameter forms
@@ -839,9 +809,8 @@ def lstm_weight_prep(w_ih, w_hh, b_ih, b_hh, KP):
     w_pad, w_t = torch.empty((ndir, G, KP), **f32), torch.empty((ndir, H, G), **f32)
     amax = torch.empty(2, dtype=torch.int32, device=dev)
     ptrs = [(ctypes.c_void_p * ndir)(*[t.data_ptr() for t in ts]) for ts in (w_ih, w_hh, b_ih, b_hh)]
-    _lib.check(_lib.timed('lstm_weight_prep', _lib.load().ptmi_lstm_weight_prep, *ptrs, ndir, H, I, w_ih_cat.data_ptr(), Ipad,
-                          bias.data_ptr(), w_pad.data_ptr(), KP, w_t.data_ptr(), amax.data_ptr(), _lib.stream(dev)),
-               'ptmi_lstm_weight_prep')
+    _lib.call('ptmi_lstm_weight_prep', *ptrs, ndir, H, I, w_ih_cat.data_ptr(), Ipad, bias.data_ptr(), w_pad.data_ptr(), KP, w_t.data_ptr(),
+              amax.data_ptr(), _lib.stream(dev), timer='lstm_weight_prep')
     return w_ih_cat, bias, w_pad, w_t, amax
 
 
@@ -851,8 +820,7 @@ def grad_norm(flat):
     lib = _lib.load()
     ws = torch.empty(int(lib.ptmi_grad_norm_workspace_elems()), dtype=torch.float64, device=flat.device)
     out = torch.empty((), dtype=torch.float32, device=flat.device)
-    _lib.check(_lib.timed('grad_norm', lib.ptmi_grad_norm, flat.data_ptr(), flat.numel(), ws.data_ptr(), out.data_ptr(),
-                          _lib.stream(flat.device)), 'ptmi_grad_norm')
+    _lib.call('ptmi_grad_norm', flat.data_ptr(), flat.numel(), ws.data_ptr(), out.data_ptr(), _lib.stream(flat.device), timer='grad_norm')
     return out
 
 
@@ -867,10 +835,9 @@ def adam_flat_(flat_grad, exp_avg, exp_avg_sq, segments, params, norm, max_norm,
     if hyper is not None:
         assert hyper.dtype == torch.float64 and hyper.numel() >= 6 and hyper.device == flat_grad.device and hyper.is_contiguous(), hyper
     applied = torch.empty((), dtype=torch.float32, device=flat_grad.device)
-    _lib.check(_lib.timed('adam_flat', _lib.load().ptmi_adam_flat, flat_grad.data_ptr(), exp_avg.data_ptr(),
-                          exp_avg_sq.data_ptr(), segments.data_ptr(), segments.shape[0], flat_grad.numel(), _lib.ptr(norm),
-                          max_norm, _lib.ptr(found_inf), _lib.ptr(finite), applied.data_ptr(), step.data_ptr(), lr, beta1, beta2,
-                          eps, weight_decay, _lib.ptr(hyper), int(zero_grad), _lib.stream(flat_grad.device)), 'ptmi_adam_flat')
+    _lib.call('ptmi_adam_flat', flat_grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), segments.data_ptr(), segments.shape[0],
+              flat_grad.numel(), _lib.ptr(norm), max_norm, _lib.ptr(found_inf), _lib.ptr(finite), applied.data_ptr(), step.data_ptr(), lr,
+              beta1, beta2, eps, weight_decay, _lib.ptr(hyper), int(zero_grad), _lib.stream(flat_grad.device), timer='adam_flat')
     return applied
 
 
@@ -881,8 +848,8 @@ def pack_planes_t(x, amax):
     lib = _lib.load()
     k, c = x.shape
     out = torch.empty(int(lib.ptmi_planes_elems(c, k)), dtype=torch.float16, device=x.device)
-    _lib.check(_lib.timed(f'pack_planes_t:{k}x{c}', lib.ptmi_pack_planes_t, x.data_ptr(), k, c, _ld(x), _lib.ptr(amax), out.data_ptr(),
-                          _lib.stream(x.device)), 'ptmi_pack_planes_t')
+    _lib.call('ptmi_pack_planes_t', x.data_ptr(), k, c, _ld(x), _lib.ptr(amax), out.data_ptr(), _lib.stream(x.device),
+              timer=f'pack_planes_t:{k}x{c}')
     return out
 
 
@@ -892,8 +859,8 @@ def pack_planes_n(x, amax):
     lib = _lib.load()
     r, k = x.shape
     out = torch.empty(int(lib.ptmi_planes_elems(r, k)), dtype=torch.float16, device=x.device)
-    _lib.check(_lib.timed(f'pack_planes_n:{r}x{k}', lib.ptmi_pack_planes_n, x.data_ptr(), r, k, _ld(x), _lib.ptr(amax), out.data_ptr(),
-                          _lib.stream(x.device)), 'ptmi_pack_planes_n')
+    _lib.call('ptmi_pack_planes_n', x.data_ptr(), r, k, _ld(x), _lib.ptr(amax), out.data_ptr(), _lib.stream(x.device),
+              timer=f'pack_planes_n:{r}x{k}')
     return out
 
 
@@ -917,12 +884,10 @@ def gemm_planes_relu_(out, a, amax_a, b, amax_b, bias, M, N, K, split_k, amax_ou
 @_register('relu_backward_absmax(Tensor g, Tensor y, Tensor(a!) amax_out) -> Tensor')
 def relu_backward_absmax(g, y, amax_out):
     """``g`` where ``y > 0`` (``y``: the ReLU's output) else 0, and the float bits of its ``max |.|`` into the ZEROED word ``amax_out``."""
-    lib = _lib.load()
     assert g.dim() == 2 and g.shape == y.shape and g.stride(1) == 1 and y.stride(1) == 1
     out = torch.empty((g.shape[0], g.shape[1]), dtype=torch.float32, device=g.device)
-    _lib.check(_lib.timed(f'relu_backward_absmax:{g.shape[0]}x{g.shape[1]}', lib.ptmi_relu_backward_absmax, g.data_ptr(), y.data_ptr(),
-                          out.data_ptr(), g.shape[0], g.shape[1], _ld(g), _ld(y), _ld(out), amax_out.data_ptr(), 1, _lib.stream(g.device)),
-               'ptmi_relu_backward_absmax')
+    _lib.call('ptmi_relu_backward_absmax', g.data_ptr(), y.data_ptr(), out.data_ptr(), g.shape[0], g.shape[1], _ld(g), _ld(y), _ld(out),
+              amax_out.data_ptr(), 1, _lib.stream(g.device), timer=f'relu_backward_absmax:{g.shape[0]}x{g.shape[1]}')
     return out
 
 
@@ -943,8 +908,7 @@ def _gemm_planes_call(entry, timer, out, M, N, K, split_k, head, tail=()):
     lib = _lib.load()
     nws = int(lib.ptmi_gemm_planes_workspace_elems(M, N, K, split_k))
     ws = torch.empty(nws, dtype=torch.float32, device=out.device) if nws else None
-    _lib.check(_lib.timed(f'{timer}:{M}x{N}x{K}:{split_k}', getattr(lib, entry), *head, split_k, _products(), _lib.ptr(ws), *tail,
-                          _lib.stream(out.device)), entry)
+    _lib.call(entry, *head, split_k, _products(), _lib.ptr(ws), *tail, _lib.stream(out.device), timer=f'{timer}:{M}x{N}x{K}:{split_k}')
 
 
 @_register('pack_planes_bf16(Tensor x, bool transposed) -> Tensor')
@@ -955,9 +919,8 @@ def pack_planes_bf16(x, transposed):
     a, b = x.shape
     rows, k = (b, a) if transposed else (a, b)
     out = torch.empty(int(lib.ptmi_planes_elems(rows, k)), dtype=torch.bfloat16, device=x.device)
-    fn = lib.ptmi_pack_planes_t_bf16 if transposed else lib.ptmi_pack_planes_n_bf16
-    _lib.check(_lib.timed(f'pack_planes_bf16:{a}x{b}', fn, x.data_ptr(), a, b, _ld(x), out.data_ptr(), _lib.stream(x.device)),
-               'ptmi_pack_planes_bf16')
+    _lib.call('ptmi_pack_planes_t_bf16' if transposed else 'ptmi_pack_planes_n_bf16', x.data_ptr(), a, b, _ld(x), out.data_ptr(),
+              _lib.stream(x.device), timer=f'pack_planes_bf16:{a}x{b}')
     return out
 
 
@@ -965,13 +928,11 @@ def pack_planes_bf16(x, transposed):
 def pack_planes_into_(out, x, amax, transposed, kb_total, kb_offset, kb_count):
     """A pack pass writing ``kb_count`` k blocks at k block ``kb_offset`` of planes ``out`` that have ``kb_total`` k blocks per row
     tile (``ptmi_pack_planes_into``); fp16 or bf16 by ``out.dtype``; ``x [r, k]``, or ``[k, c]`` when ``transposed``."""
-    lib = _lib.load()
     a, b = x.shape
     rows = b if transposed else a
     assert out.dtype in (torch.float16, torch.bfloat16) and out.numel() >= (rows + 15) // 16 * kb_total * 1024, (out.dtype, out.numel())
-    _lib.check(_lib.timed(f'pack_planes_into:{a}x{b}', lib.ptmi_pack_planes_into, x.data_ptr(), a, b, _ld(x), int(transposed),
-                          int(out.dtype == torch.bfloat16), _lib.ptr(amax), out.data_ptr(), kb_total, kb_offset, kb_count,
-                          _lib.stream(x.device)), 'ptmi_pack_planes_into')
+    _lib.call('ptmi_pack_planes_into', x.data_ptr(), a, b, _ld(x), int(transposed), int(out.dtype == torch.bfloat16), _lib.ptr(amax),
+              out.data_ptr(), kb_total, kb_offset, kb_count, _lib.stream(x.device), timer=f'pack_planes_into:{a}x{b}')
 
 
 @_register('gemm_planes_bf16_(Tensor(a!) out, Tensor a, int a_offset, Tensor b, Tensor? bias, int M, int N, int K, bool accumulate, '
@@ -1005,10 +966,10 @@ def pack_planes_bf16_list(xs):
     outs = [torch.empty(int(lib.ptmi_planes_elems(x.shape[1], k)), dtype=torch.bfloat16, device=x.device) for x in xs]
     src = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
     dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-    cols = (ctypes.c_int64 * n)(*[x.shape[1] for x in xs])
-    ld = (ctypes.c_int64 * n)(*[_ld(x) for x in xs])
-    _lib.check(_lib.timed(f'pack_planes_bf16_list:{k}x{sum(x.shape[1] for x in xs)}', lib.ptmi_pack_planes_t_bf16_list, src, cols, ld, dst, n,
-                          k, _lib.stream(xs[0].device)), 'ptmi_pack_planes_t_bf16_list')
+    cols = _lib.int64s(*[x.shape[1] for x in xs])
+    ld = _lib.int64s(*[_ld(x) for x in xs])
+    _lib.call('ptmi_pack_planes_t_bf16_list', src, cols, ld, dst, n, k, _lib.stream(xs[0].device),
+              timer=f'pack_planes_bf16_list:{k}x{sum(x.shape[1] for x in xs)}')
     return outs
 
 
@@ -1036,12 +997,8 @@ def gemm_planes_bf16_group_(outs, blocks, a, a_offset, M, m_split, bs, ns, K, ac
         return False
     ws = torch.empty(int(lib.ptmi_gemm_planes_group_workspace_elems(M, m_split, n, S, c, K, split_k)), dtype=torch.float32, device=a.device)
     shape = f'{M}/{m_split}x{"+".join(str(int(v)) for v in ns)}x{K}'
-    rc = _lib.timed(f'gemm_group_bf16:{shape}:{split_k}', lib.ptmi_gemm_planes_bf16_group, a.data_ptr() + a_offset, M, m_split, b, n, S, c,
-                    ldc, K, int(accumulate), split_k, _products(), ws.data_ptr(), _lib.stream(a.device))
-    if rc == -2:            # PTMI_E_UNSUPPORTED
-        return False
-    _lib.check(rc, 'ptmi_gemm_planes_bf16_group')
-    return True
+    return 0 == _lib.call('ptmi_gemm_planes_bf16_group', a.data_ptr() + a_offset, M, m_split, b, n, S, c, ldc, K, int(accumulate), split_k,
+                          _products(), ws.data_ptr(), _lib.stream(a.device), timer=f'gemm_group_bf16:{shape}:{split_k}', accept=(-2,))
 
 
 # ------------------------------------------------------------------------------------------------ unit norm
@@ -1050,8 +1007,8 @@ def unit_norm_forward(x, eps):
     N, E, F = x.shape
     y = torch.empty_like(x)
     inv = torch.empty((N, F), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.timed('unit_norm_forward', _lib.load().ptmi_unit_norm_forward, _lib.ptr(x), _lib.ptr(y), _lib.ptr(inv),
-                          N, E, F, eps, _lib.stream(x.device)), 'ptmi_unit_norm_forward')
+    _lib.call('ptmi_unit_norm_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(inv), N, E, F, eps, _lib.stream(x.device),
+              timer='unit_norm_forward')
     return y, inv
 
 
@@ -1059,8 +1016,8 @@ def unit_norm_forward(x, eps):
 def unit_norm_backward(gy, y, inv, eps):
     N, E, F = y.shape
     dx = torch.empty_like(y)
-    _lib.check(_lib.timed('unit_norm_backward', _lib.load().ptmi_unit_norm_backward, _lib.ptr(gy), _lib.ptr(y), _lib.ptr(inv),
-                          _lib.ptr(dx), N, E, F, eps, _lib.stream(y.device)), 'ptmi_unit_norm_backward')
+    _lib.call('ptmi_unit_norm_backward', _lib.ptr(gy), _lib.ptr(y), _lib.ptr(inv), _lib.ptr(dx), N, E, F, eps, _lib.stream(y.device),
+              timer='unit_norm_backward')
     return dx
 
 
@@ -1086,17 +1043,14 @@ def lstm_recurrence_forward(gates, hy, c0, w_hh_pad, w_amax, bs_dev, offs_dev, b
         flags = scratch if scratch is not None else torch.empty(n, dtype=torch.int32, device=dev)
         assert flags.numel() >= n and flags.dtype == torch.int32
         assert step_masks is None or (step_masks.dtype == torch.int64 and step_masks.numel() == 3 * T)
-        rc = _lib.timed('lstm_forward', lib.ptmi_lstm_forward_persistent, gates.data_ptr(), hy.data_ptr(), c.data_ptr(),
-                        _lib.ptr(c0), w_hh_pad.data_ptr(), _lib.ptr(w_amax), bs_dev.data_ptr(), offs_dev.data_ptr(),
-                        _lib.ptr(step_masks), flags.data_ptr(), T, max_batch, rows, H, KP, ndir,
-                        int(bool(prefilled and scratch is not None)), _lib.ptr(backward_scratch), st)
-        if rc != -2 or step_masks is not None:          # (a row-slot batch has no step-per-launch form)
-            _lib.check(rc, 'ptmi_lstm_forward_persistent')
+        rc = _lib.call('ptmi_lstm_forward_persistent', gates.data_ptr(), hy.data_ptr(), c.data_ptr(), _lib.ptr(c0), w_hh_pad.data_ptr(),
+                       _lib.ptr(w_amax), bs_dev.data_ptr(), offs_dev.data_ptr(), _lib.ptr(step_masks), flags.data_ptr(), T, max_batch, rows,
+                       H, KP, ndir, int(bool(prefilled and scratch is not None)), _lib.ptr(backward_scratch), st, timer='lstm_forward',
+                       accept=(-2,) if step_masks is None else ())          # (a row-slot batch has no step-per-launch form)
     if rc == -2:        # configuration not resident-able: one launch per timestep
         flags = None
-        _lib.check(_lib.timed('lstm_forward', lib.ptmi_lstm_forward, gates.data_ptr(), hy.data_ptr(), c.data_ptr(), _lib.ptr(c0),
-                              w_hh_pad.data_ptr(), ctypes.c_void_p(bs_host), ctypes.c_void_p(offs_host), T, max_batch, H, KP, ndir,
-                              st), 'ptmi_lstm_forward')
+        _lib.call('ptmi_lstm_forward', gates.data_ptr(), hy.data_ptr(), c.data_ptr(), _lib.ptr(c0), w_hh_pad.data_ptr(),
+                  ctypes.c_void_p(bs_host), ctypes.c_void_p(offs_host), T, max_batch, H, KP, ndir, st, timer='lstm_forward')
     return c, flags
 
 
@@ -1122,9 +1076,9 @@ def lstm_recurrence_backward(gates, c, c0, dhy, w_hh_t, bs_dev, offs_dev, bs_hos
     if not persistent:
         flags = None
         dcs = torch.empty((max_batch, ndir, H), dtype=torch.float32, device=dev)
-        _lib.check(_lib.timed('lstm_backward', lib.ptmi_lstm_backward, gates.data_ptr(), c.data_ptr(), _lib.ptr(c0), dhy.data_ptr(),
-                              w_hh_t.data_ptr(), dg.data_ptr(), dcs.data_ptr(), ctypes.c_void_p(bs_host), ctypes.c_void_p(offs_host),
-                              T, max_batch, H, ndir, _lib.stream(dev)), 'ptmi_lstm_backward')
+        _lib.call('ptmi_lstm_backward', gates.data_ptr(), c.data_ptr(), _lib.ptr(c0), dhy.data_ptr(), w_hh_t.data_ptr(), dg.data_ptr(),
+                  dcs.data_ptr(), ctypes.c_void_p(bs_host), ctypes.c_void_p(offs_host), T, max_batch, H, ndir, _lib.stream(dev),
+                  timer='lstm_backward')
     return dg, flags
 
 
@@ -1143,8 +1097,8 @@ def dprnn_tables(like, lengths, B, S, K, P):
     chunks = torch.empty(B, dtype=torch.int32, device=dev)
     intra = torch.empty((B * S, 3), dtype=torch.int32, device=dev)
     inter = torch.empty((B * K, 3), dtype=torch.int32, device=dev)
-    _lib.check(_lib.timed('dprnn_tables', _lib.load().ptmi_dprnn_tables, _lib.ptr(lengths), is64, B, S, K, P, chunks.data_ptr(),
-                          intra.data_ptr(), inter.data_ptr(), _lib.stream(dev)), 'ptmi_dprnn_tables')
+    _lib.call('ptmi_dprnn_tables', _lib.ptr(lengths), is64, B, S, K, P, chunks.data_ptr(), intra.data_ptr(), inter.data_ptr(),
+              _lib.stream(dev), timer='dprnn_tables')
     return chunks, intra, inter
 
 
@@ -1169,9 +1123,9 @@ def chunk_lstm_forward(gates, w_hh, w_hh_reverse, b_hh, b_hh_reverse, table, cap
                                                                                   and b_hh_reverse.shape == (4 * H,)))
     h = torch.empty((rows, ndir * H), dtype=torch.float32, device=gates.device)
     c = torch.empty((rows, ndir * H), dtype=torch.float32, device=gates.device)
-    _lib.check(_lib.timed(f'chunk_lstm_forward:{table.shape[0]}x{cap}x{H}', _lib.load().ptmi_chunk_lstm_forward, gates.data_ptr(),
-                          w_hh.data_ptr(), _lib.ptr(w_hh_reverse), b_hh.data_ptr(), _lib.ptr(b_hh_reverse), h.data_ptr(), c.data_ptr(),
-                          table.data_ptr(), table.shape[0], cap, H, ndir, _lib.stream(gates.device)), 'ptmi_chunk_lstm_forward')
+    _lib.call('ptmi_chunk_lstm_forward', gates.data_ptr(), w_hh.data_ptr(), _lib.ptr(w_hh_reverse), b_hh.data_ptr(), _lib.ptr(b_hh_reverse),
+              h.data_ptr(), c.data_ptr(), table.data_ptr(), table.shape[0], cap, H, ndir, _lib.stream(gates.device),
+              timer=f'chunk_lstm_forward:{table.shape[0]}x{cap}x{H}')
     return h, c
 
 
@@ -1184,9 +1138,9 @@ def chunk_lstm_backward(gates, dh, w_hh, w_hh_reverse, h, c, table, cap, H):
     _f32c(dh, w_hh, w_hh_reverse, h, c)
     assert dh.shape == h.shape == c.shape == (rows, ndir * H), (dh.shape, h.shape, c.shape)
     hprev = torch.empty_like(h)
-    _lib.check(_lib.timed(f'chunk_lstm_backward:{table.shape[0]}x{cap}x{H}', _lib.load().ptmi_chunk_lstm_backward, gates.data_ptr(),
-                          dh.data_ptr(), w_hh.data_ptr(), _lib.ptr(w_hh_reverse), h.data_ptr(), c.data_ptr(), hprev.data_ptr(),
-                          table.data_ptr(), table.shape[0], cap, H, ndir, _lib.stream(gates.device)), 'ptmi_chunk_lstm_backward')
+    _lib.call('ptmi_chunk_lstm_backward', gates.data_ptr(), dh.data_ptr(), w_hh.data_ptr(), _lib.ptr(w_hh_reverse), h.data_ptr(),
+              c.data_ptr(), hprev.data_ptr(), table.data_ptr(), table.shape[0], cap, H, ndir, _lib.stream(gates.device),
+              timer=f'chunk_lstm_backward:{table.shape[0]}x{cap}x{H}')
     return hprev
 
 
@@ -1197,8 +1151,8 @@ def _dprnn_colsum(x, twice):
     out = torch.empty(C, dtype=torch.float32, device=x.device)
     out2 = torch.empty(C, dtype=torch.float32, device=x.device) if twice else None
     ws = _doubles(lib.ptmi_dprnn_colsum_workspace_elems(rows, C), x.device)
-    _lib.check(_lib.timed('dprnn_colsum', lib.ptmi_dprnn_colsum, x.data_ptr(), _ld(x), out.data_ptr(), _lib.ptr(out2), ws.data_ptr(), rows,
-                          C, _lib.stream(x.device)), 'ptmi_dprnn_colsum')
+    _lib.call('ptmi_dprnn_colsum', x.data_ptr(), _ld(x), out.data_ptr(), _lib.ptr(out2), ws.data_ptr(), rows, C, _lib.stream(x.device),
+              timer='dprnn_colsum')
     return out, out2
 
 
@@ -1226,9 +1180,8 @@ def dprnn_norm_residual_forward(z, residual, gamma, beta, chunks, S, K, eps):
     assert chunks is None or chunks.numel() == rows // (S * K)
     y = torch.empty_like(z)
     stats = torch.empty((rows, 2), dtype=torch.float32, device=z.device)
-    _lib.check(_lib.timed('dprnn_norm_residual_forward', _lib.load().ptmi_dprnn_norm_residual_forward, z.data_ptr(), residual.data_ptr(),
-                          gamma.data_ptr(), beta.data_ptr(), _lib.ptr(chunks), y.data_ptr(), stats.data_ptr(), rows, N, S, K, eps,
-                          _lib.stream(z.device)), 'ptmi_dprnn_norm_residual_forward')
+    _lib.call('ptmi_dprnn_norm_residual_forward', z.data_ptr(), residual.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _lib.ptr(chunks),
+              y.data_ptr(), stats.data_ptr(), rows, N, S, K, eps, _lib.stream(z.device), timer='dprnn_norm_residual_forward')
     return y, stats
 
 
@@ -1244,9 +1197,9 @@ def dprnn_norm_residual_backward(gy, z, stats, gamma, chunks, S, K):
     dz, dres = torch.empty_like(z), torch.empty_like(z)
     dparams = torch.empty(2 * N, dtype=torch.float32, device=z.device)
     ws = _doubles(lib.ptmi_dprnn_colsum_workspace_elems(rows, N), z.device)
-    _lib.check(_lib.timed('dprnn_norm_residual_backward', lib.ptmi_dprnn_norm_residual_backward, gy.data_ptr(), z.data_ptr(),
-                          stats.data_ptr(), gamma.data_ptr(), _lib.ptr(chunks), dz.data_ptr(), dres.data_ptr(), dparams.data_ptr(),
-                          ws.data_ptr(), rows, N, S, K, _lib.stream(z.device)), 'ptmi_dprnn_norm_residual_backward')
+    _lib.call('ptmi_dprnn_norm_residual_backward', gy.data_ptr(), z.data_ptr(), stats.data_ptr(), gamma.data_ptr(), _lib.ptr(chunks),
+              dz.data_ptr(), dres.data_ptr(), dparams.data_ptr(), ws.data_ptr(), rows, N, S, K, _lib.stream(z.device),
+              timer='dprnn_norm_residual_backward')
     return dz, dres, dparams
 
 
@@ -1259,9 +1212,8 @@ def dprnn_segment(x, K, P):
     B, L, N = x.shape
     S = int(lib.ptmi_dprnn_num_chunks(L, K, P))
     seg = torch.empty((B, S, K, N), dtype=torch.float32, device=x.device)
-    strides = (ctypes.c_int64 * 3)(*x.stride())
-    _lib.check(_lib.timed('dprnn_segment', lib.ptmi_dprnn_segment, x.data_ptr(), strides, seg.data_ptr(), B, L, N, S, K, P,
-                          _lib.stream(x.device)), 'ptmi_dprnn_segment')
+    strides = _lib.int64s(*x.stride())
+    _lib.call('ptmi_dprnn_segment', x.data_ptr(), strides, seg.data_ptr(), B, L, N, S, K, P, _lib.stream(x.device), timer='dprnn_segment')
     return seg
 
 
@@ -1273,9 +1225,9 @@ def dprnn_overlap_add(seg, P, L_out, front):
     assert seg.dim() == 4 and seg.dtype == torch.float32, (seg.shape, seg.dtype)
     B, S, K, N = seg.shape
     out = torch.empty((B, L_out, N), dtype=torch.float32, device=seg.device)
-    strides = (ctypes.c_int64 * 4)(*seg.stride())
-    _lib.check(_lib.timed('dprnn_overlap_add', _lib.load().ptmi_dprnn_overlap_add, seg.data_ptr(), strides, out.data_ptr(), B, L_out, N, S,
-                          K, P, front, _lib.stream(seg.device)), 'ptmi_dprnn_overlap_add')
+    strides = _lib.int64s(*seg.stride())
+    _lib.call('ptmi_dprnn_overlap_add', seg.data_ptr(), strides, out.data_ptr(), B, L_out, N, S, K, P, front, _lib.stream(seg.device),
+              timer='dprnn_overlap_add')
     return out
 
 
@@ -1296,8 +1248,7 @@ def gl_project(a, y):
     griffin_lim.py:55-56, 151-152)."""
     _gl_check(a, y)
     P = torch.empty_like(y)
-    _lib.check(_lib.timed('gl_project', _lib.load().ptmi_gl_project, a.data_ptr(), y.data_ptr(), a.numel(), P.data_ptr(),
-                          _lib.stream(a.device)), 'ptmi_gl_project')
+    _lib.call('ptmi_gl_project', a.data_ptr(), y.data_ptr(), a.numel(), P.data_ptr(), _lib.stream(a.device), timer='gl_project')
     return P
 
 
@@ -1306,8 +1257,8 @@ def gl_project_backward(g, y):
     """``d a = Re(conj(y / |y|) g)``: the adjoint of :func:`gl_project` in ``a`` (``ptmi_gl_project_backward``)."""
     assert g.dtype == y.dtype == torch.float32 and g.is_contiguous() and y.is_contiguous() and g.shape == y.shape and g.shape[-1] == 2
     da = torch.empty(g.shape[:-1], dtype=torch.float32, device=g.device)
-    _lib.check(_lib.timed('gl_project_backward', _lib.load().ptmi_gl_project_backward, g.data_ptr(), y.data_ptr(), da.numel(),
-                          da.data_ptr(), _lib.stream(g.device)), 'ptmi_gl_project_backward')
+    _lib.call('ptmi_gl_project_backward', g.data_ptr(), y.data_ptr(), da.numel(), da.data_ptr(), _lib.stream(g.device),
+              timer='gl_project_backward')
     return da
 
 
@@ -1327,8 +1278,8 @@ def gl_update(xnew, x, a, alpha, P, partials, state):
     is set (``ptmi_gl_update``)."""
     _gl_check(a, xnew, x, P)
     assert partials.dtype == torch.float64 and partials.numel() >= _lib.load().ptmi_gl_partials_elems() and state.dtype == torch.int32
-    _lib.check(_lib.timed('gl_update', _lib.load().ptmi_gl_update, xnew.data_ptr(), x.data_ptr(), a.data_ptr(), a.numel(), alpha,
-                          P.data_ptr(), partials.data_ptr(), state.data_ptr(), _lib.stream(a.device)), 'ptmi_gl_update')
+    _lib.call('ptmi_gl_update', xnew.data_ptr(), x.data_ptr(), a.data_ptr(), a.numel(), alpha, P.data_ptr(), partials.data_ptr(),
+              state.data_ptr(), _lib.stream(a.device), timer='gl_update')
 
 
 @_register('gl_iterations(Tensor a, Tensor(a!) x, Tensor(b!) P, Tensor syn, Tensor window, Tensor twiddle, int[] geom, int samples, '
@@ -1354,19 +1305,17 @@ def gl_iterations(a, x, P, syn, window, twiddle, geom, samples, alpha, iteration
     xnew = None if fused else torch.empty_like(x)
     n = a.numel()
     for it in range(iterations):
-        _lib.check(_lib.timed('gl_istft', lib.ptmi_istft_forward, P.data_ptr(), rows, frames, None, syn.data_ptr(), twiddle.data_ptr(), g,
-                              0, 1.0, geom[3], samples, samples, audio.data_ptr(), st), 'ptmi_istft_forward')
+        _lib.call('ptmi_istft_forward', P.data_ptr(), rows, frames, None, syn.data_ptr(), twiddle.data_ptr(), g, 0, 1.0, geom[3], samples,
+                  samples, audio.data_ptr(), st, timer='gl_istft')
         if fused:
-            _lib.check(_lib.timed('gl_stft_update', lib.ptmi_gl_stft_update, audio.data_ptr(), rows, samples, samples, window.data_ptr(),
-                                  twiddle.data_ptr(), g, frames, alpha, x.data_ptr(), a.data_ptr(), P.data_ptr(), partials.data_ptr(),
-                                  state.data_ptr(), st), 'ptmi_gl_stft_update')
+            _lib.call('ptmi_gl_stft_update', audio.data_ptr(), rows, samples, samples, window.data_ptr(), twiddle.data_ptr(), g, frames,
+                      alpha, x.data_ptr(), a.data_ptr(), P.data_ptr(), partials.data_ptr(), state.data_ptr(), st, timer='gl_stft_update')
         else:
-            _lib.check(_lib.timed('gl_stft', lib.ptmi_stft_forward, audio.data_ptr(), rows, samples, samples, None, window.data_ptr(),
-                                  twiddle.data_ptr(), g, frames, 0, 1.0, xnew.data_ptr(), st), 'ptmi_stft_forward')
-            _lib.check(_lib.timed('gl_update', lib.ptmi_gl_update, xnew.data_ptr(), x.data_ptr(), a.data_ptr(), n, alpha, P.data_ptr(),
-                                  partials.data_ptr(), state.data_ptr(), st), 'ptmi_gl_update')
-        _lib.check(_lib.timed('gl_finish', lib.ptmi_gl_finish, partials.data_ptr(), n, atol, it, rmse.data_ptr(), state.data_ptr(), st),
-                   'ptmi_gl_finish')
+            _lib.call('ptmi_stft_forward', audio.data_ptr(), rows, samples, samples, None, window.data_ptr(), twiddle.data_ptr(), g, frames,
+                      0, 1.0, xnew.data_ptr(), st, timer='gl_stft')
+            _lib.call('ptmi_gl_update', xnew.data_ptr(), x.data_ptr(), a.data_ptr(), n, alpha, P.data_ptr(), partials.data_ptr(),
+                      state.data_ptr(), st, timer='gl_update')
+        _lib.call('ptmi_gl_finish', partials.data_ptr(), n, atol, it, rmse.data_ptr(), state.data_ptr(), st, timer='gl_finish')
         if poll > 0 and (it + 1) % poll == 0 and it + 1 < iterations and int(state[0].item()) != 0:
             break
 
@@ -1394,9 +1343,9 @@ def anti_alias_forward(x, up_filter, down_filter, alpha, beta, up_ratio, down_ra
     assert M >= 0, (T, up_ratio, k, down_ratio, dk, padding)
     y = torch.empty((B, C, M), dtype=torch.float32, device=x.device)
     if y.numel():
-        _lib.check(_lib.timed('anti_alias_forward', lib.ptmi_anti_alias_forward, x.data_ptr(), _lib.ptr(up_filter), _lib.ptr(down_filter),
-                              _lib.ptr(alpha), _lib.ptr(beta), B, C, T, up_ratio, k, down_ratio, dk, int(padding), int(alpha is not None),
-                              int(logscale), y.data_ptr(), _lib.stream(x.device)), 'ptmi_anti_alias_forward')
+        _lib.call('ptmi_anti_alias_forward', x.data_ptr(), _lib.ptr(up_filter), _lib.ptr(down_filter), _lib.ptr(alpha), _lib.ptr(beta), B,
+                  C, T, up_ratio, k, down_ratio, dk, int(padding), int(alpha is not None), int(logscale), y.data_ptr(),
+                  _lib.stream(x.device), timer='anti_alias_forward')
     return y
 
 
@@ -1419,8 +1368,8 @@ def anti_alias_backward(dy, x, up_filter, down_filter, alpha, beta, up_ratio, do
     if param_grads:
         ws = torch.empty(lib.ptmi_anti_alias_workspace_elems(B, C, T, up_ratio, k, down_ratio, dk, int(padding)), dtype=torch.float64,
                          device=x.device)
-    _lib.check(_lib.timed('anti_alias_backward', lib.ptmi_anti_alias_backward, dy.data_ptr(), x.data_ptr(), _lib.ptr(up_filter),
-                          _lib.ptr(down_filter), _lib.ptr(alpha), _lib.ptr(beta), B, C, T, up_ratio, k, down_ratio, dk, int(padding),
-                          int(alpha is not None), int(logscale), dx.data_ptr(), dalpha.data_ptr() if param_grads >= 1 else None,
-                          dbeta.data_ptr() if param_grads == 2 else None, _lib.ptr(ws), _lib.stream(x.device)), 'ptmi_anti_alias_backward')
+    _lib.call('ptmi_anti_alias_backward', dy.data_ptr(), x.data_ptr(), _lib.ptr(up_filter), _lib.ptr(down_filter), _lib.ptr(alpha),
+              _lib.ptr(beta), B, C, T, up_ratio, k, down_ratio, dk, int(padding), int(alpha is not None), int(logscale), dx.data_ptr(),
+              dalpha.data_ptr() if param_grads >= 1 else None, dbeta.data_ptr() if param_grads == 2 else None, _lib.ptr(ws),
+              _lib.stream(x.device), timer='anti_alias_backward')
     return dx, dalpha, dbeta

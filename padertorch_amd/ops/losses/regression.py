@@ -46,17 +46,15 @@ class _TdStatsFn(torch.autograd.Function):
         dev = est.device
         stats = torch.empty((B, int(lib.ptmi_td_stats_elems(K))), dtype=torch.float64, device=dev)
         ws = torch.empty(int(lib.ptmi_td_workspace_elems(B, K, T)), dtype=torch.float64, device=dev)
-        strides = _lib.strides4(est.stride(0), est.stride(1), tgt.stride(0), tgt.stride(1))
-        _lib.check(_lib.timed(
-            'td_pair_stats', lib.ptmi_td_pair_stats, est.data_ptr(), tgt.data_ptr(), _lib.ptr(lengths), B, K, T,
-            strides, ws.data_ptr(), stats.data_ptr(), _lib.stream(dev)), 'ptmi_td_pair_stats')
+        strides = _lib.int64s(est.stride(0), est.stride(1), tgt.stride(0), tgt.stride(1))
+        _lib.call('ptmi_td_pair_stats', est.data_ptr(), tgt.data_ptr(), _lib.ptr(lengths), B, K, T, strides, ws.data_ptr(),
+                  stats.data_ptr(), _lib.stream(dev), timer='td_pair_stats')
         ctx.save_for_backward(est, tgt, lengths)
         return stats
 
     @staticmethod
     def backward(ctx, g):
         est, tgt, lengths = ctx.saved_tensors
-        lib = _lib.load()
         B, K, T = est.shape
         g = g.to(torch.float32)
         g_set = g[:, :K * K].reshape(B, K, K)
@@ -69,11 +67,10 @@ class _TdStatsFn(torch.autograd.Function):
             if not ctx.needs_input_grad[idx]:
                 continue
             out = torch.empty((B, K, T), dtype=torch.float32, device=est.device)
-            strides = _lib.strides6(x.stride(0), x.stride(1), y.stride(0), y.stride(1), out.stride(0), out.stride(1))
+            strides = _lib.int64s(x.stride(0), x.stride(1), y.stride(0), y.stride(1), out.stride(0), out.stride(1))
             a, bmat, c = a.contiguous(), bmat.contiguous(), c.contiguous()
-            _lib.check(_lib.timed(
-                'td_lincomb', lib.ptmi_td_lincomb, x.data_ptr(), y.data_ptr(), _lib.ptr(lengths), a.data_ptr(),
-                bmat.data_ptr(), c.data_ptr(), B, K, T, strides, out.data_ptr(), st), 'ptmi_td_lincomb')
+            _lib.call('ptmi_td_lincomb', x.data_ptr(), y.data_ptr(), _lib.ptr(lengths), a.data_ptr(), bmat.data_ptr(), c.data_ptr(), B, K,
+                      T, strides, out.data_ptr(), st, timer='td_lincomb')
             grads[idx] = out
         return grads[0], grads[1], None
 

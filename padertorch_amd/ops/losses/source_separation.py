@@ -304,10 +304,9 @@ def compute_pairwise_losses(
         ws = torch.empty(int(lib.ptmi_pit_workspace_elems(1, outer, sources, inner)),
                          dtype=torch.float64, device=est.device)
         sse = torch.empty((1, 1, sources, sources), dtype=torch.float64, device=est.device)
-        _lib.check(lib.ptmi_pit_pairwise_sse(
-            est.data_ptr(), None, tgt.data_ptr(), None, 1, outer, _lib.strides6(
-                0, sources * inner, 0, 0, 0, sources * inner), sources, inner, None,
-            ws.data_ptr(), sse.data_ptr(), _lib.stream(est.device)), 'ptmi_pit_pairwise_sse')
+        _lib.call('ptmi_pit_pairwise_sse', est.data_ptr(), None, tgt.data_ptr(), None, 1, outer,
+                  _lib.int64s(0, sources * inner, 0, 0, 0, sources * inner), sources, inner, None, ws.data_ptr(), sse.data_ptr(),
+                  _lib.stream(est.device))
         return (sse[0, 0] / (outer * inner)).to(torch.float32)
     # any other loss_fn: K * K evaluations on slices, row i = estimate i, column j = target j
     est_i = estimate.unbind(axis)

@@ -20,7 +20,7 @@ def _error_sink(device):
     if ent is None:
         with torch.cuda.device(key[1]):
             word = torch.zeros(1, dtype=torch.int32, device=device)
-            _lib.check(_lib.load().ptmi_lstm_set_error_sink(word.data_ptr()), 'ptmi_lstm_set_error_sink')
+            _lib.call('ptmi_lstm_set_error_sink', word.data_ptr())
         ent = _ERR_SINK[key] = [word, 0]
     return ent
 

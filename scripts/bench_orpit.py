@@ -141,7 +141,7 @@ def main():
     e2, t2 = torch.randn(B, 2, 5 * T // 4, device=dev), torch.randn(B, 2, 5 * T // 4, device=dev)
     stats = torch.empty((B, int(lib.ptmi_td_stats_elems(2))), dtype=torch.float64, device=dev)
     ws = torch.empty(int(lib.ptmi_td_workspace_elems(B, 2, e2.shape[2])), dtype=torch.float64, device=dev)
-    strides = _lib.strides4(e2.stride(0), e2.stride(1), t2.stride(0), t2.stride(1))
+    strides = _lib.int64s(e2.stride(0), e2.stride(1), t2.stride(0), t2.stride(1))
 
     def rect():
         torch.ops.ptmi.td_rect_stats(est, tgt, True)
