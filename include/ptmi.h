@@ -905,6 +905,57 @@ int ptmi_anti_alias_backward(const float* dy, const float* x, const float* up_fi
                              int32_t down_taps, int32_t padding, int32_t act, int32_t logscale, float* dx, float* dalpha, float* dbeta,
                              double* workspace, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * WaveNet vocoder (csrc/wavenet.hip): padertorch/ops/mu_law.py, padertorch/modules/wavenet/wavenet.py and the sampling loop of
+ * nv-wavenet behind WaveNet.infer.  fp32, activations [B, T, C] with channels innermost; the 1x1 convolutions are ptmi_gemm_planes calls.
+ *
+ * ptmi_mu_law_encode / _decode : the companding per element in fp64; codes (int64) clamped to [0, Q - 1].  codes_are_float: the decode
+ *                                reads float codes.
+ * ptmi_wavenet_embed_forward   : codes[i] = mu_law(audio[i]) with Q = A and x0[i, :] = embed[codes[i], :], n = B T rows, one launch
+ * ptmi_wavenet_embed_backward  : dembed [A, R] = sum of the rows of dx0 per code, fp64, one fixed order, no atomics
+ *                                (workspace: ptmi_wavenet_embed_workspace_elems doubles)
+ * ptmi_wavenet_colsum          : out[j] = sum_r x[r ld + j], j < width, fp64, one fixed order (workspace: ..._colsum_workspace_elems)
+ * ptmi_wavenet_ola_forward     : the overlap-add of ConvTranspose1d(C, C, window, stride) behind its GEMM G [B Tf, C window] (column
+ *                                co window + k): out[b, t', co] = bias[co] + sum_f G[b, f, co, t' + front - f stride], t' < Tout
+ *                                (front: what the fading crops in front; front + Tout <= (Tf - 1) stride + window)
+ * ptmi_wavenet_ola_backward    : dG[b, f, co, k] = dout[b, f stride + k - front, co] (0 outside [0, Tout))
+ * ptmi_wavenet_gate_forward    : P [B T, 4R] = x W^T (rows 0 .. 2R - 1 of W: the tap on x[t - d]); z[b,t,j] = P[b,t-d,j] (0 for t < d)
+ *                                + P[b,t,2R+j] + bias[j] + cond[(b T + t) ldc + j]; acts[(b T + t) lda + r] = tanh(z[r]) sigmoid(z[R+r])
+ * ptmi_wavenet_gate_backward   : z recomputed; dz [.., 2R] with row stride ldd; dP [B T, 4R] (NULL: skipped): dP[b,t,j] = dz[b,t+d,j],
+ *                                dP[b,t,2R+j] = dz[b,t,j]; dbias [2R] (NULL: skipped) the column sum of dz (workspace as _colsum, 2R wide)
+ * ptmi_wavenet_generate        : nsteps time steps from t0 for nseq sequences, ptmi_wavenet_generate_ex() of them per workgroup, which
+ *                                synchronise with the workgroup barrier alone.  packed: per layer Wg [2R][2R] (k: x[t-d] | x[t]), bg [2R],
+ *                                Wrs [R][S + R] (skip | residual), brs [S + R]; then Wo [S][A], We [A][A].  cond [., Tc, L 2R], u [., Tc];
+ *                                layer_meta [L][2] = (dilation, first ring row), seq_meta [nseq][3] = (row of cond / u, onset, length).
+ *                                ring [groups][ring_rows][ex][R] (zero before t0 = 0) and last_code [groups ex] persist between launches;
+ *                                y [nseq, Tmax] int64, logits [nseq, Tmax, A] or NULL.  R <= 256, S <= 1024, A <= 1024.
+ * The launches neither allocate nor synchronise.
+ * ---------------------------------------------------------------------------------------------------------- */
+int ptmi_mu_law_encode(const float* x, int64_t n, int32_t mu_quantization, int64_t* codes, ptmi_stream_t stream);
+int ptmi_mu_law_decode(const void* codes, int32_t codes_are_float, int64_t n, int32_t mu_quantization, float* out, ptmi_stream_t stream);
+int ptmi_wavenet_embed_forward(const float* audio, const float* embed, int64_t n, int32_t A, int32_t R, int64_t* codes, float* x0,
+                               ptmi_stream_t stream);
+int64_t ptmi_wavenet_embed_workspace_elems(int64_t n, int32_t A, int32_t R);
+int ptmi_wavenet_embed_backward(const float* dx0, const int64_t* codes, int64_t n, int32_t A, int32_t R, float* dembed, double* workspace,
+                                ptmi_stream_t stream);
+int64_t ptmi_wavenet_colsum_workspace_elems(int64_t rows, int32_t width);
+int ptmi_wavenet_colsum(const float* x, int64_t rows, int32_t width, int64_t ld, float* out, double* workspace, ptmi_stream_t stream);
+int ptmi_wavenet_ola_forward(const float* G, const float* bias, int64_t B, int32_t C, int64_t Tf, int32_t window, int32_t stride,
+                             int64_t front, int64_t Tout, float* out, ptmi_stream_t stream);
+int ptmi_wavenet_ola_backward(const float* dout, int64_t B, int32_t C, int64_t Tf, int32_t window, int32_t stride, int64_t front,
+                              int64_t Tout, float* dG, ptmi_stream_t stream);
+int ptmi_wavenet_gate_forward(const float* P, const float* bias, const float* cond, int64_t ldc, int64_t B, int64_t T, int32_t R,
+                              int32_t dilation, float* acts, int64_t lda, ptmi_stream_t stream);
+int ptmi_wavenet_gate_backward(const float* dacts, int64_t lda, const float* P, const float* bias, const float* cond, int64_t ldc, int64_t B,
+                               int64_t T, int32_t R, int32_t dilation, float* dz, int64_t ldd, float* dP, float* dbias, double* workspace,
+                               ptmi_stream_t stream);
+int32_t ptmi_wavenet_generate_ex(void);
+int32_t ptmi_wavenet_generate_ring_in_lds(int32_t R, int32_t S, int32_t A, int64_t ring_rows);
+int ptmi_wavenet_generate(const float* packed, const float* embed, const float* cond, const float* u, const int32_t* layer_meta,
+                          const int32_t* seq_meta, int32_t nseq, int64_t Tc, int32_t L, int32_t R, int32_t S, int32_t A, int32_t ring_rows,
+                          int64_t t0, int32_t nsteps, int64_t Tmax, float* ring, int32_t* last_code, int64_t* y, float* logits,
+                          ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -6,3 +6,5 @@ from . import convnet  # noqa: F401
 from .convnet import ConvNet  # noqa: F401
 from . import dual_path_rnn  # noqa: F401
 from .dual_path_rnn import DPRNN, DPRNNBlock, _ChunkRNN, segment, overlap_add  # noqa: F401
+from . import wavenet  # noqa: F401
+from .wavenet import WaveNet  # noqa: F401

@@ -32,3 +32,6 @@ from . import griffin_lim  # noqa: F401
 from .griffin_lim import gl_project, gl_update, gl_iterations  # noqa: F401
 from . import anti_alias  # noqa: F401
 from .anti_alias import anti_alias_activation, kaiser_sinc_filter1d  # noqa: F401
+from . import mu_law  # noqa: F401
+from .mu_law import mu_law_encode, mu_law_decode  # noqa: F401
+from . import wavenet  # noqa: F401

@@ -37,6 +37,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.gl_project / gl_project_backward / gl_update / gl_iterations   ptmi_gl_*   (contrib/mk/synthesis/parametric/griffin_lim.py:32-156)
     torch.ops.ptmi.anti_alias_forward / _backward  ptmi_anti_alias_*         (contrib/mk/synthesis/vocoder/nvidia_bigvgan/alias_free_activation/torch,
                                                                               nvidia_bigvgan/activations.py)
+    torch.ops.ptmi.mu_law_encode / _decode, wavenet_embed_forward / _backward, wavenet_ola_forward / _backward, wavenet_gate_forward_ /
+    _backward_, wavenet_colsum, wavenet_generate_   ptmi_mu_law_*, ptmi_wavenet_*   (ops/mu_law.py, modules/wavenet/wavenet.py, nv_wavenet)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1373,3 +1375,157 @@ def anti_alias_backward(dy, x, up_filter, down_filter, alpha, beta, up_ratio, do
               dalpha.data_ptr() if param_grads >= 1 else None, dbeta.data_ptr() if param_grads == 2 else None, _lib.ptr(ws),
               _lib.stream(x.device), timer='anti_alias_backward')
     return dx, dalpha, dbeta
+
+
+# ------------------------------------------------------------------------------------------------ WaveNet vocoder
+def _f32c(*tensors):
+    for t in tensors:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), (t.shape, t.dtype, t.stride())
+
+
+@_register('mu_law_encode(Tensor x, int mu_quantization) -> Tensor')
+def mu_law_encode(x, mu_quantization):
+    """``x`` (fp32, any shape) -> int64 codes in ``[0, mu_quantization - 1]`` (``ptmi_mu_law_encode``; ops/mu_law.py:22-29)."""
+    _f32c(x)
+    codes = torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    if x.numel():
+        _lib.call('ptmi_mu_law_encode', x.data_ptr(), x.numel(), mu_quantization, codes.data_ptr(), _lib.stream(x.device), timer='mu_law_encode')
+    return codes
+
+
+@_register('mu_law_decode(Tensor codes, int mu_quantization) -> Tensor')
+def mu_law_decode(codes, mu_quantization):
+    """int64 or fp32 codes -> fp32 signal in ``[-1, 1]`` (``ptmi_mu_law_decode``; ops/mu_law.py:10-19)."""
+    assert codes.dtype in (torch.int64, torch.float32) and codes.is_contiguous(), (codes.dtype, codes.stride())
+    out = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
+    if codes.numel():
+        _lib.call('ptmi_mu_law_decode', codes.data_ptr(), int(codes.dtype == torch.float32), codes.numel(), mu_quantization, out.data_ptr(),
+                  _lib.stream(codes.device), timer='mu_law_decode')
+    return out
+
+
+@_register('wavenet_embed_forward(Tensor audio, Tensor embed) -> (Tensor, Tensor)')
+def wavenet_embed_forward(audio, embed):
+    """``audio [B, T]``, ``embed [A, R]`` -> ``(codes [B, T] int64, x0 [B, T, R])``, one launch (``ptmi_wavenet_embed_forward``)."""
+    _f32c(audio, embed)
+    assert audio.dim() == 2 and embed.dim() == 2 and audio.numel() > 0
+    A, R = embed.shape
+    codes = torch.empty(audio.shape, dtype=torch.int64, device=audio.device)
+    x0 = torch.empty((*audio.shape, R), dtype=torch.float32, device=audio.device)
+    _lib.call('ptmi_wavenet_embed_forward', audio.data_ptr(), embed.data_ptr(), audio.numel(), A, R, codes.data_ptr(), x0.data_ptr(),
+              _lib.stream(audio.device), timer='wavenet_embed_forward')
+    return codes, x0
+
+
+@_register('wavenet_embed_backward(Tensor dx0, Tensor codes, int A) -> Tensor')
+def wavenet_embed_backward(dx0, codes, A):
+    """``dembed [A, R]``: the rows of ``dx0 [B, T, R]`` summed per code in one fixed order (``ptmi_wavenet_embed_backward``)."""
+    _f32c(dx0)
+    assert codes.dtype == torch.int64 and codes.is_contiguous() and dx0.shape[:-1] == codes.shape
+    n, R = codes.numel(), dx0.shape[-1]
+    lib = _lib.load()
+    ws = torch.empty(lib.ptmi_wavenet_embed_workspace_elems(n, A, R), dtype=torch.float64, device=dx0.device)
+    out = torch.empty((A, R), dtype=torch.float32, device=dx0.device)
+    _lib.call('ptmi_wavenet_embed_backward', dx0.data_ptr(), codes.data_ptr(), n, A, R, out.data_ptr(), ws.data_ptr(), _lib.stream(dx0.device),
+              timer='wavenet_embed_backward')
+    return out
+
+
+@_register('wavenet_colsum(Tensor x) -> Tensor')
+def wavenet_colsum(x):
+    """``x [rows, width]`` (unit inner stride, any row stride) -> ``[width]``: column sums in fp64, one fixed order (``ptmi_wavenet_colsum``)."""
+    assert x.dim() == 2 and x.dtype == torch.float32 and (x.stride(1) == 1 or x.shape[1] == 1) and x.numel() > 0, (x.shape, x.stride())
+    rows, width = x.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.ptmi_wavenet_colsum_workspace_elems(rows, width), dtype=torch.float64, device=x.device)
+    out = torch.empty(width, dtype=torch.float32, device=x.device)
+    _lib.call('ptmi_wavenet_colsum', x.data_ptr(), rows, width, max(x.stride(0), width), out.data_ptr(), ws.data_ptr(), _lib.stream(x.device),
+              timer='wavenet_colsum')
+    return out
+
+
+@_register('wavenet_ola_forward(Tensor G, Tensor bias, int B, int Tf, int window, int stride, int front, int Tout) -> Tensor')
+def wavenet_ola_forward(G, bias, B, Tf, window, stride, front, Tout):
+    """``G [B Tf, C window]`` -> ``[B, Tout, C]``: overlap-add, bias and crop (``ptmi_wavenet_ola_forward``; wavenet.py:186-195)."""
+    _f32c(G, bias)
+    C = bias.numel()
+    assert tuple(G.shape) == (B * Tf, C * window), (G.shape, B, Tf, C, window)
+    out = torch.empty((B, Tout, C), dtype=torch.float32, device=G.device)
+    _lib.call('ptmi_wavenet_ola_forward', G.data_ptr(), bias.data_ptr(), B, C, Tf, window, stride, front, Tout, out.data_ptr(),
+              _lib.stream(G.device), timer='wavenet_ola_forward')
+    return out
+
+
+@_register('wavenet_ola_backward(Tensor dout, int Tf, int window, int stride, int front) -> Tensor')
+def wavenet_ola_backward(dout, Tf, window, stride, front):
+    """The adjoint of :func:`wavenet_ola_forward` in ``G``: the framing gather ``dG [B Tf, C window]`` (``ptmi_wavenet_ola_backward``)."""
+    _f32c(dout)
+    B, Tout, C = dout.shape
+    dG = torch.empty((B * Tf, C * window), dtype=torch.float32, device=dout.device)
+    _lib.call('ptmi_wavenet_ola_backward', dout.data_ptr(), B, C, Tf, window, stride, front, Tout, dG.data_ptr(), _lib.stream(dout.device),
+              timer='wavenet_ola_backward')
+    return dG
+
+
+def _rows3(t, width, what):
+    """``t [B, T, >= width]`` as (pointer, row stride): unit inner stride, rows ``b T + t`` evenly spaced."""
+    assert t.dim() == 3 and t.dtype == torch.float32 and t.shape[2] == width and (t.stride(2) == 1 or width == 1), (what, t.shape, t.stride())
+    assert t.shape[0] == 1 or t.stride(0) == t.shape[1] * t.stride(1), (what, t.shape, t.stride())
+    return t.data_ptr(), t.stride(1)
+
+
+@_register('wavenet_gate_forward_(Tensor(a!) acts, Tensor P, Tensor bias, Tensor cond, int dilation) -> ()')
+def wavenet_gate_forward_(acts, P, bias, cond, dilation):
+    """``acts [B, T, R]`` (a slice of ``acts_all`` or a tensor of its own) ``= tanh(z[:R]) sigmoid(z[R:])``, ``z`` from ``P [B, T, 4R]``,
+    ``bias [2R]`` and ``cond [B, T, 2R]`` (a slice of the conditioning GEMM's output) (``ptmi_wavenet_gate_forward``; wavenet.py:152-156)."""
+    _f32c(P, bias)
+    B, T, R = acts.shape
+    assert tuple(P.shape) == (B, T, 4 * R) and bias.numel() == 2 * R, (P.shape, bias.shape, acts.shape)
+    ap, lda = _rows3(acts, R, 'acts')
+    cp, ldc = _rows3(cond, 2 * R, 'cond')
+    assert cond.shape[:2] == acts.shape[:2]
+    _lib.call('ptmi_wavenet_gate_forward', P.data_ptr(), bias.data_ptr(), cp, ldc, B, T, R, dilation, ap, lda, _lib.stream(P.device),
+              timer='wavenet_gate_forward')
+
+
+@_register('wavenet_gate_backward_(Tensor(a!) dz, Tensor dacts, Tensor P, Tensor bias, Tensor cond, int dilation, bool want_dP, '
+           'bool want_dbias) -> (Tensor, Tensor)')
+def wavenet_gate_backward_(dz, dacts, P, bias, cond, dilation, want_dP, want_dbias):
+    """``dz [B, T, 2R]`` (a slice of ``dcond``) is written; returns ``(dP [B, T, 4R], dbias [2R])`` (empty when not wanted)
+    (``ptmi_wavenet_gate_backward``)."""
+    _f32c(P, bias)
+    B, T, R = dacts.shape
+    assert tuple(P.shape) == (B, T, 4 * R) and bias.numel() == 2 * R
+    gp, lda = _rows3(dacts, R, 'dacts')
+    cp, ldc = _rows3(cond, 2 * R, 'cond')
+    zp, ldd = _rows3(dz, 2 * R, 'dz')
+    dev = P.device
+    dP = torch.empty((B, T, 4 * R) if want_dP else (0,), dtype=torch.float32, device=dev)
+    dbias = torch.empty(2 * R if want_dbias else 0, dtype=torch.float32, device=dev)
+    ws = None
+    if want_dbias:
+        ws = torch.empty(_lib.load().ptmi_wavenet_colsum_workspace_elems(B * T, 2 * R), dtype=torch.float64, device=dev)
+    _lib.call('ptmi_wavenet_gate_backward', gp, lda, P.data_ptr(), bias.data_ptr(), cp, ldc, B, T, R, dilation, zp, ldd,
+              dP.data_ptr() if want_dP else None, dbias.data_ptr() if want_dbias else None, _lib.ptr(ws), _lib.stream(dev),
+              timer='wavenet_gate_backward')
+    return dP, dbias
+
+
+@_register('wavenet_generate_(Tensor(a!) y, Tensor(b!)? logits, Tensor(c!) ring, Tensor(d!) last_code, Tensor packed, Tensor embed, '
+           'Tensor cond, Tensor u, Tensor layer_meta, Tensor seq_meta, int S, int A, int ring_rows, int t0, int nsteps) -> ()')
+def wavenet_generate_(y, logits, ring, last_code, packed, embed, cond, u, layer_meta, seq_meta, S, A, ring_rows, t0, nsteps):
+    """``nsteps`` time steps of the sampling loop from ``t0`` in ONE launch (``ptmi_wavenet_generate``; include/ptmi.h has the layouts)."""
+    _f32c(packed, embed, cond, u, ring, logits)
+    nseq, Tmax = y.shape
+    R, L = embed.shape[1], layer_meta.shape[0]
+    ex = _lib.load().ptmi_wavenet_generate_ex()
+    groups = -(-nseq // ex)
+    assert y.dtype == torch.int64 and y.is_contiguous() and layer_meta.dtype == seq_meta.dtype == last_code.dtype == torch.int32
+    assert cond.dim() == 3 and cond.shape[2] == 2 * R * L and u.shape == cond.shape[:2], (cond.shape, u.shape)
+    assert tuple(seq_meta.shape) == (nseq, 3) and tuple(layer_meta.shape) == (L, 2) and seq_meta.is_contiguous() and layer_meta.is_contiguous()
+    assert ring.numel() == groups * ring_rows * ex * R and last_code.numel() == groups * ex and embed.shape[0] >= A
+    assert packed.numel() == L * (4 * R * R + 2 * R + R * (S + R) + S + R) + S * A + A * A, packed.shape
+    assert logits is None or tuple(logits.shape) == (nseq, Tmax, A)
+    _lib.call('ptmi_wavenet_generate', packed.data_ptr(), embed.data_ptr(), cond.data_ptr(), u.data_ptr(), layer_meta.data_ptr(),
+              seq_meta.data_ptr(), nseq, cond.shape[1], L, R, S, A, ring_rows, t0, nsteps, Tmax, ring.data_ptr(), last_code.data_ptr(),
+              y.data_ptr(), _lib.ptr(logits), _lib.stream(y.device), timer='wavenet_generate')
