@@ -956,6 +956,40 @@ int ptmi_wavenet_generate(const float* packed, const float* embed, const float* 
                           int64_t t0, int32_t nsteps, int64_t Tmax, float* ring, int32_t* last_code, int64_t* y, float* logits,
                           ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The BigVGAN generator's convolutions, inference only (csrc/bigvgan.hip): conv_pre, the up-sampling ConvTranspose1d, the dilated Conv1d
+ * of AMPBlock1 / AMPBlock2 and conv_post of padertorch/contrib/mk/synthesis/vocoder/nvidia_bigvgan/bigvgan.py.  fp32, activations
+ * [B, C, T] contiguous (the layout of ptmi_anti_alias_forward), zero padding, every sum in one fixed order, no atomics, no host reads.
+ *
+ * A dilated Conv1d(C_in, C_out, K odd, dilation d, padding (K - 1) d / 2), weight [C_out, C_in, K], has two forms with one epilogue,
+ *   v = scale (conv + bias + residual);  out = v,  or  out += v  when accumulate     (bias [C_out], residual [B, C_out, T]: NULL = absent)
+ * ptmi_bigvgan_taps        : the GEMM path behind P [B, K C_out, T] = Wtaps x_b per batch entry (row k C_out + co = tap k of channel co, a
+ *                            ptmi_gemm_planes call): conv[b,co,t] = sum_k P[b, k C_out + co, t + (k - (K-1)/2) d], zero outside [0, T).  K <= 63.
+ * ptmi_bigvgan_conv_direct : the same convolution from x [B, C_in, T] in plain fp32 FMAs (ci ascending, then k), no P; for the layers
+ *                            ptmi_bigvgan_direct_ok admits: C_in <= ptmi_bigvgan_direct_max_channels(), K <= 11, (K - 1) d / 2 <= 64.
+ * ptmi_bigvgan_tile        : samples of a row per workgroup, of the taps kernel (0) / the direct kernel (1): what the tests put T around
+ * ptmi_bigvgan_ola         : ConvTranspose1d(C_in, C_out, k, u, padding p = (k - u) / 2) behind G [B, C_out k, T] = W^T x_b (row co k + kk):
+ *                            out[b,co,t'] = bias[co] + sum_f G[b, co k + kk, f] over f u + kk - p = t' (f ascending, gather form),
+ *                            t' < ptmi_bigvgan_ola_out_len = (T - 1) u - 2 p + k.  1 <= u <= 8, k >= u, either parity of k - u.
+ * ptmi_bigvgan_post        : conv_post, C -> 1 channel: out[b,t] = act(bias[0] + sum_c sum_k w[c,k] x[b,c,t + k - (K-1)/2]), act = tanhf or the
+ *                            clamp to [-1, 1] (NaN stays NaN under both).  K odd, K <= 11.
+ * Geometry outside these limits (even K, u > 8, ...) is PTMI_E_INVALID and nothing is launched.  The launches neither allocate nor
+ * synchronise.
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_bigvgan_direct_max_channels(void);
+int32_t ptmi_bigvgan_direct_ok(int32_t C_in, int32_t K, int32_t dilation);
+int32_t ptmi_bigvgan_tile(int32_t direct);
+int64_t ptmi_bigvgan_ola_out_len(int64_t T, int32_t k, int32_t u);
+int ptmi_bigvgan_taps(const float* P, const float* bias, const float* residual, int64_t B, int32_t C_out, int64_t T, int32_t K,
+                      int32_t dilation, float scale, int32_t accumulate, float* out, ptmi_stream_t stream);
+int ptmi_bigvgan_conv_direct(const float* x, const float* weight, const float* bias, const float* residual, int64_t B, int32_t C_in,
+                             int32_t C_out, int64_t T, int32_t K, int32_t dilation, float scale, int32_t accumulate, float* out,
+                             ptmi_stream_t stream);
+int ptmi_bigvgan_ola(const float* G, const float* bias, int64_t B, int32_t C_out, int64_t T, int32_t k, int32_t u, float* out,
+                     ptmi_stream_t stream);
+int ptmi_bigvgan_post(const float* x, const float* weight, const float* bias, int64_t B, int32_t C, int64_t T, int32_t K, int32_t use_tanh,
+                      float* out, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -35,3 +35,4 @@ from .anti_alias import anti_alias_activation, kaiser_sinc_filter1d  # noqa: F40
 from . import mu_law  # noqa: F401
 from .mu_law import mu_law_encode, mu_law_decode  # noqa: F401
 from . import wavenet  # noqa: F401
+from . import bigvgan  # noqa: F401

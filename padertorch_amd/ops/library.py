@@ -39,6 +39,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                                               nvidia_bigvgan/activations.py)
     torch.ops.ptmi.mu_law_encode / _decode, wavenet_embed_forward / _backward, wavenet_ola_forward / _backward, wavenet_gate_forward_ /
     _backward_, wavenet_colsum, wavenet_generate_   ptmi_mu_law_*, ptmi_wavenet_*   (ops/mu_law.py, modules/wavenet/wavenet.py, nv_wavenet)
+    torch.ops.ptmi.bigvgan_taps_ / bigvgan_conv_direct_ / bigvgan_ola / bigvgan_post   ptmi_bigvgan_*   (contrib/mk/synthesis/vocoder/
+                                                                              nvidia_bigvgan/bigvgan.py: the generator's convolutions)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1529,3 +1531,67 @@ def wavenet_generate_(y, logits, ring, last_code, packed, embed, cond, u, layer_
     _lib.call('ptmi_wavenet_generate', packed.data_ptr(), embed.data_ptr(), cond.data_ptr(), u.data_ptr(), layer_meta.data_ptr(),
               seq_meta.data_ptr(), nseq, cond.shape[1], L, R, S, A, ring_rows, t0, nsteps, Tmax, ring.data_ptr(), last_code.data_ptr(),
               y.data_ptr(), _lib.ptr(logits), _lib.stream(y.device), timer='wavenet_generate')
+
+
+# ------------------------------------------------------------------------------------------------ BigVGAN generator (inference)
+def _bv_epilogue(out, bias, residual):
+    _f32c(out, bias, residual)
+    assert out.dim() == 3 and (bias is None or tuple(bias.shape) == (out.shape[1],)), (out.shape, None if bias is None else bias.shape)
+    assert residual is None or residual.shape == out.shape, (residual.shape, out.shape)
+
+
+@_register('bigvgan_taps_(Tensor(a!) out, Tensor P, Tensor? bias, Tensor? residual, int K, int dilation, float scale, bool accumulate) -> ()')
+def bigvgan_taps_(out, P, bias, residual, K, dilation, scale, accumulate):
+    """``out [B, C_out, T] (+)= scale (sum_k P[:, k C_out + co, t + (k - (K-1)/2) d] + bias + residual)`` behind the GEMM that made
+    ``P [B, K C_out, T]`` (``ptmi_bigvgan_taps``; the dilated Conv1d of bigvgan.py:56-88,175-189, conv_pre :286-288)."""
+    _f32c(P)
+    _bv_epilogue(out, bias, residual)
+    B, C_out, T = out.shape
+    assert tuple(P.shape) == (B, K * C_out, T), (P.shape, out.shape, K)
+    _lib.call('ptmi_bigvgan_taps', P.data_ptr(), _lib.ptr(bias), _lib.ptr(residual), B, C_out, T, K, dilation, scale, int(accumulate),
+              out.data_ptr(), _lib.stream(out.device), timer='bigvgan_taps')
+
+
+@_register('bigvgan_conv_direct_(Tensor(a!) out, Tensor x, Tensor weight, Tensor? bias, Tensor? residual, int dilation, float scale, '
+           'bool accumulate) -> ()')
+def bigvgan_conv_direct_(out, x, weight, bias, residual, dilation, scale, accumulate):
+    """The same convolution and epilogue from ``x [B, C_in, T]`` and ``weight [C_out, C_in, K]`` in fp32 FMAs, no ``P``
+    (``ptmi_bigvgan_conv_direct``: narrow layers)."""
+    _f32c(x, weight)
+    _bv_epilogue(out, bias, residual)
+    B, C_out, T = out.shape
+    C_in, K = weight.shape[1:]
+    assert tuple(x.shape) == (B, C_in, T) and weight.shape[0] == C_out, (x.shape, weight.shape, out.shape)
+    _lib.call('ptmi_bigvgan_conv_direct', x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(residual), B, C_in, C_out, T, K, dilation,
+              scale, int(accumulate), out.data_ptr(), _lib.stream(out.device), timer='bigvgan_conv_direct')
+
+
+@_register('bigvgan_ola(Tensor G, Tensor? bias, int kernel_size, int stride) -> Tensor')
+def bigvgan_ola(G, bias, kernel_size, stride):
+    """``G [B, C_out k, T]`` -> ``[B, C_out, (T - 1) u - 2 ((k - u) // 2) + k]``: the overlap-add, bias and crop of the up-sampling
+    ConvTranspose1d (``ptmi_bigvgan_ola``; bigvgan.py:302-317)."""
+    _f32c(G, bias)
+    B, rows, T = G.shape
+    C_out = rows // kernel_size
+    assert rows == C_out * kernel_size and (bias is None or tuple(bias.shape) == (C_out,)), (G.shape, kernel_size)
+    Tout = int(_lib.load().ptmi_bigvgan_ola_out_len(T, kernel_size, stride)) if T else 0
+    assert Tout >= 0, (T, kernel_size, stride)
+    out = torch.empty((B, C_out, Tout), dtype=torch.float32, device=G.device)
+    if out.numel():
+        _lib.call('ptmi_bigvgan_ola', G.data_ptr(), _lib.ptr(bias), B, C_out, T, kernel_size, stride, out.data_ptr(), _lib.stream(G.device),
+                  timer='bigvgan_ola')
+    return out
+
+
+@_register('bigvgan_post(Tensor x, Tensor weight, Tensor? bias, bool tanh) -> Tensor')
+def bigvgan_post(x, weight, bias, tanh):
+    """``x [B, C, T]``, ``weight [1, C, K]`` -> ``[B, 1, T]``: conv_post and ``tanh`` / the clamp to [-1, 1] in one launch
+    (``ptmi_bigvgan_post``; bigvgan.py:349-351,380-385)."""
+    _f32c(x, weight, bias)
+    B, C, T = x.shape
+    assert weight.dim() == 3 and weight.shape[:2] == (1, C) and (bias is None or bias.numel() == 1), (weight.shape, x.shape)
+    out = torch.empty((B, 1, T), dtype=torch.float32, device=x.device)
+    if out.numel():
+        _lib.call('ptmi_bigvgan_post', x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), B, C, T, weight.shape[2], int(tanh), out.data_ptr(),
+                  _lib.stream(x.device), timer='bigvgan_post')
+    return out
