@@ -990,6 +990,54 @@ int ptmi_bigvgan_ola(const float* G, const float* bias, int64_t B, int32_t C_out
 int ptmi_bigvgan_post(const float* x, const float* weight, const float* bias, int64_t B, int32_t C, int64_t T, int32_t K, int32_t use_tanh,
                       float* out, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Fused attention and the transformer layer's glue (csrc/attention.hip): padertorch/contrib/je/modules/transformer.py.  fp32, every
+ * product on the matrix cores in exact fp32 (v_mfma_f32_16x16x4_f32), softmax and all reductions in one fixed order, no atomics, no
+ * host reads; the [B, H, Tq, Tk] score tensor is never written unless ptmi_attn_weights is called.
+ *
+ * Operands are addressed as x[b, h, t, c] = base[b s0 + h s1 + t s2 + c]: `strides` is a HOST array of (s0, s1, s2) per tensor, in the
+ * order the prototype lists them (forward: q k v out; weights: q k; backward: q k v out dout dq dk dv).  lse, delta [B, H, Tq] and
+ * weights [B, H, Tq, Tk] are contiguous.  1 <= dh, dv <= ptmi_attn_max_head() (= 128; PTMI_E_UNSUPPORTED beyond).
+ * Masks (transformer.py:29-36, y + log(mask > 0)): (i, j) is visible iff j < min(Tk, lengths[b]) (lengths: int32 or int64 DEVICE
+ * vector, NULL: absent), j <= i + Tk - Tq when causal (get_causal_mask, :259-260) and mask[b m0 + h m1 + i m2 + j m3] != 0 (bytes,
+ * `mask_strides` a HOST array of 4, NULL mask: absent).  A row without a visible key is NaN in out, lse and weights.
+ *
+ * ptmi_attn_tile / _key_tile : rows a workgroup owns (64) / rows of a streamed tile (32): what the tests put Tq and Tk around
+ * ptmi_attn_forward   : out = softmax(scale q k^T + masks) v and lse = log sum exp per row (transformer.py:28-38)
+ * ptmi_attn_weights   : weights = exp(scale q k^T - lse), renormalised per row, 0 where masked (the second return value of :38)
+ * ptmi_attn_backward  : delta = rowsum(dout out) (one small launch), then (dk, dv) by key tile and dq by query tile, probabilities
+ *                       recomputed from lse: the adjoint of :28-38 in out
+ * ptmi_transformer_posenc : out[b,t,2i] = x + cos(t / freq[i]), out[b,t,2i+1] = x + sin(same) (:234-243; out may be x), d even; freq
+ *                       [d / 2] = 10000^(2i/d) is a DEVICE table in float32, as the reference's float32 tensors hold it; the
+ *                       angle is one correctly rounded fp32 division, cos / sin the accurate cosf / sinf
+ * ptmi_transformer_norm_residual_forward  : rows (b, t) of N channels; norm_first: y = LN(z) + res, else u = z + res, y = LN(u)
+ *                       (:151-155, :162-166, :170-174 with norm='layer': Normalization(data_format='btc', statistics_axis='c')); LN is
+ *                       zero for t >= lengths[b]; stats [B T, 2] = (mean, rstd)
+ * ptmi_transformer_norm_residual_backward : dv = the gradient of LN's input v (z or u) from gy, zero behind the length; dparams [2 N]
+ *                       = d gamma | d beta as ordered fp64 column sums (NULL: skipped; workspace: ..._norm_workspace_elems doubles)
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_attn_tile(void);
+int32_t ptmi_attn_key_tile(void);
+int32_t ptmi_attn_max_head(void);
+int ptmi_attn_forward(const float* q, const float* k, const float* v, const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk,
+                      int32_t dh, int32_t dv, float scale, const void* lengths, int32_t lengths_int64, int32_t causal, const uint8_t* mask,
+                      const int64_t* mask_strides, float* out, float* lse, ptmi_stream_t stream);
+int ptmi_attn_weights(const float* q, const float* k, const float* lse, const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk,
+                      int32_t dh, float scale, const void* lengths, int32_t lengths_int64, int32_t causal, const uint8_t* mask,
+                      const int64_t* mask_strides, float* weights, ptmi_stream_t stream);
+int ptmi_attn_backward(const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
+                       const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk, int32_t dh, int32_t dv, float scale,
+                       const void* lengths, int32_t lengths_int64, int32_t causal, const uint8_t* mask, const int64_t* mask_strides,
+                       float* delta, float* dq, float* dk, float* dv_out, ptmi_stream_t stream);
+int ptmi_transformer_posenc(const float* x, float* out, const float* freq, int64_t B, int64_t T, int32_t d, ptmi_stream_t stream);
+int64_t ptmi_transformer_norm_workspace_elems(int64_t rows, int32_t N);
+int ptmi_transformer_norm_residual_forward(const float* z, const float* res, const float* gamma, const float* beta, const void* lengths,
+                                           int32_t lengths_int64, int64_t B, int64_t T, int32_t N, float eps, int32_t norm_first, float* y,
+                                           float* u, float* stats, ptmi_stream_t stream);
+int ptmi_transformer_norm_residual_backward(const float* gy, const float* v, const float* stats, const float* gamma, const void* lengths,
+                                            int32_t lengths_int64, int64_t B, int64_t T, int32_t N, float* dv, float* dparams,
+                                            double* workspace, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -36,3 +36,5 @@ from . import mu_law  # noqa: F401
 from .mu_law import mu_law_encode, mu_law_decode  # noqa: F401
 from . import wavenet  # noqa: F401
 from . import bigvgan  # noqa: F401
+from . import attention  # noqa: F401
+from .attention import scaled_dot_product_attention  # noqa: F401

@@ -41,6 +41,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     _backward_, wavenet_colsum, wavenet_generate_   ptmi_mu_law_*, ptmi_wavenet_*   (ops/mu_law.py, modules/wavenet/wavenet.py, nv_wavenet)
     torch.ops.ptmi.bigvgan_taps_ / bigvgan_conv_direct_ / bigvgan_ola / bigvgan_post   ptmi_bigvgan_*   (contrib/mk/synthesis/vocoder/
                                                                               nvidia_bigvgan/bigvgan.py: the generator's convolutions)
+    torch.ops.ptmi.attn_forward / attn_weights / attn_backward, transformer_posenc_, transformer_norm_residual_forward / _backward
+                                                   ptmi_attn_*, ptmi_transformer_*   (contrib/je/modules/transformer.py:12-38,151-174,234-243)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1595,3 +1597,118 @@ def bigvgan_post(x, weight, bias, tanh):
         _lib.call('ptmi_bigvgan_post', x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), B, C, T, weight.shape[2], int(tanh), out.data_ptr(),
                   _lib.stream(x.device), timer='bigvgan_post')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ attention (csrc/attention.hip)
+def _attn_operand(t):
+    """``[B, H, T, d]`` fp32 with a unit stride on ``d`` (any other strides: the projections' ``[B, T, H, d]`` output is read where it lies)."""
+    assert t.dim() == 4 and t.dtype == torch.float32 and (t.stride(3) == 1 or t.shape[3] == 1), (t.shape, t.stride(), t.dtype)
+    return t
+
+
+def _attn_masks(lengths, mask, B, H, Tq, Tk):
+    lengths, is64 = _lengths(lengths, B)
+    strides = None
+    if mask is not None:
+        assert mask.dtype in (torch.uint8, torch.bool) and tuple(mask.shape) == (B, H, Tq, Tk), (mask.dtype, mask.shape, (B, H, Tq, Tk))
+        strides = _lib.int64s(*mask.stride())
+    return lengths, is64, mask, strides
+
+
+def _attn_heads_last(B, H, T, d, device):
+    """A contiguous ``[B, T, H, d]`` buffer, returned as its ``[B, H, T, d]`` view: what the ``out`` projection reads as ``[B T, H d]``."""
+    return torch.empty((B, T, H, d), dtype=torch.float32, device=device).permute(0, 2, 1, 3)
+
+
+@_register('attn_forward(Tensor q, Tensor k, Tensor v, Tensor? lengths, bool causal, Tensor? mask, float scale) -> (Tensor, Tensor)')
+def attn_forward(q, k, v, lengths, causal, mask, scale):
+    """``(out [B, H, Tq, dv] (a view of a contiguous [B, Tq, H, dv]), lse [B, H, Tq])`` (``ptmi_attn_forward``; transformer.py:28-38)."""
+    B, H, Tq, dh = _attn_operand(q).shape
+    Tk, dv = _attn_operand(k).shape[2], _attn_operand(v).shape[3]
+    assert tuple(k.shape) == (B, H, Tk, dh) and tuple(v.shape) == (B, H, Tk, dv), (q.shape, k.shape, v.shape)
+    lengths, is64, mask, mstr = _attn_masks(lengths, mask, B, H, Tq, Tk)
+    out = _attn_heads_last(B, H, Tq, dv, q.device)
+    lse = torch.empty((B, H, Tq), dtype=torch.float32, device=q.device)
+    strides = _lib.int64s(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3])
+    _lib.call('ptmi_attn_forward', q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, B, H, Tq, Tk, dh, dv, scale, _lib.ptr(lengths), is64,
+              int(causal), _lib.ptr(mask), mstr, out.data_ptr(), lse.data_ptr(), _lib.stream(q.device), timer='attn_forward')
+    return out, lse
+
+
+@_register('attn_weights(Tensor q, Tensor k, Tensor lse, Tensor? lengths, bool causal, Tensor? mask, float scale) -> Tensor')
+def attn_weights(q, k, lse, lengths, causal, mask, scale):
+    """``softmax [B, H, Tq, Tk]`` from ``q``, ``k``, the forward's ``lse`` and the masks (``ptmi_attn_weights``)."""
+    B, H, Tq, dh = _attn_operand(q).shape
+    Tk = _attn_operand(k).shape[2]
+    assert tuple(k.shape) == (B, H, Tk, dh) and tuple(lse.shape) == (B, H, Tq) and lse.is_contiguous(), (q.shape, k.shape, lse.shape)
+    lengths, is64, mask, mstr = _attn_masks(lengths, mask, B, H, Tq, Tk)
+    w = torch.empty((B, H, Tq, Tk), dtype=torch.float32, device=q.device)
+    _lib.call('ptmi_attn_weights', q.data_ptr(), k.data_ptr(), lse.data_ptr(), _lib.int64s(*q.stride()[:3], *k.stride()[:3]), B, H, Tq, Tk, dh,
+              scale, _lib.ptr(lengths), is64, int(causal), _lib.ptr(mask), mstr, w.data_ptr(), _lib.stream(q.device), timer='attn_weights')
+    return w
+
+
+@_register('attn_backward(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor lse, Tensor? lengths, bool causal, Tensor? mask, '
+           'float scale) -> (Tensor, Tensor, Tensor)')
+def attn_backward(q, k, v, out, dout, lse, lengths, causal, mask, scale):
+    """``(dq, dk, dv)`` as ``[B, H, T, d]`` views of contiguous ``[B, T, H, d]`` buffers (``ptmi_attn_backward``)."""
+    B, H, Tq, dh = _attn_operand(q).shape
+    Tk, dv = _attn_operand(k).shape[2], _attn_operand(v).shape[3]
+    assert tuple(_attn_operand(out).shape) == (B, H, Tq, dv) and tuple(_attn_operand(dout).shape) == (B, H, Tq, dv), (out.shape, dout.shape)
+    lengths, is64, mask, mstr = _attn_masks(lengths, mask, B, H, Tq, Tk)
+    dev = q.device
+    dq, dk, dvv = _attn_heads_last(B, H, Tq, dh, dev), _attn_heads_last(B, H, Tk, dh, dev), _attn_heads_last(B, H, Tk, dv, dev)
+    delta = torch.empty((B, H, Tq), dtype=torch.float32, device=dev)
+    strides = _lib.int64s(*[s for t in (q, k, v, out, dout, dq, dk, dvv) for s in t.stride()[:3]])
+    _lib.call('ptmi_attn_backward', q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), strides, B, H,
+              Tq, Tk, dh, dv, scale, _lib.ptr(lengths), is64, int(causal), _lib.ptr(mask), mstr, delta.data_ptr(), dq.data_ptr(),
+              dk.data_ptr(), dvv.data_ptr(), _lib.stream(dev), timer='attn_backward')
+    return dq, dk, dvv
+
+
+@_register('transformer_posenc_(Tensor(a!) x, Tensor freq) -> ()')
+def transformer_posenc_(x, freq):
+    """``x [B, T, d] += `` the interleaved cos / sin encoding with ``freq [d / 2] = 10000^(2i/d)``, in place (``ptmi_transformer_posenc``;
+    transformer.py:234-243)."""
+    _f32c(x, freq)
+    B, T, d = x.shape
+    assert d % 2 == 0 and freq.numel() == d // 2, (x.shape, freq.shape)
+    _lib.call('ptmi_transformer_posenc', x.data_ptr(), x.data_ptr(), freq.data_ptr(), B, T, d, _lib.stream(x.device),
+              timer='transformer_posenc')
+
+
+@_register('transformer_norm_residual_forward(Tensor z, Tensor res, Tensor gamma, Tensor beta, Tensor? lengths, float eps, bool norm_first) '
+           '-> (Tensor, Tensor?, Tensor)')
+def transformer_norm_residual_forward(z, res, gamma, beta, lengths, eps, norm_first):
+    """``(y, u or None, stats [B T, 2])`` of ``z, res [B, T, N]``: ``y = LN(z) + res`` (``norm_first``) or ``u = z + res``, ``y = LN(u)``
+    (``ptmi_transformer_norm_residual_forward``; transformer.py:151-155)."""
+    _f32c(z, res, gamma, beta)
+    B, T, N = z.shape
+    assert res.shape == z.shape and gamma.numel() == N and beta.numel() == N, (z.shape, res.shape, gamma.shape, beta.shape)
+    lengths, is64 = _lengths(lengths, B)
+    y = torch.empty_like(z)
+    u = None if norm_first else torch.empty_like(z)
+    stats = torch.empty((B * T, 2), dtype=torch.float32, device=z.device)
+    _lib.call('ptmi_transformer_norm_residual_forward', z.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _lib.ptr(lengths),
+              is64, B, T, N, eps, int(norm_first), y.data_ptr(), _lib.ptr(u), stats.data_ptr(), _lib.stream(z.device),
+              timer='transformer_norm_residual_forward')
+    return y, u, stats
+
+
+@_register('transformer_norm_residual_backward(Tensor gy, Tensor v, Tensor stats, Tensor gamma, Tensor? lengths, bool want_params) '
+           '-> (Tensor, Tensor?)')
+def transformer_norm_residual_backward(gy, v, stats, gamma, lengths, want_params):
+    """``(dv [B, T, N], dparams [2 N] = d gamma | d beta or None)`` for the normalised tensor ``v`` (``z``, or ``u`` when the norm came
+    second) (``ptmi_transformer_norm_residual_backward``)."""
+    lib = _lib.load()
+    _f32c(gy, v, stats, gamma)
+    B, T, N = v.shape
+    assert gy.shape == v.shape and stats.shape == (B * T, 2) and gamma.numel() == N, (gy.shape, v.shape, stats.shape)
+    lengths, is64 = _lengths(lengths, B)
+    dv = torch.empty_like(v)
+    dparams = torch.empty(2 * N, dtype=torch.float32, device=v.device) if want_params else None
+    ws = _doubles(lib.ptmi_transformer_norm_workspace_elems(B * T, N), v.device) if want_params else None
+    _lib.call('ptmi_transformer_norm_residual_backward', gy.data_ptr(), v.data_ptr(), stats.data_ptr(), gamma.data_ptr(), _lib.ptr(lengths),
+              is64, B, T, N, dv.data_ptr(), _lib.ptr(dparams), _lib.ptr(ws), _lib.stream(v.device),
+              timer='transformer_norm_residual_backward')
+    return dv, dparams

@@ -36,6 +36,32 @@ DEFER_MAX_FLOP = 15e9
 FUSE_RELU = True
 
 
+#: attribute of an input that several Linear layers read (the three projections of self-attention): [tensor version, amax word, its
+#: ``pack_n`` form] - the first layer packs, the others take the form as it lies (:func:`share_input` / :func:`release_input`)
+PACK_ATTR = '_ptmi_pack_n'
+
+
+def share_input(x):
+    """The ``linear`` calls on ``x`` that follow (same tensor object, same ``x_range``) pack the operand ONCE, until :func:`release_input`."""
+    setattr(x, PACK_ATTR, [x._version, None, None])
+    return x
+
+
+def release_input(x):
+    if hasattr(x, PACK_ATTR):
+        delattr(x, PACK_ATTR)
+
+
+def _pack_input(x, amax):
+    rec = getattr(x, PACK_ATTR, None)
+    if rec is None or rec[0] != x._version:
+        return _gemm.pack_n(x, amax)
+    same = rec[1] is amax or (torch.is_tensor(rec[1]) and torch.is_tensor(amax) and rec[1].data_ptr() == amax.data_ptr())
+    if rec[2] is None or not same:
+        rec[1], rec[2] = amax, _gemm.pack_n(x, amax)
+    return rec[2]
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, module, amax_x, relu=False):
@@ -57,7 +83,7 @@ class _LinearFn(torch.autograd.Function):
                 (scratch, cols), ndir, H = lh
                 a, b, K = (scratch, _gemm.scale_word(x.device)), _gemm.weight_planes_h(module.weight, ndir, H, cols), ndir * cols
             else:
-                a, b, K = _gemm.pack_n(x, amax_x), _gemm.weight_planes(module.weight), x.shape[1]
+                a, b, K = _pack_input(x, amax_x), _gemm.weight_planes(module.weight), x.shape[1]
             split = _gemm.auto_split_k(x.shape[0], weight.shape[0], K)
             if relu:
                 torch.ops.ptmi.gemm_planes_relu_(y, a[0], a[1], b[0], b[1], bias, x.shape[0], weight.shape[0], K, split, amax_y)
