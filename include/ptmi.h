@@ -1038,6 +1038,49 @@ int ptmi_transformer_norm_residual_backward(const float* gy, const float* v, con
                                             int32_t lengths_int64, int64_t B, int64_t T, int32_t N, float* dv, float* dparams,
                                             double* workspace, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The GRU recurrence (csrc/gru.hip) and the sequence glue (csrc/seq_pool.hip) of padertorch/contrib/je/modules/rnn.py and reduce.py.
+ * fp32, every launcher capturable, lengths and tables are device data, sums fp64 in a fixed order, no atomics.
+ *
+ * ptmi_chunk_gru_forward  : the time loop of one torch.nn.GRU layer (gate order r, z, n), ndir = 1 or 2 directions, over the sequences
+ *   of table [nseq][3] = (base row, step stride, step count <= cap), the contract of ptmi_chunk_lstm_forward.  gates [rows, ndir 3H]
+ *   holds x W_ih^T + b_ih and becomes the activated gates; q [rows, ndir H] receives h W_hn^T + b_hn, h [rows, ndir H] the output (zero
+ *   on a sequence's rows count .. cap).  b_hh may be NULL (bias=False).  flip != 0 runs direction d in the opposite sense of time.  A
+ *   sequence whose rows do not all lie inside [0, rows) is skipped.  A workgroup owns ptmi_chunk_gru_tile() sequences of one
+ *   direction; W_hh stays in registers for H <= ptmi_chunk_gru_max_resident_hidden() (128) and is streamed from the L2 above that, up
+ *   to H = ptmi_chunk_gru_max_hidden() (1792: the streamed backward kernel keeps 5 tile H words in LDS); beyond: PTMI_E_UNSUPPORTED.
+ * ptmi_chunk_gru_backward : gates is OVERWRITTEN by (dr_pre, dz_pre, dn_pre) - the operand of dW_ih, db_ih and dx - and q by dn_pre r,
+ *   the n block of the operand of dW_hh and db_hh (its r and z blocks are those of gates); hprev [rows, ndir H] receives h of every
+ *   row's step before.  Zeros in all three on the rows of no step.
+ * ptmi_seq_table   : table [B][3] = (b T, 1, clip(lengths[b], 0, T)); lengths NULL: T.
+ * ptmi_seq_gather  : out [B, T, F] contiguous from x through x_strides [3].  mode 0: a copy; 1: reverse_sequence (rnn.py:130-154:
+ *   out[b, t] = x[b, len - 1 - t] below the length, x[b, (len - 1 - t) mod T] * 0 behind it); 2: its adjoint (plain zeros behind).
+ * ptmi_seq_pool_forward  : x read as [B, M, T, I] = dims [4] through strides [4]; y [B, M, I].  mode 0 sum, 1 mean (with lengths: sum /
+ *   (float(len) + 1e-6f), without: / T), 2 max (index [B, M, I] int64 = first position of the maximum, a NaN wins; no step: -inf, 0), 3
+ *   last (x[len - 1]; len 0: x[T - 1]), 4 autopool (sum_t softmax_t(alpha x) x over t < len; alpha [M] (then I = 1) or NULL: alpha0).
+ *   wave_per_row != 0: a wavefront per (b, m, i), else a thread.
+ * ptmi_seq_pool_backward : dx [B, M, T, I] contiguous, written whole.  autopool recomputes the softmax from x and y; dalpha [M] (with
+ *   workspace [B M] doubles) = sum over b of g (sum_t w x^2 - y^2), or both NULL.
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_chunk_gru_max_hidden(void);
+int32_t ptmi_chunk_gru_max_resident_hidden(void);
+int32_t ptmi_chunk_gru_tile(void);
+int ptmi_chunk_gru_forward(float* gates, const float* w_hh, const float* w_hh_reverse, const float* b_hh, const float* b_hh_reverse,
+                           float* q, float* h, const int32_t* table, int64_t rows, int32_t nseq, int32_t cap, int32_t H, int32_t ndir,
+                           int32_t flip, ptmi_stream_t stream);
+int ptmi_chunk_gru_backward(float* gates, float* q, const float* dh, const float* w_hh, const float* w_hh_reverse, const float* h,
+                            float* hprev, const int32_t* table, int64_t rows, int32_t nseq, int32_t cap, int32_t H, int32_t ndir,
+                            int32_t flip, ptmi_stream_t stream);
+int ptmi_seq_table(const void* lengths, int32_t lengths_int64, int32_t B, int32_t T, int32_t* table, ptmi_stream_t stream);
+int ptmi_seq_gather(const float* x, const int64_t* x_strides, const void* lengths, int32_t lengths_int64, float* out, int64_t B, int64_t T,
+                    int64_t F, int32_t mode, ptmi_stream_t stream);
+int ptmi_seq_pool_forward(const float* x, const int64_t* dims, const int64_t* strides, const void* lengths, int32_t lengths_int64,
+                          int32_t mode, const float* alpha, float alpha0, float* y, int64_t* index, int32_t wave_per_row,
+                          ptmi_stream_t stream);
+int ptmi_seq_pool_backward(const float* x, const int64_t* dims, const int64_t* strides, const void* lengths, int32_t lengths_int64,
+                           int32_t mode, const float* alpha, float alpha0, const float* g, const float* y, const int64_t* index,
+                           float* dx, double* workspace, float* dalpha, int32_t wave_per_row, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -38,3 +38,7 @@ from . import wavenet  # noqa: F401
 from . import bigvgan  # noqa: F401
 from . import attention  # noqa: F401
 from .attention import scaled_dot_product_attention  # noqa: F401
+from . import gru  # noqa: F401
+from .gru import chunk_gru  # noqa: F401
+from . import seq_pool  # noqa: F401
+from .seq_pool import reverse_sequence  # noqa: F401

@@ -9,6 +9,7 @@ stride, step count): intra-chunk sequences have stride 1, inter-chunk sequences 
     segment_rows(x [B, L, N], K, P) -> [B, S, K, N]        differentiable; each is the other's backward
     overlap_add_rows(seg [B, S, K, N], P) -> [B, S P - (K - P), N]
     chunk_lstm(x [rows, N], table, cap, rnn) -> [rows, D H] one ``torch.nn.LSTM`` layer over the table's sequences
+    chunk_lstm_params(x [rows, N], table, cap, w_ih, w_hh, b_ih, b_hh, ...) -> [rows, D H]   the same for one layer's parameter tensors
     chunk_rnn(x [rows, N], table, cap, chunks, S, K, rnn, fc, norm) -> [rows, N]
         one ``_ChunkRNN``: LSTM, projection, layer norm (zeros on the positions with ``s >= chunks[b]``), plus ``x``
 
@@ -23,7 +24,7 @@ from .. import _lib
 from . import gemm as _gemm
 from . import library  # noqa: F401  (registers torch.ops.ptmi.*)
 
-__all__ = ['num_chunks', 'chunk_counts', 'tables', 'segment_rows', 'overlap_add_rows', 'chunk_lstm', 'chunk_rnn', 'MAX_HIDDEN', 'RESIDENT_HIDDEN']
+__all__ = ['num_chunks', 'chunk_counts', 'tables', 'segment_rows', 'overlap_add_rows', 'chunk_lstm', 'chunk_lstm_params', 'chunk_rnn', 'MAX_HIDDEN', 'RESIDENT_HIDDEN']
 
 #: the largest ``hidden_size`` the recurrence kernels take (``ptmi_chunk_lstm_max_hidden``); up to :data:`RESIDENT_HIDDEN` ``W_hh`` stays
 #: in the registers of a workgroup, above it is streamed from the L2 every step
@@ -273,6 +274,29 @@ def chunk_lstm(x, table, cap, rnn):
     if x.shape[1] != rnn.input_size:
         raise ValueError(f'chunk_lstm: x [rows, {rnn.input_size}], got {tuple(x.shape)}')
     _check('chunk_lstm', *params)
+    return _ChunkLstmFn.apply(x, table, cap, *params)
+
+
+def chunk_lstm_params(x, table, cap, w_ih, w_hh, b_ih, b_hh, w_ih_reverse=None, w_hh_reverse=None, b_ih_reverse=None,
+                      b_hh_reverse=None):
+    """:func:`chunk_lstm` for the parameter tensors of ONE layer (``weight_ih [4H, N]``, ``weight_hh [4H, H]``, ``bias_ih``, ``bias_hh
+    [4H]``; the ``_reverse`` four make it bidirectional), so that a multi-layer ``torch.nn.LSTM`` can be walked layer by layer."""
+    params = [w_ih, w_hh, b_ih, b_hh, w_ih_reverse, w_hh_reverse, b_ih_reverse, b_hh_reverse]
+    _check('chunk_lstm', x, *params)
+    table, cap = _table('chunk_lstm', x, table, cap)
+    dirs = _directions(params)
+    if not dirs or any(p is None for d in dirs for p in d):
+        raise NotImplementedError('chunk_lstm: weight_ih, weight_hh, bias_ih and bias_hh per direction (the recurrence kernel has no '
+                                  'bias-free form)')
+    H = w_hh.shape[1]
+    for w_i, w_h, b_i, b_h in dirs:
+        if tuple(w_i.shape) != (4 * H, x.shape[1]) or tuple(w_h.shape) != (4 * H, H) or b_i.shape != (4 * H,) or b_h.shape != (4 * H,):
+            raise ValueError(f'chunk_lstm: weight_ih [{4 * H}, {x.shape[1]}], weight_hh [{4 * H}, {H}] and biases [{4 * H}], got '
+                             f'{tuple(w_i.shape)}, {tuple(w_h.shape)}, {tuple(b_i.shape)}, {tuple(b_h.shape)}')
+    if H > MAX_HIDDEN:
+        raise NotImplementedError(f'chunk_lstm: hidden_size {H} > {MAX_HIDDEN}')
+    if len(dirs) == 1:
+        params[4:] = [None] * 4
     return _ChunkLstmFn.apply(x, table, cap, *params)
 
 

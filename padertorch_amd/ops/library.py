@@ -43,6 +43,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                                               nvidia_bigvgan/bigvgan.py: the generator's convolutions)
     torch.ops.ptmi.attn_forward / attn_weights / attn_backward, transformer_posenc_, transformer_norm_residual_forward / _backward
                                                    ptmi_attn_*, ptmi_transformer_*   (contrib/je/modules/transformer.py:12-38,151-174,234-243)
+    torch.ops.ptmi.chunk_gru_forward / chunk_gru_backward, seq_table, seq_gather, seq_pool_forward / _backward
+                                                   ptmi_chunk_gru_*, ptmi_seq_*   (contrib/je/modules/rnn.py, reduce.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1712,3 +1714,110 @@ def transformer_norm_residual_backward(gy, v, stats, gamma, lengths, want_params
               is64, B, T, N, dv.data_ptr(), _lib.ptr(dparams), _lib.ptr(ws), _lib.stream(v.device),
               timer='transformer_norm_residual_backward')
     return dv, dparams
+
+
+# ------------------------------------------------------------------------------------------------ GRU + sequence glue (csrc/gru.hip, csrc/seq_pool.hip)
+def _chunk_gru_dims(gates, table, H):
+    _f32c(gates)
+    _i32c(table)
+    assert gates.dim() == 2 and table.dim() == 2 and table.shape[1] == 3 and gates.shape[1] % (3 * H) == 0, (gates.shape, table.shape, H)
+    ndir = gates.shape[1] // (3 * H)
+    assert ndir in (1, 2), gates.shape
+    return gates.shape[0], ndir
+
+
+@_register('chunk_gru_forward(Tensor(a!) gates, Tensor w_hh, Tensor? w_hh_reverse, Tensor? b_hh, Tensor? b_hh_reverse, Tensor table, '
+           'int cap, int H, bool flip) -> (Tensor, Tensor)')
+def chunk_gru_forward(gates, w_hh, w_hh_reverse, b_hh, b_hh_reverse, table, cap, H, flip):
+    """The time loop of one GRU layer over the sequences of ``table [nseq, 3]``: ``gates [rows, ndir 3H]`` holds ``x W_ih^T + b_ih`` and
+    becomes the activated ``(r, z, n)``; returns ``(h, q) [rows, ndir H]`` with ``q = h W_hn^T + b_hn`` (``ptmi_chunk_gru_forward``)."""
+    rows, ndir = _chunk_gru_dims(gates, table, H)
+    _f32c(w_hh, w_hh_reverse, b_hh, b_hh_reverse)
+    assert w_hh.shape == (3 * H, H) and (ndir == 1 or w_hh_reverse.shape == (3 * H, H)), (w_hh.shape, ndir)
+    assert all(b is None or b.shape == (3 * H,) for b in (b_hh, b_hh_reverse))
+    h = torch.empty((rows, ndir * H), dtype=torch.float32, device=gates.device)
+    q = torch.empty((rows, ndir * H), dtype=torch.float32, device=gates.device)
+    rc = _lib.call('ptmi_chunk_gru_forward', gates.data_ptr(), w_hh.data_ptr(), _lib.ptr(w_hh_reverse), _lib.ptr(b_hh), _lib.ptr(b_hh_reverse),
+                   q.data_ptr(), h.data_ptr(), table.data_ptr(), rows, table.shape[0], cap, H, ndir, int(flip), _lib.stream(gates.device),
+                   timer=f'chunk_gru_forward:{table.shape[0]}x{cap}x{H}', accept=(-2,))
+    if rc == -2:
+        raise NotImplementedError(f'chunk_gru: hidden_size {H} is beyond the recurrence kernels\' bound')
+    return h, q
+
+
+@_register('chunk_gru_backward(Tensor(a!) gates, Tensor(b!) q, Tensor dh, Tensor w_hh, Tensor? w_hh_reverse, Tensor h, Tensor table, '
+           'int cap, int H, bool flip) -> Tensor')
+def chunk_gru_backward(gates, q, dh, w_hh, w_hh_reverse, h, table, cap, H, flip):
+    """``gates`` becomes ``(dr_pre, dz_pre, dn_pre)``, ``q`` becomes ``dn_pre r``; returns ``hprev [rows, ndir H]``
+    (``ptmi_chunk_gru_backward``)."""
+    rows, ndir = _chunk_gru_dims(gates, table, H)
+    _f32c(q, dh, w_hh, w_hh_reverse, h)
+    assert dh.shape == h.shape == q.shape == (rows, ndir * H), (dh.shape, h.shape, q.shape)
+    hprev = torch.empty_like(h)
+    _lib.call('ptmi_chunk_gru_backward', gates.data_ptr(), q.data_ptr(), dh.data_ptr(), w_hh.data_ptr(), _lib.ptr(w_hh_reverse), h.data_ptr(),
+              hprev.data_ptr(), table.data_ptr(), rows, table.shape[0], cap, H, ndir, int(flip), _lib.stream(gates.device),
+              timer=f'chunk_gru_backward:{table.shape[0]}x{cap}x{H}')
+    return hprev
+
+
+@_register('seq_table(Tensor like, Tensor? lengths, int B, int T) -> Tensor')
+def seq_table(like, lengths, B, T):
+    """``table [B, 3]`` int32 = ``(b T, 1, clip(lengths[b], 0, T))`` on ``like``'s device; no lengths: ``T`` (``ptmi_seq_table``)."""
+    lengths, is64 = _lengths(lengths, B)
+    table = torch.empty((B, 3), dtype=torch.int32, device=like.device)
+    _lib.call('ptmi_seq_table', _lib.ptr(lengths), is64, B, T, table.data_ptr(), _lib.stream(like.device), timer='seq_table')
+    return table
+
+
+@_register('seq_gather(Tensor x, Tensor? lengths, int mode) -> Tensor')
+def seq_gather(x, lengths, mode):
+    """``x [B, T, F]`` (any strides) -> contiguous ``[B, T, F]``: a copy (0), ``reverse_sequence`` (1) or its adjoint (2)
+    (``ptmi_seq_gather``)."""
+    assert x.dim() == 3 and x.dtype == torch.float32 and x.numel() > 0, (x.shape, x.dtype)
+    B, T, F = x.shape
+    lengths, is64 = _lengths(lengths, B)
+    out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
+    _lib.call('ptmi_seq_gather', x.data_ptr(), _lib.int64s(*x.stride()), _lib.ptr(lengths), is64, out.data_ptr(), B, T, F, mode,
+              _lib.stream(x.device), timer='seq_gather')
+    return out
+
+
+@_register('seq_pool_forward(Tensor x, int[] dims, int[] strides, Tensor? lengths, int mode, Tensor? alpha, float alpha0, bool wave) '
+           '-> (Tensor, Tensor?)')
+def seq_pool_forward(x, dims, strides, lengths, mode, alpha, alpha0, wave):
+    """``x`` read as ``[B, M, T, I] = dims`` through ``strides`` -> ``(y [B, M, I], index [B, M, I] int64 for mode 2)``
+    (``ptmi_seq_pool_forward``)."""
+    assert x.dtype == torch.float32 and len(dims) == 4 and len(strides) == 4 and min(dims) >= 1, (x.dtype, dims, strides)
+    B, M, T, I = dims
+    assert sum((d - 1) * s for d, s in zip(dims, strides)) < max(x.untyped_storage().nbytes() // 4 - x.storage_offset(), 1) and min(strides) >= 0
+    lengths, is64 = _lengths(lengths, B)
+    _f32c(alpha)
+    assert alpha is None or (alpha.numel() == M and I == 1)
+    y = torch.empty((B, M, I), dtype=torch.float32, device=x.device)
+    index = torch.empty((B, M, I), dtype=torch.int64, device=x.device) if mode == 2 else None
+    _lib.call('ptmi_seq_pool_forward', x.data_ptr(), _lib.int64s(*dims), _lib.int64s(*strides), _lib.ptr(lengths), is64, mode, _lib.ptr(alpha),
+              alpha0, y.data_ptr(), _lib.ptr(index), int(wave), _lib.stream(x.device), timer=f'seq_pool_forward:{mode}')
+    return y, index
+
+
+@_register('seq_pool_backward(Tensor x, int[] dims, int[] strides, Tensor? lengths, int mode, Tensor? alpha, float alpha0, Tensor g, '
+           'Tensor? y, Tensor? index, bool want_dalpha) -> (Tensor, Tensor?)')
+def seq_pool_backward(x, dims, strides, lengths, mode, alpha, alpha0, g, y, index, want_dalpha):
+    """``(dx [B, M, T, I] contiguous, dalpha [M] or None)`` (``ptmi_seq_pool_backward``); the thread map follows ``dx``'s layout: a
+    wavefront per row when ``I == 1``."""
+    assert x.dtype == torch.float32 and len(dims) == 4 and len(strides) == 4 and min(dims) >= 1, (x.dtype, dims, strides)
+    B, M, T, I = dims
+    lengths, is64 = _lengths(lengths, B)
+    _f32c(alpha, g, y)
+    assert g.numel() == B * M * I and (y is None or y.numel() == g.numel()) and (index is None or (index.numel() == g.numel()
+                                                                                                   and index.is_contiguous()))
+    dx = torch.empty((B, M, T, I), dtype=torch.float32, device=x.device)
+    dalpha = ws = None
+    if want_dalpha:
+        assert mode == 4 and alpha is not None and I == 1
+        dalpha = torch.empty(M, dtype=torch.float32, device=x.device)
+        ws = _doubles(B * M, x.device)
+    _lib.call('ptmi_seq_pool_backward', x.data_ptr(), _lib.int64s(*dims), _lib.int64s(*strides), _lib.ptr(lengths), is64, mode,
+              _lib.ptr(alpha), alpha0, g.data_ptr(), _lib.ptr(y), _lib.ptr(index), dx.data_ptr(), _lib.ptr(ws), _lib.ptr(dalpha), int(I == 1),
+              _lib.stream(x.device), timer=f'seq_pool_backward:{mode}')
+    return dx, dalpha
