@@ -1081,6 +1081,46 @@ int ptmi_seq_pool_backward(const float* x, const int64_t* dims, const int64_t* s
                            int32_t mode, const float* alpha, float alpha0, const float* g, const float* y, const int64_t* index,
                            float* dx, double* workspace, float* dalpha, int32_t wave_per_row, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The convolution blocks and pools of padertorch/contrib/je/modules/conv.py and conv_utils.py (csrc/je_conv.hip) on channels-last rows:
+ * an activation [B, C, T] is held as [B T, C] (row b T + t).  fp32, every launcher capturable, lengths are device data (int32 or int64,
+ * clipped to [0, T]; NULL: T), sums fp64 in a fixed order, no atomics.  act: 0 identity, 1 relu, 2 leaky_relu (act_p: negative slope),
+ * 3 elu (act_p: alpha), 4 tanh, 5 sigmoid, 6 prelu (slope: its one parameter on the device).
+ *
+ * geom [11] of taps / dtaps = (B, T_in, T_out, C_out, K, stride, dilation, front pad, G, ld of P, ld of residual); G = 1, or 2 with gate rows.
+ * ptmi_je_conv_taps  : z[b, t, co] = bias[co] + sum_k P[b, t stride + k dilation - front, k C_out + co] (k ascending; rows outside
+ *   [0, T_in) are zero: no padded copy), P [B T_in, G K C_out]; gz likewise from the columns K C_out.. and gate_bias.  out != NULL:
+ *   out = act(z) sigmoid(gz) + residual in the same launch (gz / residual where given).  z, gz, out [B T_out, C_out] contiguous.
+ * ptmi_je_conv_dtaps : dP[b, u, (q K + k) C_out + co] = (q ? dgz : dz)[b, (u + front - k dilation) / stride, co] where the division is
+ *   exact and the row exists, else 0; every element of dP [B T_in, G K C_out] is written.
+ * ptmi_je_conv_stats : sums [3][groups][C] (doubles; sum, sum of squares, 0) of x [B T, C] (row stride ldx) over t < lengths[b], and
+ *   stats [groups][4][C] = mean, rstd = 1 / sqrt(max(power - mean^2, 0) + eps), power, count; groups = 1 (per_example 0: over b and t)
+ *   or B.  workspace: ptmi_je_conv_workspace_elems(B, T, C) doubles.
+ * ptmi_je_conv_apply : out = act(n) sigmoid(g) + residual with n = gamma (z - mean) rstd + beta and n = 0 for t >= lengths[b]; stats
+ *   NULL: n = z and gamma, beta, lengths are not read.  g, residual, gamma, beta may be NULL.
+ * ptmi_je_conv_apply_backward : dz (the gradient of z: through the statistics unless fixed_stats) and dgz from dout [B T, C]; dparams
+ *   [2 C + 1] = d gamma | d beta | d slope or NULL.  workspace as above and sums [3][groups][C] doubles are needed with stats (not
+ *   fixed) or dparams.
+ * geom [8] of the pools = (B, T_in, T_out, C, size, stride, front pad, ld of x): the padded axis holds zeros around the T_in values.
+ * ptmi_je_pool_forward  : max (index [B T_out, C]: position on the padded axis; the first of equal values, a NaN beats numbers) or mean.
+ * ptmi_je_pool_backward : dx [B T_in, C] contiguous, every element written: a gather over the windows that hold the position.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t ptmi_je_conv_workspace_elems(int64_t B, int64_t T, int64_t C);
+int ptmi_je_conv_taps(const float* P, const float* bias, const float* gate_bias, const float* residual, const float* slope, float* z,
+                      float* gz, float* out, const int64_t* geom, int32_t act, float act_p, ptmi_stream_t stream);
+int ptmi_je_conv_dtaps(const float* dz, const float* dgz, float* dP, const int64_t* geom, ptmi_stream_t stream);
+int ptmi_je_conv_stats(const float* x, int64_t ldx, const void* lengths, int32_t lengths_int64, int64_t B, int64_t T, int64_t C,
+                       int32_t per_example, float eps, double* workspace, double* sums, float* stats, ptmi_stream_t stream);
+int ptmi_je_conv_apply(const float* z, int64_t ldz, const float* g, const float* residual, int64_t ldr, const float* stats,
+                       const float* gamma, const float* beta, const void* lengths, int32_t lengths_int64, const float* slope, float* out,
+                       int64_t B, int64_t T, int64_t C, int32_t per_example, int32_t act, float act_p, ptmi_stream_t stream);
+int ptmi_je_conv_apply_backward(const float* dout, const float* z, int64_t ldz, const float* g, const float* stats, const float* gamma,
+                                const float* beta, const void* lengths, int32_t lengths_int64, const float* slope, float* dz, float* dgz,
+                                float* dparams, double* workspace, double* sums, int64_t B, int64_t T, int64_t C, int32_t per_example,
+                                int32_t fixed_stats, int32_t act, float act_p, ptmi_stream_t stream);
+int ptmi_je_pool_forward(const float* x, float* y, int64_t* index, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
+int ptmi_je_pool_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

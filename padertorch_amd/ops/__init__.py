@@ -42,3 +42,4 @@ from . import gru  # noqa: F401
 from .gru import chunk_gru  # noqa: F401
 from . import seq_pool  # noqa: F401
 from .seq_pool import reverse_sequence  # noqa: F401
+from . import je_conv  # noqa: F401

@@ -45,6 +45,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                    ptmi_attn_*, ptmi_transformer_*   (contrib/je/modules/transformer.py:12-38,151-174,234-243)
     torch.ops.ptmi.chunk_gru_forward / chunk_gru_backward, seq_table, seq_gather, seq_pool_forward / _backward
                                                    ptmi_chunk_gru_*, ptmi_seq_*   (contrib/je/modules/rnn.py, reduce.py)
+    torch.ops.ptmi.je_conv_taps / je_conv_dtaps / je_conv_stats / je_conv_apply / je_conv_apply_backward, je_pool_forward / _backward
+                                                   ptmi_je_conv_*, ptmi_je_pool_*   (contrib/je/modules/conv.py, conv_utils.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1821,3 +1823,131 @@ def seq_pool_backward(x, dims, strides, lengths, mode, alpha, alpha0, g, y, inde
               _lib.ptr(alpha), alpha0, g.data_ptr(), _lib.ptr(y), _lib.ptr(index), dx.data_ptr(), _lib.ptr(ws), _lib.ptr(dalpha), int(I == 1),
               _lib.stream(x.device), timer=f'seq_pool_backward:{mode}')
     return dx, dalpha
+
+
+# ------------------------------------------------------------------------------------------------ contrib/je convolution blocks (csrc/je_conv.hip)
+#: the activation codes of ptmi_je_conv_*
+JE_CONV_ACTIVATIONS = {'identity': 0, 'relu': 1, 'leaky_relu': 2, 'elu': 3, 'tanh': 4, 'sigmoid': 5, 'prelu': 6}
+
+
+def _jc_rows(t, width, what):
+    """``t [rows, width]`` as (pointer, row stride): unit inner stride."""
+    assert t.dim() == 2 and t.dtype == torch.float32 and t.shape[1] == width and (t.stride(1) == 1 or width == 1), (what, t.shape, t.stride())
+    return t.data_ptr(), max(_ld(t), width)
+
+
+@_register('je_conv_taps(Tensor P, Tensor? bias, Tensor? gate_bias, Tensor? residual, Tensor? slope, int[] geom, int act, float act_p, '
+           'bool fused) -> (Tensor, Tensor?, Tensor?)')
+def je_conv_taps(P, bias, gate_bias, residual, slope, geom, act, act_p, fused):
+    """``(z, gz or None, out or None) [B T_out, C_out]`` from ``P [B T_in, G K C_out]``; ``geom = (B, T_in, T_out, C_out, K, stride,
+    dilation, front, G)``; ``fused``: the epilogue ``out = act(z) sigmoid(gz) + residual`` in the same launch (``ptmi_je_conv_taps``)."""
+    _f32c(P, bias, gate_bias, slope)
+    B, T_in, T_out, C_out, K, _, _, _, G = geom
+    assert tuple(P.shape) == (B * T_in, G * K * C_out), (P.shape, geom)
+    assert all(b is None or b.numel() == C_out for b in (bias, gate_bias))
+    rp, ldr = (None, C_out) if residual is None else _jc_rows(residual, C_out, 'residual')
+    assert residual is None or residual.shape[0] == B * T_out
+    dev = P.device
+    z = torch.empty((B * T_out, C_out), dtype=torch.float32, device=dev)
+    gz = torch.empty_like(z) if G == 2 else None
+    out = torch.empty_like(z) if fused else None
+    _lib.call('ptmi_je_conv_taps', P.data_ptr(), _lib.ptr(bias), _lib.ptr(gate_bias), rp, _lib.ptr(slope), z.data_ptr(), _lib.ptr(gz),
+              _lib.ptr(out), _lib.int64s(*geom, G * K * C_out, ldr), act, act_p, _lib.stream(dev), timer='je_conv_taps')
+    return z, gz, out
+
+
+@_register('je_conv_dtaps(Tensor dz, Tensor? dgz, int[] geom) -> Tensor')
+def je_conv_dtaps(dz, dgz, geom):
+    """``dP [B T_in, G K C_out]`` in gather form from ``dz`` / ``dgz [B T_out, C_out]`` (``ptmi_je_conv_dtaps``)."""
+    _f32c(dz, dgz)
+    B, T_in, T_out, C_out, K, _, _, _, G = geom
+    assert tuple(dz.shape) == (B * T_out, C_out) and (G == 1 or dgz.shape == dz.shape), (dz.shape, geom)
+    dP = torch.empty((B * T_in, G * K * C_out), dtype=torch.float32, device=dz.device)
+    _lib.call('ptmi_je_conv_dtaps', dz.data_ptr(), _lib.ptr(dgz), dP.data_ptr(), _lib.int64s(*geom, G * K * C_out, C_out),
+              _lib.stream(dz.device), timer='je_conv_dtaps')
+    return dP
+
+
+@_register('je_conv_stats(Tensor x, Tensor? lengths, int B, int T, bool per_example, float eps) -> Tensor')
+def je_conv_stats(x, lengths, B, T, per_example, eps):
+    """``stats [groups, 4, C]`` = mean, rstd, power, count of ``x [B T, C]`` over ``t < lengths[b]`` (``ptmi_je_conv_stats``)."""
+    C = x.shape[1]
+    xp, ldx = _jc_rows(x, C, 'x')
+    assert x.shape[0] == B * T
+    lengths, is64 = _lengths(lengths, B)
+    groups = B if per_example else 1
+    ws = _doubles(_lib.load().ptmi_je_conv_workspace_elems(B, T, C), x.device)
+    sums = _doubles(3 * groups * C, x.device)
+    stats = torch.empty((groups, 4, C), dtype=torch.float32, device=x.device)
+    _lib.call('ptmi_je_conv_stats', xp, ldx, _lib.ptr(lengths), is64, B, T, C, int(per_example), eps, ws.data_ptr(), sums.data_ptr(),
+              stats.data_ptr(), _lib.stream(x.device), timer='je_conv_stats')
+    return stats
+
+
+@_register('je_conv_apply(Tensor z, Tensor? g, Tensor? residual, Tensor? stats, Tensor? gamma, Tensor? beta, Tensor? lengths, '
+           'Tensor? slope, int B, int T, bool per_example, int act, float act_p) -> Tensor')
+def je_conv_apply(z, g, residual, stats, gamma, beta, lengths, slope, B, T, per_example, act, act_p):
+    """``out [B T, C] = act(n) sigmoid(g) + residual``, ``n = gamma (z - mean) rstd + beta`` and 0 behind the length (``ptmi_je_conv_apply``)."""
+    C = z.shape[1]
+    zp, ldz = _jc_rows(z, C, 'z')
+    rp, ldr = (None, C) if residual is None else _jc_rows(residual, C, 'residual')
+    _f32c(g, stats, gamma, beta, slope)
+    assert z.shape[0] == B * T and (g is None or g.shape == z.shape) and (residual is None or residual.shape == z.shape)
+    assert stats is None or tuple(stats.shape) == (B if per_example else 1, 4, C), (stats.shape, B, C)
+    assert all(p is None or p.numel() == C for p in (gamma, beta))
+    lengths, is64 = _lengths(lengths, B)
+    out = torch.empty((B * T, C), dtype=torch.float32, device=z.device)
+    _lib.call('ptmi_je_conv_apply', zp, ldz, _lib.ptr(g), rp, ldr, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(lengths), is64,
+              _lib.ptr(slope), out.data_ptr(), B, T, C, int(per_example), act, act_p, _lib.stream(z.device), timer='je_conv_apply')
+    return out
+
+
+@_register('je_conv_apply_backward(Tensor dout, Tensor z, Tensor? g, Tensor? stats, Tensor? gamma, Tensor? beta, Tensor? lengths, '
+           'Tensor? slope, int B, int T, bool per_example, bool fixed_stats, int act, float act_p, bool want_params) '
+           '-> (Tensor, Tensor?, Tensor?)')
+def je_conv_apply_backward(dout, z, g, stats, gamma, beta, lengths, slope, B, T, per_example, fixed_stats, act, act_p, want_params):
+    """``(dz, dgz or None, dparams [2 C + 1] = d gamma | d beta | d slope or None)`` (``ptmi_je_conv_apply_backward``)."""
+    C = z.shape[1]
+    zp, ldz = _jc_rows(z, C, 'z')
+    _f32c(dout, g, stats, gamma, beta, slope)
+    assert dout.shape == z.shape and z.shape[0] == B * T and (g is None or g.shape == z.shape)
+    assert stats is None or tuple(stats.shape) == (B if per_example else 1, 4, C), (stats.shape, B, C)
+    lengths, is64 = _lengths(lengths, B)
+    dev = z.device
+    dz = torch.empty((B * T, C), dtype=torch.float32, device=dev)
+    dgz = torch.empty_like(dz) if g is not None else None
+    dparams = torch.empty(2 * C + 1, dtype=torch.float32, device=dev) if want_params else None
+    ws = sums = None
+    if want_params or (stats is not None and not fixed_stats):
+        ws = _doubles(_lib.load().ptmi_je_conv_workspace_elems(B, T, C), dev)
+        sums = _doubles(3 * (B if per_example and stats is not None else 1) * C, dev)
+    _lib.call('ptmi_je_conv_apply_backward', dout.data_ptr(), zp, ldz, _lib.ptr(g), _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta),
+              _lib.ptr(lengths), is64, _lib.ptr(slope), dz.data_ptr(), _lib.ptr(dgz), _lib.ptr(dparams), _lib.ptr(ws), _lib.ptr(sums), B, T, C,
+              int(per_example), int(fixed_stats), act, act_p, _lib.stream(dev), timer='je_conv_apply_backward')
+    return dz, dgz, dparams
+
+
+@_register('je_pool_forward(Tensor x, int[] geom, bool max_pool) -> (Tensor, Tensor?)')
+def je_pool_forward(x, geom, max_pool):
+    """``(y [B T_out, C], index int64 or None)`` from ``x [B T_in, C]``; ``geom = (B, T_in, T_out, C, size, stride, front)``
+    (``ptmi_je_pool_forward``)."""
+    B, T_in, T_out, C = geom[:4]
+    xp, ldx = _jc_rows(x, C, 'x')
+    assert x.shape[0] == B * T_in
+    y = torch.empty((B * T_out, C), dtype=torch.float32, device=x.device)
+    index = torch.empty((B * T_out, C), dtype=torch.int64, device=x.device) if max_pool else None
+    _lib.call('ptmi_je_pool_forward', xp, y.data_ptr(), _lib.ptr(index), _lib.int64s(*geom, ldx), int(max_pool), _lib.stream(x.device),
+              timer='je_pool_forward')
+    return y, index
+
+
+@_register('je_pool_backward(Tensor dy, Tensor? index, int[] geom, bool max_pool) -> Tensor')
+def je_pool_backward(dy, index, geom, max_pool):
+    """``dx [B T_in, C]`` (``ptmi_je_pool_backward``)."""
+    B, T_in, T_out, C = geom[:4]
+    _f32c(dy)
+    assert tuple(dy.shape) == (B * T_out, C) and (index is None or (index.shape == dy.shape and index.is_contiguous() and index.dtype == torch.int64))
+    dx = torch.empty((B * T_in, C), dtype=torch.float32, device=dy.device)
+    _lib.call('ptmi_je_pool_backward', dy.data_ptr(), _lib.ptr(index), dx.data_ptr(), _lib.int64s(*geom, C), int(max_pool),
+              _lib.stream(dy.device), timer='je_pool_backward')
+    return dx
