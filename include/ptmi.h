@@ -1121,6 +1121,37 @@ int ptmi_je_conv_apply_backward(const float* dout, const float* z, int64_t ldz, 
 int ptmi_je_pool_forward(const float* x, float* y, int64_t* index, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 int ptmi_je_pool_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The 2-D convolution blocks and pools of conv.py / conv_utils.py (csrc/je_conv2d.hip): activations are channels-last [B, F, T, C]
+ * (row (b F + f) T + t), the convolution is direct on v_mfma_f32_16x16x32_f16 with fp16 hi / lo operands (a b = hi hi + hi lo + lo hi)
+ * scaled by the power of two of their absmax words (ptmi_absmax); no padded copy and no plane of tap products exist.
+ *
+ * geom [21] of pack / forward = (B, F_src, T_src, C_src, sources, zero insertion f, t, F_out, T_out, C_out, outputs, K_f, K_t, stride f,
+ *   t, dilation f, t, front pad f, t, ld of the sources, ld of the residual).  Forward: one source, zero insertion 1, outputs = 1, or 2
+ *   with a gate convolution.  Input gradient: sources dz (and dgz) [B, F_o, T_o, C_conv_out], zero insertion = the forward stride,
+ *   stride 1, front pad (K - 1) dilation - front, C_out = the forward's input channels, one output.
+ * ptmi_je_conv2d_pack_elems : uint16 elements of a layer's weight planes (0: a geometry the kernel does not take).
+ * ptmi_je_conv2d_pack    : the planes of w0 (and w1, the gate convolution's) [C_conv_out, C_conv_in, K_f, K_t] in fragment order, k order
+ *   (k_f, k_t, channel padded to 8); input_grad: taps flipped, k order (k_f, k_t, co).  amax: the word of max |w0|, |w1|.
+ * ptmi_je_conv2d_forward : z = bias + conv(x0 | x1) (positions outside the plane are zero), gz likewise; out != NULL:
+ *   out = act(z) sigmoid(gz) + residual in the same launch.  z, gz, out [B F_out T_out, C_out] contiguous.
+ * geom [17] of wgrad = (B, F_in, T_in, C_in, F_out, T_out, C_out, G, K_f, K_t, stride f, t, dilation f, t, front pad f, t, ld of x).
+ * ptmi_je_conv2d_wgrad   : dw [G, C_out, C_in, K_f, K_t] = sum over pixels of dz_q x (shifted); `slabs` workgroup ranges of pixel tiles
+ *   write workspace [slabs][G C_out C_in K_f K_t] floats, added in slab order.  No atomics.
+ * geom [13] of the pools = (B, F_in, T_in, F_out, T_out, C, size f, t, stride f, t, ld of x, front pad f, t).
+ * ptmi_je_pool2d_forward / _backward : as ptmi_je_pool_*; index = f T_p + t on the padded and trimmed plane, T_p = (T_out - 1) stride + size.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t ptmi_je_conv2d_pack_elems(const int64_t* geom);
+int ptmi_je_conv2d_pack(const float* w0, const float* w1, const uint32_t* amax, uint16_t* planes, const int64_t* geom, int32_t input_grad,
+                        ptmi_stream_t stream);
+int ptmi_je_conv2d_forward(const float* x0, const float* x1, const uint16_t* planes, const uint32_t* amax_x, const uint32_t* amax_w,
+                           const float* bias, const float* gate_bias, const float* residual, const float* slope, float* z, float* gz,
+                           float* out, const int64_t* geom, int32_t act, float act_p, ptmi_stream_t stream);
+int ptmi_je_conv2d_wgrad(const float* dz, const float* dgz, const float* x, const uint32_t* amax_dz, const uint32_t* amax_x,
+                         float* workspace, int64_t slabs, float* dw, const int64_t* geom, ptmi_stream_t stream);
+int ptmi_je_pool2d_forward(const float* x, float* y, int64_t* index, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
+int ptmi_je_pool2d_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

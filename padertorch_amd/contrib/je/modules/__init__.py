@@ -5,7 +5,11 @@ from . import reduce  # noqa: F401
 from . import rnn  # noqa: F401
 from . import conv  # noqa: F401
 from . import conv_utils  # noqa: F401
+from . import conv2d  # noqa: F401
+from . import hybrid  # noqa: F401
+from .hybrid import CNN, CRNN  # noqa: F401
 from .conv import CNN1d, Conv1d  # noqa: F401
+from .conv2d import CNN2d, Conv2d, Pool2d  # noqa: F401
 from .conv_utils import (Pad, Pool1d, Trim, compute_conv_output_sequence_lengths, compute_conv_output_shape,  # noqa: F401
                          compute_pad_size, map_activation_fn, to_list, to_pair)
 from .reduce import AutoPool, Max, Mean, Sum, TakeLast  # noqa: F401

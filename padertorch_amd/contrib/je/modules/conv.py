@@ -22,8 +22,8 @@ positions whose window holds it.  Pad with finite values (zeros), as every layer
 
 Not built (``NotImplementedError``, no library fallback): ``state`` / ``return_state`` (the streaming mode), CUDA-resident
 ``sequence_lengths``, ``get_transpose_config``, other activations or callables, a normalisation with ``shift=False`` or ``scale=False``, and
-the transposed and 2-D classes (``ConvTranspose1d``, ``Conv2d``, ``ConvTranspose2d``, ``CNNTranspose1d``, ``CNN2d``, ``CNNTranspose2d``,
-``Pool2d``, ``Unpool1d``, ``Unpool2d``, ``resnet50``, ``hybrid.py``), which are not defined here at all.
+the transposed classes (``ConvTranspose1d``, ``ConvTranspose2d``, ``CNNTranspose1d``, ``CNNTranspose2d``, ``Unpool1d``, ``Unpool2d``) and
+``resnet50``, which are not defined at all.  ``Conv2d``, ``CNN2d`` and ``Pool2d`` are in ``conv2d.py``, built on ``_Conv`` / ``_CNN`` here.
 """
 from copy import copy
 from typing import List
@@ -36,7 +36,7 @@ from torch import nn
 from ....modules.normalization import Normalization
 from ....ops import je_conv as _ops
 from .conv_utils import (LengthTable, Pool1d, _finalize_norm_kwargs, activation_code, compute_conv_output_sequence_lengths,
-                         compute_conv_output_shape, compute_pad_size, host_lengths, map_activation_fn, to_list)
+                         compute_conv_output_shape, compute_pad_size, host_lengths, map_activation_fn, to_list, to_pair)
 
 __all__ = ['Conv1d', 'CNN1d']
 
@@ -72,15 +72,19 @@ def _norm_act(norm, activation_fn, x, lengths, table):
     return _ops.unrows(out, B, T)
 
 
-class Conv1d(nn.Module):
-    """``torch.nn.Conv1d`` with padding, an optional gate convolution, normalisation and activation of its output (or, ``pre_activation``,
-    of its input) - one fused block of ``ops.je_conv``."""
+class _Conv(nn.Module):
+    """``torch_cls`` (``torch.nn.Conv1d`` / ``Conv2d``) with padding, an optional gate convolution, normalisation and activation of its
+    output (or, ``pre_activation``, of its input) - one fused block of ``ops.je_conv`` (``Conv1d``) or ``ops.je_conv2d`` (``Conv2d`` in
+    ``conv2d.py``, which brings its own ``forward``).  With ``is_2d()`` the geometry arguments are scalars or pairs ``(f, t)``."""
+    torch_cls = nn.Conv1d
 
     def __init__(self, in_channels, out_channels, kernel_size, dropout=0., pad_type='both', dilation=1, stride=1, bias=True, norm=None,
                  norm_kwargs=None, activation_fn='relu', pre_activation=False, gated=False, return_state=False):
         super().__init__()
         if return_state:
-            raise NotImplementedError('Conv1d: return_state (the streaming mode) is not built')
+            raise NotImplementedError(f'{type(self).__name__}: return_state (the streaming mode) is not built')
+        if self.is_2d():
+            pad_type, kernel_size, dilation, stride = to_pair(pad_type), to_pair(kernel_size), to_pair(dilation), to_pair(stride)
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.bias = bias
@@ -93,15 +97,15 @@ class Conv1d(nn.Module):
         self.pre_activation = pre_activation
         self.gated = gated
         self.return_state = return_state
-        self.conv = nn.Conv1d(in_channels, out_channels, kernel_size=kernel_size, dilation=dilation, stride=stride, bias=bias)
+        self.conv = self.torch_cls(in_channels, out_channels, kernel_size=kernel_size, dilation=dilation, stride=stride, bias=bias)
         if self.gated:
-            self.gate_conv = nn.Conv1d(in_channels, out_channels, kernel_size=kernel_size, dilation=dilation, stride=stride, bias=bias)
+            self.gate_conv = self.torch_cls(in_channels, out_channels, kernel_size=kernel_size, dilation=dilation, stride=stride, bias=bias)
         if norm is None:
             self.norm = None
             assert norm_kwargs is None, norm_kwargs
         else:
             num_channels = self.in_channels if self.pre_activation else self.out_channels
-            self.norm = Normalization(**_finalize_norm_kwargs({} if norm_kwargs is None else norm_kwargs, norm, num_channels, False))
+            self.norm = Normalization(**_finalize_norm_kwargs({} if norm_kwargs is None else norm_kwargs, norm, num_channels, self.is_2d()))
             _norm_operands(self.norm)                           # (refuses shift=False / scale=False here, not in the first call)
 
     @classmethod
@@ -110,7 +114,7 @@ class Conv1d(nn.Module):
 
     @classmethod
     def is_2d(cls):
-        return False
+        return cls.torch_cls is nn.Conv2d
 
     def reset_parameters(self, output_activation_fn):
         if isinstance(self.activation_fn, nn.PReLU):
@@ -140,7 +144,7 @@ class Conv1d(nn.Module):
 
     def forward(self, x, sequence_lengths=None, state=None, *, _table=None, _residual=None):
         if state is not None:
-            raise NotImplementedError('Conv1d: state (the streaming mode) is not built')
+            raise NotImplementedError(f'{type(self).__name__}: state (the streaming mode) is not built')
         if self.training and self.dropout > 0.:
             x = F.dropout(x, self.dropout)
         r, B, T = _ops.rows(x)
@@ -167,20 +171,20 @@ class Conv1d(nn.Module):
         return _ops.unrows(y, B, T_out), out_lengths
 
     def get_output_shape(self, input_shape):
-        assert len(input_shape) == 3, len(input_shape)
+        assert len(input_shape) == 3 + self.is_2d(), len(input_shape)
         assert input_shape[1] == self.in_channels, (input_shape[1], self.in_channels)
         return compute_conv_output_shape(input_shape, out_channels=self.out_channels, kernel_size=self.kernel_size, dilation=self.dilation,
                                          pad_type=self.pad_type, stride=self.stride, transpose=False)
 
     def get_input_shape(self, output_shape):
-        assert len(output_shape) == 3, len(output_shape)
+        assert len(output_shape) == 3 + self.is_2d(), len(output_shape)
         assert output_shape[1] == self.out_channels, (output_shape[1], self.out_channels)
         return compute_conv_output_shape(output_shape, out_channels=self.in_channels, kernel_size=self.kernel_size, dilation=self.dilation,
                                          pad_type=self.pad_type, stride=self.stride, transpose=True)
 
     def get_output_sequence_lengths(self, input_sequence_lengths, state=None):
         if state is not None:
-            raise NotImplementedError('Conv1d: state (the streaming mode) is not built')
+            raise NotImplementedError(f'{type(self).__name__}: state (the streaming mode) is not built')
         input_sequence_lengths = np.array(input_sequence_lengths)
         assert input_sequence_lengths.ndim == 1, input_sequence_lengths.ndim
         return compute_conv_output_sequence_lengths(input_sequence_lengths, kernel_size=self.kernel_size, dilation=self.dilation,
@@ -193,9 +197,16 @@ class Conv1d(nn.Module):
                                                     stride=self.stride, pad_type=self.pad_type, transpose=True)
 
 
-class CNN1d(nn.Module):
-    """A stack of ``Conv1d`` blocks with residual and dense connections and pooling (the reference's ``CNN1d``)."""
+class Conv1d(_Conv):
+    torch_cls = nn.Conv1d
+
+
+class _CNN(nn.Module):
+    """A stack of ``conv_cls`` blocks with residual and dense connections and pooling (the reference's ``_CNN``): ``CNN1d`` here, ``CNN2d``
+    in ``conv2d.py``.  What differs between them are the hooks ``pool_cls``, ``_norm_act``, ``_add`` and ``_all_lengths``."""
     conv_cls = Conv1d
+    pool_cls = Pool1d
+    _norm_act = staticmethod(_norm_act)
 
     def __init__(self, in_channels, out_channels: List[int], kernel_size, input_layer=True, output_layer=True, residual_connections=None,
                  dense_connections=None, dropout=0., pad_type='both', dilation=1, stride=1, norm=None, norm_kwargs=None,
@@ -203,7 +214,7 @@ class CNN1d(nn.Module):
                  return_pool_indices=False, return_state=False, normalize_skip_convs=False):
         super().__init__()
         if return_state:
-            raise NotImplementedError('CNN1d: return_state (the streaming mode) is not built')
+            raise NotImplementedError(f'{type(self).__name__}: return_state (the streaming mode) is not built')
         self.in_channels = in_channels
         self.out_channels = copy(out_channels)
         num_layers = len(out_channels)
@@ -264,11 +275,11 @@ class CNN1d(nn.Module):
 
         self.input_norm = self.input_activation_fn = self.output_norm = self.output_activation_fn = None
         if self.norm[0] is not None and not pre_activation:
-            kwargs = _finalize_norm_kwargs({} if norm_kwargs is None else norm_kwargs, self.norm[0], self.in_channels, False)
+            kwargs = _finalize_norm_kwargs({} if norm_kwargs is None else norm_kwargs, self.norm[0], self.in_channels, self.is_2d())
             self.input_norm = Normalization(**kwargs)
             self.input_activation_fn = map_activation_fn(self.activation_fn[0])
         if self.norm[-1] is not None and pre_activation:
-            kwargs = _finalize_norm_kwargs({} if norm_kwargs is None else norm_kwargs, self.norm[-1], layer_in_channels[-1], False)
+            kwargs = _finalize_norm_kwargs({} if norm_kwargs is None else norm_kwargs, self.norm[-1], layer_in_channels[-1], self.is_2d())
             self.output_norm = Normalization(**kwargs)
             self.output_activation_fn = map_activation_fn(self.activation_fn[-1])
         self.reset_parameters()
@@ -279,7 +290,12 @@ class CNN1d(nn.Module):
 
     @classmethod
     def is_2d(cls):
-        return False
+        return cls.conv_cls.is_2d()
+
+    @staticmethod
+    def _add(x, x_):
+        a, B, T = _ops.rows(x)
+        return _ops.unrows(_ops.add(a, _ops.rows(x_)[0], B, T), B, T)
 
     def reset_parameters(self):
         for fn in (self.input_activation_fn, self.output_activation_fn):
@@ -315,7 +331,7 @@ class CNN1d(nn.Module):
             if isinstance(self.output_activation_fn, nn.PReLU):
                 self.output_activation_fn.weight.requires_grad = False
 
-    def _all_lengths(self, lengths):
+    def _all_lengths(self, lengths, shape):
         """Every length vector the call will meet: the input's and, per layer, behind the convolution and behind the pool."""
         out = [lengths]
         for i, conv in enumerate(self.convs):
@@ -327,26 +343,26 @@ class CNN1d(nn.Module):
         return out
 
     def forward(self, x, sequence_lengths=None, target_shape=None, target_sequence_lengths=None, pool_indices=None, state=None):
-        assert x.dim() == 3, x.shape
+        assert x.dim() == 3 + self.is_2d(), (x.shape, self.is_2d())
         if state is not None:
-            raise NotImplementedError('CNN1d: state (the streaming mode) is not built')
+            raise NotImplementedError(f'{type(self).__name__}: state (the streaming mode) is not built')
         assert target_shape is None, target_shape
         assert target_sequence_lengths is None, target_sequence_lengths
         assert pool_indices is None, pool_indices
         sequence_lengths = host_lengths(sequence_lengths)
-        table = LengthTable(x.device, [] if sequence_lengths is None else self._all_lengths(sequence_lengths))
+        table = LengthTable(x.device, [] if sequence_lengths is None else self._all_lengths(sequence_lengths, x.shape))
         pool_indices = [None] * self.num_layers
         skip_signals = []
         for i, conv in enumerate(self.convs):
             if i == 0 and self.input_norm is not None:
-                x = _norm_act(self.input_norm, self.input_activation_fn, x, sequence_lengths, table)
+                x = self._norm_act(self.input_norm, self.input_activation_fn, x, sequence_lengths, table)
             skip_signals.append(x if self.residual_connections[i] + self.dense_connections[i] else None)
             # the skip signals follow this layer's stride; none of that depends on the layer's output, so it comes first and the first
             # residual connection that ends here is the convolution's own residual operand
-            if self.strides[i] > 1:
+            if any(np.array(to_list(self.strides[i])) > 1):
                 for src_idx, x_ in enumerate(skip_signals):
                     if x_ is not None:
-                        skip_signals[src_idx] = Pool1d('avg', self.strides[i], pad_type=self.pad_types[i])(x_)[0]
+                        skip_signals[src_idx] = self.pool_cls('avg', self.strides[i], pad_type=self.pad_types[i])(x_)[0]
             has_dense = any(x_ is not None and i + 1 in self.dense_connections[src] for src, x_ in enumerate(skip_signals))
             residuals = []
             for src_idx, x_ in enumerate(skip_signals):
@@ -358,26 +374,25 @@ class CNN1d(nn.Module):
             x, sequence_lengths = conv(x, sequence_lengths=sequence_lengths, _table=table, _residual=fused)
             for src_idx, x_ in enumerate(skip_signals):
                 if x_ is not None and i + 1 in self.dense_connections[src_idx]:
-                    size = x_.shape[2] - x.shape[2]
-                    assert size >= 0, size
-                    x = torch.cat((x, x_[..., :x.shape[2]]), dim=1)
+                    size = np.array(x_.shape[2:]) - np.array(x.shape[2:])
+                    assert all(size >= 0), size
+                    x = torch.cat((x, x_[(..., *[slice(0, n) for n in x.shape[2:]])]), dim=1)
             for x_ in residuals:
                 assert x_.shape == x.shape, (x_.shape, x.shape)
-                a, B, T = _ops.rows(x)
-                x = _ops.unrows(_ops.add(a, _ops.rows(x_)[0], B, T), B, T)
+                x = self._add(x, x_)
             for src_idx in range(len(skip_signals)):
                 destinations = self.dense_connections[src_idx] + self.residual_connections[src_idx]
                 if destinations and max(destinations) <= i + 1:
                     skip_signals[src_idx] = None
             if i == self.num_layers - 1 and self.output_norm is not None:
-                x = _norm_act(self.output_norm, self.output_activation_fn, x, sequence_lengths, table)
-            if self.pool_sizes[i] > 1:
+                x = self._norm_act(self.output_norm, self.output_activation_fn, x, sequence_lengths, table)
+            if any(np.array(to_list(self.pool_sizes[i])) > 1):
                 assert self.pool_types[i] is not None
-                x, sequence_lengths, pool_indices[i] = Pool1d(self.pool_types[i], self.pool_sizes[i], self.pool_strides[i],
-                                                              self.pad_types[i])(x, sequence_lengths)
+                x, sequence_lengths, pool_indices[i] = self.pool_cls(self.pool_types[i], self.pool_sizes[i], self.pool_strides[i],
+                                                                     self.pad_types[i])(x, sequence_lengths)
                 for src_idx, x_ in enumerate(skip_signals):
                     if x_ is not None:
-                        skip_signals[src_idx] = Pool1d('avg', self.pool_strides[i], pad_type=self.pad_types[i])(x_)[0]
+                        skip_signals[src_idx] = self.pool_cls('avg', self.pool_strides[i], pad_type=self.pad_types[i])(x_)[0]
         outputs = [x, sequence_lengths]
         if self.return_pool_indices:
             outputs.append(pool_indices)
@@ -385,7 +400,7 @@ class CNN1d(nn.Module):
 
     @classmethod
     def get_transpose_config(cls, config, transpose_config=None):
-        raise NotImplementedError('CNN1d.get_transpose_config: the transposed stack (CNNTranspose1d) is not built')
+        raise NotImplementedError(f'{cls.__name__}.get_transpose_config: the transposed stack is not built')
 
     def get_shapes(self, input_shape=None, target_shape=None):
         assert (input_shape is None) ^ (target_shape is None), (input_shape, target_shape)
@@ -422,10 +437,14 @@ class CNN1d(nn.Module):
         return seq_lens if forward else seq_lens[::-1]
 
     def get_receptive_field(self):
-        receptive_field = np.ones(1).astype(int)
+        receptive_field = np.ones(1 + self.is_2d()).astype(int)
         for i in reversed(range(self.num_layers)):
             receptive_field *= np.array(self.pool_strides[i])
             receptive_field += np.array(self.pool_sizes[i]) - np.array(self.pool_strides[i])
             receptive_field *= np.array(self.strides[i])
             receptive_field += 1 + (np.array(self.kernel_sizes[i]) - 1) * self.dilations[i] - np.array(self.strides[i])
         return receptive_field
+
+
+class CNN1d(_CNN):
+    conv_cls = Conv1d

@@ -4,9 +4,10 @@
 
 ``Pool1d`` runs on the pool kernels of ``csrc/je_conv.hip`` (``ops.je_conv.pool``): its padding and the trailing trim are index
 arithmetic there, the indices of max pooling count on the padded axis as ``nn.MaxPool1d(return_indices=True)`` gives them behind
-``Pad`` / ``Trim``.  ``Pad`` (``mode='constant'`` only) and ``Trim`` are views / one ``F.pad``: the convolution blocks never call them.
+``Pad`` / ``Trim``.  ``Pad`` (``mode='constant'`` only) and ``Trim`` are views / one ``F.pad`` on ``[B, C, T]`` or ``[B, C, F, T]``: the
+convolution blocks never call them.  ``Pool2d`` lives in ``conv2d.py`` beside the 2-D blocks.
 
-Not built: ``Pool2d``, ``Unpool1d``, ``Unpool2d``.
+Not built: ``Unpool1d``, ``Unpool2d``.
 """
 import math
 
@@ -64,31 +65,38 @@ def _split(side, size):
 
 
 class Pad(nn.Module):
-    """Pads the time axis of ``x [B, C, T]`` by ``size`` zeros in front, at the end, or split between both."""
+    """Pads the last axis of ``x [B, C, T]``, or the last two of ``x [B, C, F, T]`` (``size``: a pair), by ``size`` zeros in front, at
+    the end, or split between both."""
     def __init__(self, side='both', mode='constant'):
         super().__init__()
         self.side = side
         self.mode = mode
 
     def forward(self, x, size):
-        assert x.dim() == 3, x.shape
-        size, = to_list(size, 1)
-        if not size:
+        assert x.dim() in (3, 4), x.shape
+        sizes, sides = to_list(size, x.dim() - 2), to_list(self.side, x.dim() - 2)
+        if not any(sizes):
             return x
-        return F.pad(x, list(_split(self.side, int(size))), mode=self.mode)
+        pad = []
+        for side, n in reversed(list(zip(sides, sizes))):           # F.pad counts from the last axis
+            pad += list(_split(side, int(n)) if n else (0, 0))
+        return F.pad(x, pad, mode=self.mode)
 
 
 class Trim(nn.Module):
-    """The counterpart of ``Pad``: removes ``size`` positions of the time axis."""
+    """The counterpart of ``Pad``: removes ``size`` positions of the last axis (``[B, C, T]``) or axes (``[B, C, F, T]``)."""
     def __init__(self, side='both'):
         super().__init__()
         self.side = side
 
     def forward(self, x, size):
-        assert x.dim() == 3, x.shape
-        size, = to_list(size, 1)
-        front, end = _split(self.side, int(size))
-        return x[..., front:x.shape[-1] - end]
+        assert x.dim() in (3, 4), x.shape
+        sizes, sides = to_list(size, x.dim() - 2), to_list(self.side, x.dim() - 2)
+        index = [slice(None)] * x.dim()
+        for axis, (side, n) in enumerate(zip(sides, sizes), 2):
+            front, end = _split(side, int(n)) if n else (0, 0)
+            index[axis] = slice(front, x.shape[axis] - end)
+        return x[tuple(index)]
 
 
 def compute_pad_size(kernel_size, dilation, stride, pad_type):
@@ -214,8 +222,9 @@ class LengthTable:
         vectors = [v for v in vectors if v is not None]
         if vectors:
             from .... import _lib
-            dev = _lib.host_to_device(np.stack(vectors), torch.int64, device)
-            self.rows = {tuple(v.tolist()): dev[i] for i, v in enumerate(vectors)}
+            dev = _lib.host_to_device(np.concatenate(vectors), torch.int64, device)       # (the vectors of a 2-D stack differ in size)
+            ends = np.cumsum([len(v) for v in vectors])
+            self.rows = {tuple(v.tolist()): dev[e - len(v):e] for v, e in zip(vectors, ends)}
 
     def get(self, lengths):
         if lengths is None:

@@ -94,24 +94,24 @@ struct StoreDepthwise {
 };
 
 // store(j, sum_s ws[s][j]) for j < width: four chains s = g, g + 4, ... (ascending), combined ((0 + 1) + 2) + 3.
-// Grid: (width + 63) / 64 workgroups of 256 threads.
-template <class Store>
-static __global__ __launch_bounds__(256) void colreduce_kernel(const double* __restrict__ ws, long long slabs, long long width,
+// Grid: (width + 63) / 64 workgroups of 256 threads.  The slabs hold doubles or (S = float) single-precision partials; the sum is fp64.
+template <class Store, class S = double>
+static __global__ __launch_bounds__(256) void colreduce_kernel(const S* __restrict__ ws, long long slabs, long long width,
                                                                const Store store) {
     __shared__ double red[4][64];
     const int jx = threadIdx.x & 63, g = threadIdx.x >> 6;
     const long long j = (long long)blockIdx.x * 64 + jx;
     double s = 0.;
     if (j < width)
-        for (long long sl = g; sl < slabs; sl += 4) s += ws[sl * width + j];
+        for (long long sl = g; sl < slabs; sl += 4) s += (double)ws[sl * width + j];
     red[g][jx] = s;
     __syncthreads();
     if (g == 0 && j < width) store(j, ((red[0][jx] + red[1][jx]) + red[2][jx]) + red[3][jx]);
 }
 
-template <class Store>
-inline int colreduce(const double* ws, long long slabs, long long width, Store store, hipStream_t st) {
-    hipLaunchKernelGGL(colreduce_kernel<Store>, dim3((unsigned)((width + 63) / 64)), dim3(256), 0, st, ws, slabs, width, store);
+template <class Store, class S = double>
+inline int colreduce(const S* ws, long long slabs, long long width, Store store, hipStream_t st) {
+    hipLaunchKernelGGL((colreduce_kernel<Store, S>), dim3((unsigned)((width + 63) / 64)), dim3(256), 0, st, ws, slabs, width, store);
     return launch_status();
 }
 

@@ -47,6 +47,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                    ptmi_chunk_gru_*, ptmi_seq_*   (contrib/je/modules/rnn.py, reduce.py)
     torch.ops.ptmi.je_conv_taps / je_conv_dtaps / je_conv_stats / je_conv_apply / je_conv_apply_backward, je_pool_forward / _backward
                                                    ptmi_je_conv_*, ptmi_je_pool_*   (contrib/je/modules/conv.py, conv_utils.py)
+    torch.ops.ptmi.je_conv2d_pack / je_conv2d_forward / je_conv2d_wgrad, je_pool2d_forward / _backward
+                                                   ptmi_je_conv2d_*, ptmi_je_pool2d_*   (Conv2d, CNN2d, Pool2d)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1950,4 +1952,87 @@ def je_pool_backward(dy, index, geom, max_pool):
     dx = torch.empty((B * T_in, C), dtype=torch.float32, device=dy.device)
     _lib.call('ptmi_je_pool_backward', dy.data_ptr(), _lib.ptr(index), dx.data_ptr(), _lib.int64s(*geom, C), int(max_pool),
               _lib.stream(dy.device), timer='je_pool_backward')
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------ contrib/je 2-D convolution blocks (csrc/je_conv2d.hip)
+@_register('je_conv2d_pack(Tensor w0, Tensor? w1, Tensor amax, int[] geom, bool input_grad) -> Tensor')
+def je_conv2d_pack(w0, w1, amax, geom, input_grad):
+    """The fp16 hi / lo planes of the weights ``[C_out, C_in, K_f, K_t]`` in fragment order for the launch ``geom`` describes (the 19
+    geometry values of ``ptmi_je_conv2d_forward``) (``ptmi_je_conv2d_pack``)."""
+    _f32c(w0, w1)
+    g = _lib.int64s(*geom, geom[3], geom[9])
+    elems = _lib.load().ptmi_je_conv2d_pack_elems(g)
+    if elems < 1:
+        raise NotImplementedError(f'je_conv2d: the halo of this geometry does not fit the LDS of a workgroup: {list(geom)}')
+    planes = torch.empty(elems, dtype=torch.int16, device=w0.device)
+    _lib.call('ptmi_je_conv2d_pack', w0.data_ptr(), _lib.ptr(w1), amax.data_ptr(), planes.data_ptr(), g, int(input_grad),
+              _lib.stream(w0.device), timer='je_conv2d_pack')
+    return planes
+
+
+@_register('je_conv2d_forward(Tensor x0, Tensor? x1, Tensor planes, Tensor amax_x, Tensor amax_w, Tensor? bias, Tensor? gate_bias, '
+           'Tensor? residual, Tensor? slope, int[] geom, int act, float act_p, bool fused) -> (Tensor, Tensor?, Tensor?)')
+def je_conv2d_forward(x0, x1, planes, amax_x, amax_w, bias, gate_bias, residual, slope, geom, act, act_p, fused):
+    """``(z, gz or None, out or None) [B F_out T_out, C_out]`` of the direct convolution of the rows ``x0`` (and ``x1``)
+    ``[B F_src T_src, C_src]``; ``geom``: the first 19 values of ``ptmi_je_conv2d_forward``'s."""
+    B, SF, ST, Cs, NS = geom[:5]
+    OF, OT, Co, NQ = geom[7:11]
+    xp, lds = _jc_rows(x0, Cs, 'x0')
+    assert x0.shape[0] == B * SF * ST and (NS == 1) == (x1 is None), (x0.shape, geom)
+    if x1 is not None:
+        x1p, ld1 = _jc_rows(x1, Cs, 'x1')
+        assert ld1 == lds and x1.shape == x0.shape
+    _f32c(bias, gate_bias, slope)
+    assert all(b is None or b.numel() == Co for b in (bias, gate_bias))
+    rp, ldr = (None, Co) if residual is None else _jc_rows(residual, Co, 'residual')
+    assert residual is None or residual.shape[0] == B * OF * OT
+    dev = x0.device
+    z = torch.empty((B * OF * OT, Co), dtype=torch.float32, device=dev)
+    gz = torch.empty_like(z) if NQ == 2 else None
+    out = torch.empty_like(z) if fused else None
+    _lib.call('ptmi_je_conv2d_forward', xp, _lib.ptr(x1), planes.data_ptr(), amax_x.data_ptr(), amax_w.data_ptr(), _lib.ptr(bias),
+              _lib.ptr(gate_bias), rp, _lib.ptr(slope), z.data_ptr(), _lib.ptr(gz), _lib.ptr(out), _lib.int64s(*geom, lds, ldr), act, act_p,
+              _lib.stream(dev), timer='je_conv2d_forward')
+    return z, gz, out
+
+
+@_register('je_conv2d_wgrad(Tensor dz, Tensor? dgz, Tensor x, Tensor amax_dz, Tensor amax_x, int[] geom, int slabs) -> Tensor')
+def je_conv2d_wgrad(dz, dgz, x, amax_dz, amax_x, geom, slabs):
+    """``dw [G, C_out, C_in, K_f, K_t]`` from ``dz`` / ``dgz [B F_out T_out, C_out]`` and ``x [B F_in T_in, C_in]``; ``geom``: the first
+    16 values of ``ptmi_je_conv2d_wgrad``'s; ``slabs`` ranges of pixel tiles are summed in order."""
+    B, IF, IT, Ci, OF, OT, Co, G, KF, KT = geom[:10]
+    _f32c(dz, dgz)
+    xp, ldx = _jc_rows(x, Ci, 'x')
+    assert tuple(dz.shape) == (B * OF * OT, Co) and (G == 1 or dgz.shape == dz.shape) and x.shape[0] == B * IF * IT, (dz.shape, x.shape, geom)
+    dw = torch.empty((G, Co, Ci, KF, KT), dtype=torch.float32, device=dz.device)
+    ws = torch.empty(slabs * dw.numel(), dtype=torch.float32, device=dz.device)
+    _lib.call('ptmi_je_conv2d_wgrad', dz.data_ptr(), _lib.ptr(dgz), xp, amax_dz.data_ptr(), amax_x.data_ptr(), ws.data_ptr(), slabs,
+              dw.data_ptr(), _lib.int64s(*geom, ldx), _lib.stream(dz.device), timer='je_conv2d_wgrad')
+    return dw
+
+
+@_register('je_pool2d_forward(Tensor x, int[] geom, bool max_pool) -> (Tensor, Tensor?)')
+def je_pool2d_forward(x, geom, max_pool):
+    """``(y [B F_out T_out, C], index int64 or None)`` from ``x [B F_in T_in, C]``; ``geom = (B, F_in, T_in, F_out, T_out, C, size f, t,
+    stride f, t, front f, t)`` (``ptmi_je_pool2d_forward``)."""
+    B, IF, IT, OF, OT, C = geom[:6]
+    xp, ldx = _jc_rows(x, C, 'x')
+    assert x.shape[0] == B * IF * IT
+    y = torch.empty((B * OF * OT, C), dtype=torch.float32, device=x.device)
+    index = torch.empty((B * OF * OT, C), dtype=torch.int64, device=x.device) if max_pool else None
+    _lib.call('ptmi_je_pool2d_forward', xp, y.data_ptr(), _lib.ptr(index), _lib.int64s(*geom[:10], ldx, *geom[10:]), int(max_pool),
+              _lib.stream(x.device), timer='je_pool2d_forward')
+    return y, index
+
+
+@_register('je_pool2d_backward(Tensor dy, Tensor? index, int[] geom, bool max_pool) -> Tensor')
+def je_pool2d_backward(dy, index, geom, max_pool):
+    """``dx [B F_in T_in, C]`` (``ptmi_je_pool2d_backward``)."""
+    B, IF, IT, OF, OT, C = geom[:6]
+    _f32c(dy)
+    assert tuple(dy.shape) == (B * OF * OT, C) and (index is None or (index.shape == dy.shape and index.is_contiguous() and index.dtype == torch.int64))
+    dx = torch.empty((B * IF * IT, C), dtype=torch.float32, device=dy.device)
+    _lib.call('ptmi_je_pool2d_backward', dy.data_ptr(), _lib.ptr(index), dx.data_ptr(), _lib.int64s(*geom[:10], C, *geom[10:]), int(max_pool),
+              _lib.stream(dy.device), timer='je_pool2d_backward')
     return dx
