@@ -1138,6 +1138,8 @@ int ptmi_je_pool_backward(const float* dy, const int64_t* index, float* dx, cons
  * geom [17] of wgrad = (B, F_in, T_in, C_in, F_out, T_out, C_out, G, K_f, K_t, stride f, t, dilation f, t, front pad f, t, ld of x).
  * ptmi_je_conv2d_wgrad   : dw [G, C_out, C_in, K_f, K_t] = sum over pixels of dz_q x (shifted); `slabs` workgroup ranges of pixel tiles
  *   write workspace [slabs][G C_out C_in K_f K_t] floats, added in slab order.  No atomics.
+ * ptmi_je_conv2d_wgrad_lds : bytes of LDS a workgroup of ptmi_je_conv2d_wgrad stages for geom [17] (0: a geometry it does not take and
+ *   answers with PTMI_E_UNSUPPORTED); asked in the forward of a layer whose weights are trained.
  * geom [13] of the pools = (B, F_in, T_in, F_out, T_out, C, size f, t, stride f, t, ld of x, front pad f, t).
  * ptmi_je_pool2d_forward / _backward : as ptmi_je_pool_*; index = f T_p + t on the padded and trimmed plane, T_p = (T_out - 1) stride + size.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -1149,6 +1151,7 @@ int ptmi_je_conv2d_forward(const float* x0, const float* x1, const uint16_t* pla
                            float* out, const int64_t* geom, int32_t act, float act_p, ptmi_stream_t stream);
 int ptmi_je_conv2d_wgrad(const float* dz, const float* dgz, const float* x, const uint32_t* amax_dz, const uint32_t* amax_x,
                          float* workspace, int64_t slabs, float* dw, const int64_t* geom, ptmi_stream_t stream);
+int64_t ptmi_je_conv2d_wgrad_lds(const int64_t* geom);
 int ptmi_je_pool2d_forward(const float* x, float* y, int64_t* index, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 int ptmi_je_pool2d_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 

@@ -475,6 +475,29 @@ static bool c2_geom(const int64_t* g, C2Geom& G) {
 
 static long long c2_pack_chunks(const C2Geom& G) { return (long long)G.tiles_n * G.NCH * G.KS * 8 * 64; }
 
+// The geometry of a weight-gradient launch from geom [17] (ptmi.h): the launch's dynamic LDS in bytes; 0: a shape the kernel does not
+// take (the transposed dz tile and the halo of the input channels of 64 columns beyond kC2WgradLdsLimit); -1: not a geometry.
+static long long c2_wgrad_plan(const int64_t* geom, C2Wgrad& A) {
+    if (!geom) return -1;
+    for (int i = 0; i < 17; ++i)
+        if (geom[i] < (i == 14 || i == 15 ? 0 : 1) || geom[i] > 0x3fffffff) return -1;
+    A.B = geom[0], A.IF = (int)geom[1], A.IT = (int)geom[2], A.Ci = (int)geom[3], A.OF = (int)geom[4], A.OT = (int)geom[5];
+    A.Co = (int)geom[6], A.NQ = (int)geom[7], A.KF = (int)geom[8], A.KT = (int)geom[9], A.sf = (int)geom[10], A.st = (int)geom[11];
+    A.df = (int)geom[12], A.dt = (int)geom[13], A.ff = (int)geom[14], A.ft = (int)geom[15], A.ldx = geom[16];
+    if (A.NQ > 2 || A.KF > 64 || A.KT > 64 || A.ldx < A.Ci) return -1;
+    const long long hf = (long long)(kC2TileF - 1) * A.sf + (long long)(A.KF - 1) * A.df + 1;
+    const long long ht = (long long)(kC2TileT - 1) * A.st + (long long)(A.KT - 1) * A.dt + 1;
+    const long long taps = (long long)A.KF * A.KT, M = (long long)A.NQ * A.Co, N = A.Ci * taps;
+    long long nci = (62 + taps) / taps + 1;             // the input channels 64 neighbouring columns ci taps + tap can touch
+    if (nci > A.Ci) nci = A.Ci;
+    const long long lds = 2 * 64 * kC2DzPitch * 2 + 2 * nci * hf * ht * 2;
+    if (hf * ht > 8192 || lds > kC2WgradLdsLimit || M * N > 0x7fffffffLL || (N + 63) / 64 > 65535) return 0;
+    A.HF = (int)hf, A.HT = (int)ht, A.HP = (int)(hf * ht);
+    A.tiles_f = (A.OF + kC2TileF - 1) / kC2TileF, A.tiles_t = (A.OT + kC2TileT - 1) / kC2TileT;
+    A.tiles = A.B * A.tiles_f * A.tiles_t;
+    return lds;
+}
+
 }  // namespace ptmi
 
 using namespace ptmi;
@@ -484,6 +507,12 @@ extern "C" {
 int64_t ptmi_je_conv2d_pack_elems(const int64_t* geom) {
     C2Geom G;
     return c2_geom(geom, G) ? c2_pack_chunks(G) * 8 : 0;
+}
+
+int64_t ptmi_je_conv2d_wgrad_lds(const int64_t* geom) {
+    C2Wgrad A;
+    const long long lds = c2_wgrad_plan(geom, A);
+    return lds > 0 ? lds : 0;
 }
 
 int ptmi_je_conv2d_pack(const float* w0, const float* w1, const uint32_t* amax, uint16_t* planes, const int64_t* geom, int32_t input_grad,
@@ -526,30 +555,18 @@ int ptmi_je_conv2d_forward(const float* x0, const float* x1, const uint16_t* pla
 int ptmi_je_conv2d_wgrad(const float* dz, const float* dgz, const float* x, const uint32_t* amax_dz, const uint32_t* amax_x,
                          float* workspace, int64_t slabs, float* dw, const int64_t* geom, ptmi_stream_t stream) {
     PTMI_RETURN_IF(!dz || !x || !amax_dz || !amax_x || !workspace || !dw || !geom || slabs < 1 || slabs > 65535, PTMI_E_INVALID);
-    for (int i = 0; i < 17; ++i) PTMI_RETURN_IF(geom[i] < (i == 14 || i == 15 ? 0 : 1) || geom[i] > 0x3fffffff, PTMI_E_INVALID);
     C2Wgrad A;
+    const long long lds = c2_wgrad_plan(geom, A);
+    PTMI_RETURN_IF(lds < 0 || (A.NQ == 2 && !dgz), PTMI_E_INVALID);
+    PTMI_RETURN_IF(lds == 0, PTMI_E_UNSUPPORTED);
     A.dz[0] = dz, A.dz[1] = dgz, A.x = x, A.ws = workspace, A.amax_dz = amax_dz, A.amax_x = amax_x;
-    A.B = geom[0], A.IF = (int)geom[1], A.IT = (int)geom[2], A.Ci = (int)geom[3], A.OF = (int)geom[4], A.OT = (int)geom[5];
-    A.Co = (int)geom[6], A.NQ = (int)geom[7], A.KF = (int)geom[8], A.KT = (int)geom[9], A.sf = (int)geom[10], A.st = (int)geom[11];
-    A.df = (int)geom[12], A.dt = (int)geom[13], A.ff = (int)geom[14], A.ft = (int)geom[15], A.ldx = geom[16];
-    PTMI_RETURN_IF(A.NQ > 2 || (A.NQ == 2 && !dgz) || A.KF > 64 || A.KT > 64 || A.ldx < A.Ci, PTMI_E_INVALID);
-    const long long hf = (long long)(kC2TileF - 1) * A.sf + (long long)(A.KF - 1) * A.df + 1;
-    const long long ht = (long long)(kC2TileT - 1) * A.st + (long long)(A.KT - 1) * A.dt + 1;
-    const long long taps = (long long)A.KF * A.KT, M = (long long)A.NQ * A.Co, N = A.Ci * taps;
-    long long nci = (62 + taps) / taps + 1;             // the input channels 64 neighbouring columns ci taps + tap can touch
-    if (nci > A.Ci) nci = A.Ci;
-    const long long lds = 2 * 64 * kC2DzPitch * 2 + 2 * nci * hf * ht * 2;
-    PTMI_RETURN_IF(hf * ht > 8192 || lds > kC2WgradLdsLimit || M * N > 0x7fffffffLL, PTMI_E_UNSUPPORTED);
     // a 1 x 1 layer with 64 or more input channels needs 66 KB (34 KB of dz, 32 KB of input): beyond what a launch gets unasked
     static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(je_conv2d_wgrad_kernel),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, kC2WgradLdsLimit);
     PTMI_RETURN_IF(lds > kC2LdsLimit && raised != hipSuccess, PTMI_E_UNSUPPORTED);
-    A.HF = (int)hf, A.HT = (int)ht, A.HP = (int)(hf * ht);
-    A.tiles_f = (A.OF + kC2TileF - 1) / kC2TileF, A.tiles_t = (A.OT + kC2TileT - 1) / kC2TileT;
-    A.tiles = A.B * A.tiles_f * A.tiles_t;
     A.tiles_per_slab = (A.tiles + slabs - 1) / slabs;
     A.vec_dz = A.Co % 4 == 0 && aligned16({dz, dgz});
-    PTMI_RETURN_IF((M + 63) / 64 > 0x7fffffffLL || (N + 63) / 64 > 65535, PTMI_E_UNSUPPORTED);
+    const long long M = (long long)A.NQ * A.Co, N = (long long)A.Ci * A.KF * A.KT;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(je_conv2d_wgrad_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)((N + 63) / 64), (unsigned)slabs), dim3(256),
                        (size_t)lds, st, A);

@@ -20,7 +20,8 @@ The backward recomputes ``act'`` and the sigmoid from the saved ``z`` and ``g`` 
 convolution kernel on ``dz`` (and ``dg``) with flipped taps and, for a stride, zeros inserted in LDS; ``dW`` is ``je_conv2d_wgrad`` (the
 reduction over the pixels, slabs summed in order); bias gradients are ``wavenet_colsum``.  Operand scales are measured into words a
 captured graph zeroes itself, so forward + backward capture in a plain ``torch.cuda.graph``.  fp32 on the GPU only; nothing is read on
-the host.
+the host.  A geometry whose halo does not fit the LDS of a workgroup raises ``NotImplementedError`` in the first forward; one whose weight
+gradient alone does not fit (``ptmi_je_conv2d_wgrad_lds``) raises it in the forward too when a weight requires a gradient.
 """
 import weakref
 from collections import namedtuple
@@ -117,6 +118,11 @@ def _planes_form(weight, gate_weight, geom, input_grad):
     return form
 
 
+def _wgrad_geom(cfg, C_in, C_out, G, KF, KT):
+    """The first 16 geometry values of ``ptmi_je_conv2d_wgrad``."""
+    return [cfg.B, cfg.F_in, cfg.T_in, C_in, cfg.F_out, cfg.T_out, C_out, G, KF, KT, *cfg.stride, *cfg.dilation, *cfg.front]
+
+
 class _Block2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, gate_weight, gate_bias, gamma, beta, slope, fixed, lengths, cfg):
@@ -180,8 +186,7 @@ class _Block2dFn(torch.autograd.Function):
         dw = dgw = None
         if need[2] or need[4]:
             slabs = wgrad_slabs(B, cfg.F_out, cfg.T_out, G, C_out, C_in, KF * KT)
-            dW = ops.je_conv2d_wgrad(dz, dgz, a, amax_d, amax_a, [B, cfg.F_in, cfg.T_in, C_in, cfg.F_out, cfg.T_out, C_out, G, KF, KT,
-                                                                   *cfg.stride, *cfg.dilation, *cfg.front], slabs)
+            dW = ops.je_conv2d_wgrad(dz, dgz, a, amax_d, amax_a, _wgrad_geom(cfg, C_in, C_out, G, KF, KT), slabs)
             dw, dgw = dW[0], (dW[1] if G == 2 else None)
         dx = None
         pre_stage = cfg.pre and (has_norm or bool(act))
@@ -213,6 +218,13 @@ def conv_block2d(x, cfg, weight, bias=None, gate_weight=None, gate_bias=None, ga
         raise ValueError(f'je_conv2d.conv_block2d: x [{cfg.B * cfg.F_in * cfg.T_in}, {weight.shape[1]}], got {tuple(x.shape)}')
     if cfg.act == ACTIVATIONS['prelu'] and (slope is None or slope.numel() != 1):
         raise NotImplementedError('je_conv2d.conv_block2d: a PReLU with one parameter')
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (weight, gate_weight)):
+        # a layer whose weight gradient is not built says so here, not by a status code in the first backward
+        C_out, C_in, KF, KT = weight.shape
+        wgeom = _wgrad_geom(cfg, C_in, C_out, 1 if gate_weight is None else 2, KF, KT)
+        if _lib.load().ptmi_je_conv2d_wgrad_lds(_lib.int64s(*wgeom, C_in)) < 1:
+            raise NotImplementedError('je_conv2d.conv_block2d: the weight gradient of this geometry does not fit the LDS of a workgroup '
+                                      f'(the layer runs with weights that do not require a gradient): {wgeom}')
     cont = [None if t is None else t.contiguous() for t in (weight, bias, gate_weight, gate_bias)]
     flat = [None if t is None else t.reshape(-1) for t in (gamma, beta)]
     if cfg.norm is None:

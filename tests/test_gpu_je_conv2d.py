@@ -53,7 +53,8 @@ def block64(net, x, lengths, residual=None):
 
 
 def check(name, net, want_fn, run_fn, x0, extra=()):
-    """Values and every gradient of ``run_fn(net on the GPU, x, *extra)`` against ``want_fn(its fp64 copy, x, *extra)``."""
+    """Values and every gradient of ``run_fn(net on the GPU, x, *extra)`` against ``want_fn(its fp64 copy, x, *extra)``; returns the GPU's
+    ``(y, [dx, every parameter gradient])``."""
     cpu = copy.deepcopy(net).cpu().double()
     xc = torch.from_numpy(x0).double().requires_grad_()
     ec = [torch.from_numpy(e).double() for e in extra]
@@ -68,6 +69,7 @@ def check(name, net, want_fn, run_fn, x0, extra=()):
     wants = {n: w.numpy() for (n, _), w in zip(net.named_parameters(), want[1:])}
     for (n, _), g in zip(net.named_parameters(), got[1:]):
         close(f'{name} d {n}', g, wants[n], GRAD, grad_scale(wants, n))
+    return y, list(got)
 
 
 def perturbed(net, seed=1):
@@ -222,9 +224,9 @@ def test_evaluation_after_two_training_steps(g27):
             close('w0 buffer ' + k, state[k], g27['w0e_b_' + k], VALUE)
 
 
-def test_graph_replays_bit_identically(g27):
-    """Forward + backward of the first fixture case without lengths in a plain ``torch.cuda.graph``: replays on new inputs against the eager call (the
-    operand scale words start from zero in every replay)."""
+def capture(g27):
+    """Forward + backward of the first fixture case without lengths captured in a plain ``torch.cuda.graph``: ``(net, graph, its static
+    x and r, its outputs, the eager step)``."""
     net = build(g27, 'w0')
     params = list(net.parameters())
     sx = torch.zeros(B, 1, F_IN, T_IN).cuda().requires_grad_()
@@ -241,6 +243,12 @@ def test_graph_replays_bit_identically(g27):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, stream=side):
         captured = step(sx, sr)
+    return net, graph, sx, sr, captured, step
+
+
+def test_graph_replays_bit_identically(g27):
+    """Replays on new inputs against the eager call (the operand scale words start from zero in every replay)."""
+    _, graph, sx, sr, captured, step = capture(g27)
     for seed, scale in ((11, 3.), (12, .01), (13, 1.)):
         rng = np.random.RandomState(seed)
         nx, nr = (torch.from_numpy((scale * rng.randn(*t.shape)).astype(np.float32)).cuda() for t in (sx, sr))
@@ -251,3 +259,27 @@ def test_graph_replays_bit_identically(g27):
         torch.cuda.synchronize()
         for k, (a, b) in enumerate(zip(captured, step(nx.requires_grad_(), nr))):
             assert torch.equal(a, b), ('replay', seed, k)
+
+
+def test_graph_replay_follows_a_weight_update(g27):
+    """The weight planes are packed inside the graph: after an in-place update of every parameter the replay gives the bits of the eager
+    call with the updated weights (several replays), not those of the weights it was captured with."""
+    net, graph, sx, sr, captured, step = capture(g27)
+    rng = np.random.RandomState(14)
+    nx, nr = (torch.from_numpy(rng.randn(*t.shape).astype(np.float32)).cuda() for t in (sx, sr))
+    with torch.no_grad():
+        sx.copy_(nx)
+        sr.copy_(nr)
+    graph.replay()
+    torch.cuda.synchronize()
+    before = [t.clone() for t in captured]
+    gen = torch.Generator().manual_seed(15)
+    for _ in range(2):
+        with torch.no_grad():
+            for p in net.parameters():
+                p.add_((0.1 * torch.randn(p.shape, generator=gen)).cuda())
+        graph.replay()
+        torch.cuda.synchronize()
+        for k, (a, b) in enumerate(zip(captured, step(nx.requires_grad_(), nr))):
+            assert torch.equal(a, b), ('replay after a weight update', k)
+        assert not torch.equal(captured[0], before[0]) and not torch.equal(captured[1], before[1])
