@@ -1155,6 +1155,43 @@ int64_t ptmi_je_conv2d_wgrad_lds(const int64_t* geom);
 int ptmi_je_pool2d_forward(const float* x, float* y, int64_t* index, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 int ptmi_je_pool2d_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The angular-margin softmax head of padertorch/contrib/tcl/speaker_embeddings/loss.py:64-103 and the BatchNorm1d(E, affine=False) of
+ * dvectors.py (csrc/aam_softmax.hip).  fp32, products exact fp32 on v_mfma_f32_16x16x4_f32, the logits [B, C] are never written, no
+ * atomics, every sum in one fixed order, nothing read on the host: every launcher is capturable.  weight [C, E], e [B, E] contiguous,
+ * labels [B] int32 / int64 on the device; 1 <= E <= ptmi_aam_max_features() (= 512; PTMI_E_UNSUPPORTED beyond), B >= 1, C >= 2.
+ * loss_type: 0 aam  n = s (cos_y - m), 1 arcface  n = s cos(acos(clamp(cos_y, -1 + eps, 1 - eps)) + m), 2 sphereface  n = s cos(m acos(..)).
+ *
+ * ptmi_aam_class_tile / _row_tile : classes a workgroup owns (32) / batch rows of a streamed tile (64): what the tests put C and B around
+ * ptmi_aam_prepare  : weight <- weight / max(||row||, 1e-12) IN PLACE, e_hat likewise from e, e_rnorm [B] = 1 / max(||e||, 1e-12); one launch
+ * ptmi_aam_forward  : part_max, part_sum [ceil(C / class tile)][B] (per class tile: maximum and sum of exp(s cos - max) over the classes
+ *   other than the target), cos_y [B]; then loss_rows [B] = -L_b = lse_b - n_b, lse [B] (log-sum-exp over n_b and the other classes, with a
+ *   running maximum), n [B], dn [B] = dn/dcos_y (0 where the clamp is active), loss_mean [1] = mean of loss_rows (fp64) or NULL.  A label
+ *   outside [0, C): loss NaN, lse +inf (no gradient from that row), nothing indexed with it.
+ * ptmi_aam_backward : dw [C, E] (gradient of the NORMALISED rows) and / or de [B, E] (through the embedding's normalisation), from
+ *   gout [B], or gout [1] / B with gout_mean; each may be NULL.  de needs e_rnorm, splits = ptmi_aam_de_splits(B, C) and a workspace of
+ *   splits B E floats.  Both are written whole.
+ * ptmi_batch_norm_rows_forward  : y = (x - mean) rstd over the rows of x [B, E]; training: batch statistics (fp64, biased variance),
+ *   running_mean / running_var (unbiased) updated with momentum, num_batches_tracked + 1 (each may be NULL), B >= 2; else the running
+ *   statistics.  stats [2][E] doubles = mean | rstd, for the backward.
+ * ptmi_batch_norm_rows_backward : dx from gy, x and stats (through the batch statistics when training).
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_aam_max_features(void);
+int32_t ptmi_aam_class_tile(void);
+int32_t ptmi_aam_row_tile(void);
+int64_t ptmi_aam_de_splits(int64_t B, int64_t C);
+int ptmi_aam_prepare(float* weight, const float* e, float* e_hat, float* e_rnorm, int64_t B, int64_t C, int32_t E, ptmi_stream_t stream);
+int ptmi_aam_forward(const float* w_hat, const float* e_hat, const void* labels, int32_t labels_int64, int64_t B, int64_t C, int32_t E,
+                     int32_t loss_type, float s, double m, double eps, float* part_max, float* part_sum, float* cos_y, float* loss_rows,
+                     float* lse, float* n, float* dn, float* loss_mean, ptmi_stream_t stream);
+int ptmi_aam_backward(const float* w_hat, const float* e_hat, const float* e_rnorm, const void* labels, int32_t labels_int64, const float* lse,
+                      const float* n, const float* dn, const float* gout, int32_t gout_mean, int64_t B, int64_t C, int32_t E, float s,
+                      float* dw, float* de, float* workspace, int64_t splits, ptmi_stream_t stream);
+int ptmi_batch_norm_rows_forward(const float* x, float* y, double* stats, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                 int64_t B, int32_t E, int32_t training, double momentum, double eps, ptmi_stream_t stream);
+int ptmi_batch_norm_rows_backward(const float* gy, const float* x, const double* stats, float* dx, int64_t B, int32_t E, int32_t training,
+                                  ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

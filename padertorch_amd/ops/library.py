@@ -49,6 +49,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                    ptmi_je_conv_*, ptmi_je_pool_*   (contrib/je/modules/conv.py, conv_utils.py)
     torch.ops.ptmi.je_conv2d_pack / je_conv2d_forward / je_conv2d_wgrad, je_pool2d_forward / _backward
                                                    ptmi_je_conv2d_*, ptmi_je_pool2d_*   (Conv2d, CNN2d, Pool2d)
+    torch.ops.ptmi.aam_prepare / aam_forward / aam_backward, batch_norm_rows_forward / _backward
+                                                   ptmi_aam_*, ptmi_batch_norm_rows_*   (contrib/tcl/speaker_embeddings/loss.py, dvectors.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -2035,4 +2037,94 @@ def je_pool2d_backward(dy, index, geom, max_pool):
     dx = torch.empty((B * IF * IT, C), dtype=torch.float32, device=dy.device)
     _lib.call('ptmi_je_pool2d_backward', dy.data_ptr(), _lib.ptr(index), dx.data_ptr(), _lib.int64s(*geom[:10], C, *geom[10:]), int(max_pool),
               _lib.stream(dy.device), timer='je_pool2d_backward')
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------ angular-margin softmax head (csrc/aam_softmax.hip)
+def _aam_dims(w_hat, e_hat, labels):
+    _f32c(w_hat, e_hat)
+    (C, E), B = w_hat.shape, e_hat.shape[0]
+    assert e_hat.shape == (B, E), (w_hat.shape, e_hat.shape)
+    labels, is64 = _lengths(labels, B)
+    return B, C, E, labels, is64
+
+
+@_register('aam_prepare(Tensor(a!) weight, Tensor e) -> (Tensor, Tensor)')
+def aam_prepare(weight, e):
+    """``weight [C, E]`` becomes its row-normalised self IN PLACE; returns ``(e_hat [B, E], 1 / max(||e||, 1e-12) [B])`` (``ptmi_aam_prepare``;
+    speaker_embeddings/loss.py:79-83)."""
+    _f32c(weight, e)
+    (C, E), B = weight.shape, e.shape[0]
+    assert e.shape == (B, E), (weight.shape, e.shape)
+    e_hat, e_rnorm = torch.empty_like(e), torch.empty(B, dtype=torch.float32, device=e.device)
+    rc = _lib.call('ptmi_aam_prepare', weight.data_ptr(), e.data_ptr(), e_hat.data_ptr(), e_rnorm.data_ptr(), B, C, E, _lib.stream(e.device),
+                   timer='aam_prepare', accept=(-2,))
+    if rc == -2:
+        raise NotImplementedError(f'aam_softmax: {E} features are beyond the kernels\' bound of {_lib.load().ptmi_aam_max_features()}')
+    return e_hat, e_rnorm
+
+
+@_register('aam_forward(Tensor w_hat, Tensor e_hat, Tensor labels, int loss_type, float s, float m, float eps, bool mean) '
+           '-> (Tensor, Tensor, Tensor, Tensor, Tensor?)')
+def aam_forward(w_hat, e_hat, labels, loss_type, s, m, eps, mean):
+    """``(-L [B], lse [B], n [B], dn/dcos_y [B], -mean(L) [] or None)``: the class-tile kernel (partials ``[tiles, B]``, no logits), the row
+    kernel and the fp64 mean (``ptmi_aam_forward``; loss.py:86-103)."""
+    B, C, E, labels, is64 = _aam_dims(w_hat, e_hat, labels)
+    dev = e_hat.device
+    tiles = -(-C // _lib.load().ptmi_aam_class_tile())
+    part = torch.empty((2, tiles, B), dtype=torch.float32, device=dev)
+    rows = torch.empty((5, B), dtype=torch.float32, device=dev)           # cos_y | -L | lse | n | dn
+    total = torch.empty((), dtype=torch.float32, device=dev) if mean else None
+    _lib.call('ptmi_aam_forward', w_hat.data_ptr(), e_hat.data_ptr(), labels.data_ptr(), is64, B, C, E, loss_type, s, m, eps, part[0].data_ptr(),
+              part[1].data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), rows[3].data_ptr(), rows[4].data_ptr(),
+              _lib.ptr(total), _lib.stream(dev), timer='aam_forward')
+    return rows[1], rows[2], rows[3], rows[4], total
+
+
+@_register('aam_backward(Tensor w_hat, Tensor e_hat, Tensor e_rnorm, Tensor labels, Tensor lse, Tensor n, Tensor dn, Tensor gout, bool mean, '
+           'float s, bool want_dw, bool want_de) -> (Tensor?, Tensor?)')
+def aam_backward(w_hat, e_hat, e_rnorm, labels, lse, n, dn, gout, mean, s, want_dw, want_de):
+    """``(dW [C, E] of the normalised rows, de [B, E])`` - the class-tile kernel, the row-tile kernel over class ranges and its finish
+    (``ptmi_aam_backward``); cosines recomputed, no atomics."""
+    B, C, E, labels, is64 = _aam_dims(w_hat, e_hat, labels)
+    _f32c(e_rnorm, lse, n, dn, gout)
+    assert gout.numel() == (1 if mean else B), (gout.shape, mean, B)
+    dev = e_hat.device
+    dw = torch.empty_like(w_hat) if want_dw else None
+    de = ws = None
+    splits = 0
+    if want_de:
+        splits = _lib.load().ptmi_aam_de_splits(B, C)
+        de, ws = torch.empty_like(e_hat), torch.empty((splits, B, E), dtype=torch.float32, device=dev)
+    if want_dw or want_de:
+        _lib.call('ptmi_aam_backward', w_hat.data_ptr(), e_hat.data_ptr(), e_rnorm.data_ptr(), labels.data_ptr(), is64, lse.data_ptr(),
+                  n.data_ptr(), dn.data_ptr(), gout.data_ptr(), int(mean), B, C, E, s, _lib.ptr(dw), _lib.ptr(de), _lib.ptr(ws), splits,
+                  _lib.stream(dev), timer='aam_backward')
+    return dw, de
+
+
+@_register('batch_norm_rows_forward(Tensor x, Tensor(a!)? running_mean, Tensor(b!)? running_var, Tensor(c!)? num_batches_tracked, '
+           'bool training, float momentum, float eps) -> (Tensor, Tensor)')
+def batch_norm_rows_forward(x, running_mean, running_var, num_batches_tracked, training, momentum, eps):
+    """``(y [B, E], stats [2, E] fp64 = mean | rstd)``; training updates the three buffers in the same launch
+    (``ptmi_batch_norm_rows_forward``; nn.BatchNorm1d(E, affine=False) of dvectors.py)."""
+    _f32c(x, running_mean, running_var)
+    B, E = x.shape
+    assert all(t is None or t.shape == (E,) for t in (running_mean, running_var)), (running_mean.shape, running_var.shape, E)
+    assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.numel() == 1)
+    y, stats = torch.empty_like(x), torch.empty((2, E), dtype=torch.float64, device=x.device)
+    _lib.call('ptmi_batch_norm_rows_forward', x.data_ptr(), y.data_ptr(), stats.data_ptr(), _lib.ptr(running_mean), _lib.ptr(running_var),
+              _lib.ptr(num_batches_tracked), B, E, int(training), momentum, eps, _lib.stream(x.device), timer='batch_norm_rows_forward')
+    return y, stats
+
+
+@_register('batch_norm_rows_backward(Tensor gy, Tensor x, Tensor stats, bool training) -> Tensor')
+def batch_norm_rows_backward(gy, x, stats, training):
+    """``dx [B, E]`` (``ptmi_batch_norm_rows_backward``)."""
+    _f32c(gy, x)
+    B, E = x.shape
+    assert gy.shape == x.shape and stats.shape == (2, E) and stats.dtype == torch.float64 and stats.is_contiguous(), (gy.shape, stats.shape)
+    dx = torch.empty_like(x)
+    _lib.call('ptmi_batch_norm_rows_backward', gy.data_ptr(), x.data_ptr(), stats.data_ptr(), dx.data_ptr(), B, E, int(training),
+              _lib.stream(x.device), timer='batch_norm_rows_backward')
     return dx
