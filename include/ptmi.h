@@ -1156,6 +1156,40 @@ int ptmi_je_pool2d_forward(const float* x, float* y, int64_t* index, const int64
 int ptmi_je_pool2d_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, int32_t max_pool, ptmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The transposed convolution blocks and the unpooling of conv.py / conv_utils.py (csrc/je_conv_transpose.hip): a phase-split
+ * (sub-pixel) direct convolution on the rows and in the arithmetic of csrc/je_conv2d.hip.  Per axis the output position o of the window
+ * that starts `front` positions into the full output belongs to phase (o + front) mod stride; a workgroup owns one phase, whose pixels
+ * form a dense grid under the taps k with k dilation = phase (mod stride).  No inserted zero is staged or multiplied.
+ *
+ * geom [18 + K_f + K_t] = (B, F_in, T_in, C_in, F_out, T_out, C_out, outputs (1, or 2 with a gate convolution), K_f, K_t, stride f, t,
+ *   dilation f, t, front f, t, ld of x, ld of the residual, then per axis the taps 0 .. K - 1 ordered by phase (k dilation mod stride),
+ *   ascending).  F_out + front <= (F_in - 1) stride + (K_f - 1) dilation + 1, likewise t.  K, stride <= 16 per axis, at most 64 phases.
+ * ptmi_je_conv_transpose_pack_elems : uint16 elements of the weight planes (0 is a size: no phase has a tap); -1: not a geometry;
+ *   -2: a geometry the kernel does not take (the limits above, or the halo beyond the LDS of a workgroup).
+ * ptmi_je_conv_transpose_ksteps : matrix-instruction k steps (32 wide) per output pixel and 16 output channels, summed over the phases
+ *   and the channel chunks (what the benchmark prints); negative as above.
+ * ptmi_je_conv_transpose_pack    : the planes of w0 (and w1, the gate's) [C_in, C_out, K_f, K_t] (torch.nn.ConvTranspose2d's layout) in
+ *   fragment order [channel tile][chunk][phase][k step], k order (tap within the phase, channel padded to 8).  amax: word of max |w|.
+ * ptmi_je_conv_transpose_forward : z = bias + the transposed convolution of x, gz likewise; out != NULL: out = act(z) sigmoid(gz) +
+ *   residual in the same launch.  z, gz, out [B F_out T_out, C_out] contiguous, every element written.
+ * The backward has no entry of its own: dx is ptmi_je_conv2d_forward (mode 0, the same weights read as [C_out' = C_in, C_in' = C_out]),
+ *   dW is ptmi_je_conv2d_wgrad with x as the pixel operand and dy under the taps.
+ * geom [13] of the unpooling = (B, F_in, T_in, F_out, T_out, C, size f, t, stride f, t, ld of x, front f, t): x the pooled rows.
+ * ptmi_je_unpool_forward / _backward : index != NULL (int64 [B F_in T_in, C], f T_p + t on the plane (F_in - 1) stride + size of
+ *   MaxUnpool): y[p] = x[w] of the last window w (row-major) that holds p + front and stores it, else 0; index == NULL: nearest
+ *   upsampling, F_out = F_in stride.  The backward is the matching gather / block sum; dx [B F_in T_in, C] is written whole.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t ptmi_je_conv_transpose_pack_elems(const int64_t* geom);
+int64_t ptmi_je_conv_transpose_ksteps(const int64_t* geom);
+int ptmi_je_conv_transpose_pack(const float* w0, const float* w1, const uint32_t* amax, uint16_t* planes, const int64_t* geom,
+                                ptmi_stream_t stream);
+int ptmi_je_conv_transpose_forward(const float* x, const uint16_t* planes, const uint32_t* amax_x, const uint32_t* amax_w, const float* bias,
+                                   const float* gate_bias, const float* residual, const float* slope, float* z, float* gz, float* out,
+                                   const int64_t* geom, int32_t act, float act_p, ptmi_stream_t stream);
+int ptmi_je_unpool_forward(const float* x, const int64_t* index, float* y, const int64_t* geom, ptmi_stream_t stream);
+int ptmi_je_unpool_backward(const float* dy, const int64_t* index, float* dx, const int64_t* geom, ptmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The angular-margin softmax head of padertorch/contrib/tcl/speaker_embeddings/loss.py:64-103 and the BatchNorm1d(E, affine=False) of
  * dvectors.py (csrc/aam_softmax.hip).  fp32, products exact fp32 on v_mfma_f32_16x16x4_f32, the logits [B, C] are never written, no
  * atomics, every sum in one fixed order, nothing read on the host: every launcher is capturable.  weight [C, E], e [B, E] contiguous,

@@ -7,6 +7,7 @@ from . import conv  # noqa: F401
 from . import conv_utils  # noqa: F401
 from . import conv2d  # noqa: F401
 from . import hybrid  # noqa: F401
+from . import conv_transpose  # noqa: F401  (the transposed classes live there only; none of its names is re-exported)
 from .hybrid import CNN, CRNN  # noqa: F401
 from .conv import CNN1d, Conv1d  # noqa: F401
 from .conv2d import CNN2d, Conv2d, Pool2d  # noqa: F401

@@ -21,9 +21,10 @@ GEMM's output in front of the lengths too - and with it the statistics computed 
 positions whose window holds it.  Pad with finite values (zeros), as every layer here does for the next.
 
 Not built (``NotImplementedError``, no library fallback): ``state`` / ``return_state`` (the streaming mode), CUDA-resident
-``sequence_lengths``, ``get_transpose_config``, other activations or callables, a normalisation with ``shift=False`` or ``scale=False``, and
-the transposed classes (``ConvTranspose1d``, ``ConvTranspose2d``, ``CNNTranspose1d``, ``CNNTranspose2d``, ``Unpool1d``, ``Unpool2d``) and
-``resnet50``, which are not defined at all.  ``Conv2d``, ``CNN2d`` and ``Pool2d`` are in ``conv2d.py``, built on ``_Conv`` / ``_CNN`` here.
+``sequence_lengths``, other activations or callables, a normalisation with ``shift=False`` or ``scale=False``, and ``resnet50``, which is
+not defined at all.  ``Conv2d``, ``CNN2d`` and ``Pool2d`` are in ``conv2d.py``, built on ``_Conv`` / ``_CNN`` here; the transposed classes
+(``ConvTranspose1d``, ``ConvTranspose2d``, ``CNNTranspose1d``, ``CNNTranspose2d``, ``Unpool1d``, ``Unpool2d``) and a working
+``get_transpose_config`` are in ``conv_transpose.py`` and only there: the classmethod of ``CNN1d`` / ``CNN2d`` raises and names it.
 """
 from copy import copy
 from typing import List
@@ -400,7 +401,7 @@ class _CNN(nn.Module):
 
     @classmethod
     def get_transpose_config(cls, config, transpose_config=None):
-        raise NotImplementedError(f'{cls.__name__}.get_transpose_config: the transposed stack is not built')
+        raise NotImplementedError(f'{cls.__name__}.get_transpose_config: use the module-level conv_transpose.get_transpose_config(config)')
 
     def get_shapes(self, input_shape=None, target_shape=None):
         assert (input_shape is None) ^ (target_shape is None), (input_shape, target_shape)

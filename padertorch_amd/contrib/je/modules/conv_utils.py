@@ -7,7 +7,7 @@ arithmetic there, the indices of max pooling count on the padded axis as ``nn.Ma
 ``Pad`` / ``Trim``.  ``Pad`` (``mode='constant'`` only) and ``Trim`` are views / one ``F.pad`` on ``[B, C, T]`` or ``[B, C, F, T]``: the
 convolution blocks never call them.  ``Pool2d`` lives in ``conv2d.py`` beside the 2-D blocks.
 
-Not built: ``Unpool1d``, ``Unpool2d``.
+``Unpool1d`` and ``Unpool2d`` live in ``conv_transpose.py``.
 """
 import math
 

@@ -133,7 +133,8 @@ class CNN(_Configured, nn.Module):
 
     @classmethod
     def get_transpose_config(cls, config, transpose_config=None):
-        raise NotImplementedError('CNN.get_transpose_config: the transposed stack (CNNTranspose) is not built')
+        raise NotImplementedError('CNN.get_transpose_config: a transposed hybrid (CNNTranspose) is not built; conv_transpose.get_transpose_config '
+                                  'mirrors a CNN1d / CNN2d')
 
     def get_shapes(self, in_shape):
         cnn_2d_shapes = self.cnn_2d.get_shapes(in_shape)

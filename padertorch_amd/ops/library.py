@@ -49,6 +49,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                    ptmi_je_conv_*, ptmi_je_pool_*   (contrib/je/modules/conv.py, conv_utils.py)
     torch.ops.ptmi.je_conv2d_pack / je_conv2d_forward / je_conv2d_wgrad, je_pool2d_forward / _backward
                                                    ptmi_je_conv2d_*, ptmi_je_pool2d_*   (Conv2d, CNN2d, Pool2d)
+    torch.ops.ptmi.je_conv_transpose_pack / je_conv_transpose_forward, je_unpool_forward / _backward
+                                                   ptmi_je_conv_transpose_*, ptmi_je_unpool_*   (ConvTranspose*, CNNTranspose*, Unpool*)
     torch.ops.ptmi.aam_prepare / aam_forward / aam_backward, batch_norm_rows_forward / _backward
                                                    ptmi_aam_*, ptmi_batch_norm_rows_*   (contrib/tcl/speaker_embeddings/loss.py, dvectors.py)
 """
@@ -2037,6 +2039,78 @@ def je_pool2d_backward(dy, index, geom, max_pool):
     dx = torch.empty((B * IF * IT, C), dtype=torch.float32, device=dy.device)
     _lib.call('ptmi_je_pool2d_backward', dy.data_ptr(), _lib.ptr(index), dx.data_ptr(), _lib.int64s(*geom[:10], C, *geom[10:]), int(max_pool),
               _lib.stream(dy.device), timer='je_pool2d_backward')
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------ contrib/je transposed convolution blocks (csrc/je_conv_transpose.hip)
+def _jct_elems(geom):
+    """uint16 elements of the planes for the launch ``geom`` (its values in front of the two leading dimensions); refuses what the
+    planner does not take."""
+    elems = _lib.load().ptmi_je_conv_transpose_pack_elems(_lib.int64s(*geom[:16], geom[3], geom[6], *geom[16:]))
+    if elems == -2:
+        raise NotImplementedError('je_conv_transpose: more than 16 taps or a stride beyond 16 per axis, more than 64 phases, or a halo '
+                                  f'that does not fit the LDS of a workgroup: {list(geom)}')
+    assert elems >= 0, geom
+    return elems
+
+
+@_register('je_conv_transpose_pack(Tensor w0, Tensor? w1, Tensor amax, int[] geom) -> Tensor')
+def je_conv_transpose_pack(w0, w1, amax, geom):
+    """The fp16 hi / lo planes of the weights ``[C_in, C_out, K_f, K_t]`` per phase in fragment order; ``geom``: the values of
+    ``ptmi_je_conv_transpose_forward``'s without the two leading dimensions (16 values, then the phase table)."""
+    _f32c(w0, w1)
+    assert tuple(w0.shape) == (geom[3], geom[6], geom[8], geom[9]) and (w1 is None or w1.shape == w0.shape), (w0.shape, geom)
+    planes = torch.empty(_jct_elems(geom), dtype=torch.int16, device=w0.device)
+    _lib.call('ptmi_je_conv_transpose_pack', w0.data_ptr(), _lib.ptr(w1), amax.data_ptr(), planes.data_ptr(),
+              _lib.int64s(*geom[:16], geom[3], geom[6], *geom[16:]), _lib.stream(w0.device), timer='je_conv_transpose_pack')
+    return planes
+
+
+@_register('je_conv_transpose_forward(Tensor x, Tensor planes, Tensor amax_x, Tensor amax_w, Tensor? bias, Tensor? gate_bias, '
+           'Tensor? residual, Tensor? slope, int[] geom, int act, float act_p, bool fused) -> (Tensor, Tensor?, Tensor?)')
+def je_conv_transpose_forward(x, planes, amax_x, amax_w, bias, gate_bias, residual, slope, geom, act, act_p, fused):
+    """``(z, gz or None, out or None) [B F_out T_out, C_out]`` of the phase-split transposed convolution of the rows ``x
+    [B F_in T_in, C_in]``; ``geom`` as for :func:`je_conv_transpose_pack`."""
+    B, IF, IT, Ci, OF, OT, Co, NQ = geom[:8]
+    xp, ldx = _jc_rows(x, Ci, 'x')
+    assert x.shape[0] == B * IF * IT and planes.numel() == _jct_elems(geom), (x.shape, planes.shape, geom)
+    _f32c(bias, gate_bias, slope)
+    assert all(b is None or b.numel() == Co for b in (bias, gate_bias))
+    rp, ldr = (None, Co) if residual is None else _jc_rows(residual, Co, 'residual')
+    assert residual is None or residual.shape[0] == B * OF * OT
+    z = torch.empty((B * OF * OT, Co), dtype=torch.float32, device=x.device)
+    gz = torch.empty_like(z) if NQ == 2 else None
+    out = torch.empty_like(z) if fused else None
+    _lib.call('ptmi_je_conv_transpose_forward', xp, planes.data_ptr(), amax_x.data_ptr(), amax_w.data_ptr(), _lib.ptr(bias),
+              _lib.ptr(gate_bias), rp, _lib.ptr(slope), z.data_ptr(), _lib.ptr(gz), _lib.ptr(out),
+              _lib.int64s(*geom[:16], ldx, ldr, *geom[16:]), act, act_p, _lib.stream(x.device), timer='je_conv_transpose_forward')
+    return z, gz, out
+
+
+@_register('je_unpool_forward(Tensor x, Tensor? index, int[] geom) -> Tensor')
+def je_unpool_forward(x, index, geom):
+    """``y [B F_out T_out, C]`` from the pooled rows ``x [B F_in T_in, C]``; ``geom = (B, F_in, T_in, F_out, T_out, C, size f, t, stride
+    f, t, front f, t)``; with ``index`` (int64, as ``je_pool2d_forward`` gives it) max unpooling, else nearest upsampling."""
+    B, IF, IT, OF, OT, C = geom[:6]
+    xp, ldx = _jc_rows(x, C, 'x')
+    assert x.shape[0] == B * IF * IT
+    assert index is None or (tuple(index.shape) == (B * IF * IT, C) and index.is_contiguous() and index.dtype == torch.int64)
+    y = torch.empty((B * OF * OT, C), dtype=torch.float32, device=x.device)
+    _lib.call('ptmi_je_unpool_forward', xp, _lib.ptr(index), y.data_ptr(), _lib.int64s(*geom[:10], ldx, *geom[10:]), _lib.stream(x.device),
+              timer='je_unpool_forward')
+    return y
+
+
+@_register('je_unpool_backward(Tensor dy, Tensor? index, int[] geom) -> Tensor')
+def je_unpool_backward(dy, index, geom):
+    """``dx [B F_in T_in, C]`` (``ptmi_je_unpool_backward``)."""
+    B, IF, IT, OF, OT, C = geom[:6]
+    _f32c(dy)
+    assert tuple(dy.shape) == (B * OF * OT, C), (dy.shape, geom)
+    assert index is None or (tuple(index.shape) == (B * IF * IT, C) and index.is_contiguous() and index.dtype == torch.int64)
+    dx = torch.empty((B * IF * IT, C), dtype=torch.float32, device=dy.device)
+    _lib.call('ptmi_je_unpool_backward', dy.data_ptr(), _lib.ptr(index), dx.data_ptr(), _lib.int64s(*geom[:10], C, *geom[10:]),
+              _lib.stream(dy.device), timer='je_unpool_backward')
     return dx
 
 
