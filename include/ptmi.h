@@ -1226,6 +1226,43 @@ int ptmi_batch_norm_rows_forward(const float* x, float* y, double* stats, float*
 int ptmi_batch_norm_rows_backward(const float* gy, const float* x, const double* stats, float* dx, int64_t B, int32_t E, int32_t training,
                                   ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The feature extractor of padertorch/contrib/je/modules/features.py:142-206 and the augmentations of contrib/je/modules/augment.py
+ * (csrc/je_features.hip).  fp32, forward only.  Every random quantity is drawn on the host and arrives as a per-example table [B] (or
+ * [n, B]) on the device; a NULL table switches its stage off.  Limits (PTMI_E_UNSUPPORTED beyond): F <= 1025, M <= 256, C <= 8, blur
+ * taps k <= 9 and odd with T', M >= (k + 1) / 2, delta width 5, B <= 65535, M T < 2^31.
+ *
+ * ptmi_je_front_tile / _shape_tile : frames of a workgroup's tile in _logmel_front (32) / _feature_shape (64): what the tests put T around
+ * ptmi_je_logmel_front  : x [B, C, T, F, 2] -> logmel [B, C, M, T] = log(|gain_b x_b + lambda_b partner_gain_b x_partner(b)|^2 . fb + eps),
+ *   fb either the band-compressed static filterbank of ptmi_mel_apply (mel_lo, mel_cnt, mel_off, mel_w) or, with edges_hz [B, M + 2]
+ *   (strictly increasing rows, Hz), the example's own triangles max(0, min((f - l) / (c - l), (r - f) / (r - c))) at f = k bin_hz,
+ *   normalised by sum + 1e-6.  n_pairs > 0: ipd_cos, ipd_sin [B, n_pairs, M, T] of the phase difference between the channels
+ *   pair_other[p] and pair_ref[p] (HOST arrays) at bin max_bin[m]; (1, 0) where both values vanish.
+ * ptmi_je_feature_shape : x [B, C, M, T] -> out [B, C (1 + d + dd), M, T_out]: frame t is (1 - frac) x[floor] + frac x[floor + 1] with
+ *   time_floor / time_frac [B, T_out] (NULL: T_out = T); the separable k x k blur taps [B, k] (x) taps [B, k] over the reflect-padded
+ *   plane; then the static channels, the correlations with delta_kernel [5] and delta_delta_kernel [5] (HOST arrays), zero in the two
+ *   frames at either edge and from seq_len[b] - 2 on.
+ * ptmi_je_feature_tail  : x [B, C, M, T] -> out [B, C + 2 n_pairs, M, T]: v = clamp((x - mean) rstd) [t < seq_len[b]] on the C feature
+ *   channels (mean, rstd indexed c stat_stride_c + f stat_stride_f), the IPD planes behind them; v = lambda_b v_b + (1 - lambda_b)
+ *   v_partner(b); + noise_scale_b noise; 0 inside [onset, offset) of any of the n_time_masks / n_freq_masks tables [n, B] (int32).
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_je_front_tile(void);
+int32_t ptmi_je_shape_tile(void);
+int ptmi_je_logmel_front(const float* x, int64_t B, int32_t C, int64_t T, int32_t F, const float* gain, const int32_t* partner,
+                         const float* partner_gain, const float* lambda, const int32_t* mel_lo, const int32_t* mel_cnt, const int32_t* mel_off,
+                         const float* mel_w, const float* edges_hz, float bin_hz, const int32_t* max_bin, int32_t M, const int32_t* pair_ref,
+                         const int32_t* pair_other, int32_t n_pairs, float eps, float* logmel, float* ipd_cos, float* ipd_sin,
+                         ptmi_stream_t stream);
+int ptmi_je_feature_shape(const float* x, int64_t B, int32_t C, int32_t M, int64_t T, const int32_t* time_floor, const float* time_frac,
+                          int64_t T_out, const float* taps, int32_t k, int32_t add_deltas, int32_t add_delta_deltas, const float* delta_kernel,
+                          const float* delta_delta_kernel, int32_t delta_width, const int32_t* seq_len, float* out, ptmi_stream_t stream);
+int ptmi_je_feature_tail(const float* x, int64_t B, int32_t C, int32_t M, int64_t T, const float* mean, const float* rstd,
+                         int64_t stat_stride_c, int64_t stat_stride_f, int32_t has_clamp, float clamp, const float* ipd_cos,
+                         const float* ipd_sin, int32_t n_pairs, const int32_t* partner, const float* lambda, const float* noise_scale,
+                         const float* noise, const int32_t* time_onset, const int32_t* time_offset, int32_t n_time_masks,
+                         const int32_t* freq_onset, const int32_t* freq_offset, int32_t n_freq_masks, const int32_t* seq_len, float* out,
+                         ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

@@ -1,4 +1,6 @@
+from . import augment  # noqa: F401
 from . import features  # noqa: F401
+from .features import DeltaExtractor, MelTransform, NormalizedLogMelExtractor  # noqa: F401
 from . import transformer  # noqa: F401
 from .transformer import MultiHeadAttention, TransformerLayer, TransformerLayerStack, get_causal_mask  # noqa: F401
 from . import reduce  # noqa: F401

@@ -12,7 +12,13 @@ absent from the reference tree and pinned by none of its tests.  It is restated 
 published behaviour (HTK mel scale, ``number_of_filters + 2`` boundaries equally spaced in mel,
 unit-peak triangles evaluated at the FFT bin frequencies); parity of THAT matrix to paderbox is
 unverified.  ``MelTransform(fbanks=...)`` accepts any ``[F, M]`` matrix instead.
-Frequency warping (a random CPU-side augmentation) is out of scope.
+``MelTransform`` itself takes no ``warping_fn``.
+
+``NormalizedLogMelExtractor`` (``features.py:17-211``) is the whole front-end of the je models - scale / superpose, IPDs, (frequency
+warped) log-mel, time warp, blur, deltas, normalise, clamp, mixup, noise, masks - on the three kernels of ``csrc/je_features.hip``
+(``ops/je_features.py``), with every random draw made on the host in the reference's order (``augment.py``).  Frequency warping is
+restated like ``get_fbanks``: ``frequency_warping_fn`` maps the float64 mel-scale edge array ``[B, 1, 1, M + 2]`` to warped edges of the
+same shape, once per batch; parity of that contract to paderbox's ``get_fbanks(..., warping_fn, size)`` is unpinned too.
 """
 from typing import Optional
 
@@ -21,9 +27,12 @@ import torch
 from torch import nn
 
 from .... import _lib
+from ....modules.normalization import InputNormalization, Normalization
+from ....ops import je_features as _ops
 from ....ops._stft import STFT
+from .augment import AdditiveNoise, GaussianBlur2d, Mask, Mixup, Scale, Superpose, TimeWarping, TruncatedExponential
 
-__all__ = ['MelTransform', 'get_fbanks', 'stft_logmel']
+__all__ = ['MelTransform', 'get_fbanks', 'stft_logmel', 'NormalizedLogMelExtractor', 'DeltaExtractor']
 
 
 def _hz2mel(f, htk_mel):
@@ -161,6 +170,169 @@ class MelTransform(nn.Module):
             x = torch.exp(x)
         x = x @ ifbanks
         return torch.max(x, torch.zeros_like(x))
+
+
+class DeltaExtractor(nn.Module):
+    """Savitzky-Golay derivative of ``order`` along time: a valid correlation with ``(-1)^order savgol_coeffs(width, order,
+    deriv=order)``, zero in the ``(width - 1) / 2`` frames at either edge and from ``seq_len - (width - 1) / 2`` on (``features.py:341-390``).
+    The kernel covers ``width = 5`` on float32 ``[B, C, F, T]`` tensors."""
+
+    def __init__(self, width=5, order=1):
+        super().__init__()
+        from scipy.signal import savgol_coeffs
+        self.width = width
+        self.order = order
+        kernel = savgol_coeffs(width, order, deriv=order, delta=1.0).astype(np.float32)
+        self.kernel = nn.Parameter(torch.from_numpy((-1) ** (order % 2) * kernel), requires_grad=False)
+
+    def forward(self, x, seq_len=None):
+        C = x.shape[1]
+        return _ops.feature_shape(x, delta_kernel=self.kernel, seq_len=seq_len)[:, C:]
+
+
+class NormalizedLogMelExtractor(nn.Module):
+    """Stacked STFT ``[B, C, T, F, 2]`` (or complex64 ``[B, C, T, F]``) -> normalised log-mel features ``[B, C', M, T']`` with the
+    reference's constructor, return values, running statistics and training-mode augmentations.  ``forward`` is three launches (plus the
+    existing statistics reduction in training): ``logmel_front`` (scale, superpose, IPD, optionally warped log-mel, transpose),
+    ``feature_shape`` (time warp, blur, deltas; skipped when all are off) and ``feature_tail`` (normalise, clamp, IPD concat, mixup, noise,
+    masks)."""
+
+    def __init__(
+            self, sample_rate, stft_size, number_of_filters, *,
+            num_channels=1,
+            lowest_frequency=50, highest_frequency=None, htk_mel=True,
+            add_deltas=False, add_delta_deltas=False,
+            norm_statistics_axis='bt', norm_eps=1e-5, batch_norm=False,
+            clamp=6, ipd_pairs=(),
+            # augmentation
+            scale_sampling_fn=None,
+            superposition_prob=0.,
+            frequency_warping_fn=None, time_warping_fn=None,
+            blur_sigma=0, blur_kernel_size=5,
+            mixup_prob=0., mixup_alpha=1.,
+            max_noise_scale=0.,
+            n_time_masks=0, max_masked_time_steps=70, max_masked_time_rate=1.,
+            n_frequency_masks=0, max_masked_frequency_bands=20, max_masked_frequency_rate=1.,
+    ):
+        super().__init__()
+        if num_channels > _ops.MAX_C or number_of_filters > _ops.MAX_M or stft_size // 2 + 1 > _ops.MAX_F:
+            raise NotImplementedError(f'NormalizedLogMelExtractor covers num_channels <= {_ops.MAX_C}, number_of_filters <= {_ops.MAX_M} and '
+                                      f'stft_size <= {2 * _ops.MAX_F - 2}, got {num_channels}, {number_of_filters}, {stft_size}')
+        if blur_sigma > 0 and (blur_kernel_size % 2 == 0 or blur_kernel_size > _ops.MAX_K):
+            raise NotImplementedError(f'NormalizedLogMelExtractor covers odd blur_kernel_size <= {_ops.MAX_K}, got {blur_kernel_size}')
+        # the static filterbank, fbanks, inverse; the warping function stays here (MelTransform takes none)
+        self.mel_transform = MelTransform(sample_rate=sample_rate, stft_size=stft_size, number_of_filters=number_of_filters,
+                                          lowest_frequency=lowest_frequency, highest_frequency=highest_frequency, htk_mel=htk_mel, log=True)
+        self.frequency_warping_fn = frequency_warping_fn
+        self.deltas_extractor = DeltaExtractor(order=1) if add_deltas else None
+        self.delta_deltas_extractor = DeltaExtractor(order=2) if add_delta_deltas else None
+
+        assert all([len(pair) == 2 for pair in ipd_pairs]), ipd_pairs
+        assert all([c < num_channels for pair in ipd_pairs for c in pair]), ipd_pairs
+        self.ipd_pairs = list(zip(*ipd_pairs))
+        self.filter_max_indices = self.mel_transform.fbanks.argmax(0)
+        norm_cls = Normalization if batch_norm else InputNormalization
+        self.norm = norm_cls(
+            data_format='bcft',
+            shape=(None, (1 + add_deltas + add_delta_deltas) * num_channels, number_of_filters, None),
+            statistics_axis=norm_statistics_axis, shift=True, scale=True, eps=norm_eps, independent_axis=None, momentum=None,
+        )
+        self.clamp = clamp
+
+        scale_fn = None if scale_sampling_fn is None else Scale(scale_sampling_fn=scale_sampling_fn)
+        assert 0. <= superposition_prob <= 1., superposition_prob
+        self.superpose = Superpose(p=superposition_prob, scale_fn=scale_fn) if superposition_prob > 0. else None
+        self.scale = None if superposition_prob > 0. else scale_fn
+        self.time_warping = None if time_warping_fn is None else TimeWarping(warping_fn=time_warping_fn)
+        self.blur = None
+        if blur_sigma > 0:
+            self.blur = GaussianBlur2d(kernel_size=blur_kernel_size,
+                                       sigma_sampling_fn=TruncatedExponential(loc=.1, scale=blur_sigma, truncation=blur_kernel_size))
+        assert 0 <= mixup_prob <= 1, mixup_prob
+        self.mixup = Mixup(p=mixup_prob, alpha=mixup_alpha) if mixup_prob > 0 else None
+        self.time_masking = self.mel_masking = None
+        if n_time_masks > 0:
+            self.time_masking = Mask(axis=-1, n_masks=n_time_masks, max_masked_steps=max_masked_time_steps,
+                                     max_masked_rate=max_masked_time_rate)
+        if n_frequency_masks > 0:
+            self.mel_masking = Mask(axis=-2, n_masks=n_frequency_masks, max_masked_steps=max_masked_frequency_bands,
+                                    max_masked_rate=max_masked_frequency_rate)
+        self.noise = AdditiveNoise(max_noise_scale) if max_noise_scale > 0. else None
+
+    def warped_edges_hz(self, B):
+        """One call of ``frequency_warping_fn`` on the mel-scale edges ``[B, 1, 1, M + 2]`` -> filter edges in Hz ``[B, M + 2]`` (float32)."""
+        mt = self.mel_transform
+        nyquist = mt.sample_rate / 2
+        lo = 0. if mt.lowest_frequency is None else mt.lowest_frequency
+        hi = nyquist if mt.highest_frequency is None else mt.highest_frequency
+        lo, hi = (nyquist + lo if lo < 0 else lo), (nyquist + hi if hi < 0 else hi)
+        M = mt.number_of_filters
+        mel = np.linspace(_hz2mel(lo, mt.htk_mel), _hz2mel(hi, mt.htk_mel), M + 2)
+        edges = np.ascontiguousarray(np.broadcast_to(mel, (B, 1, 1, M + 2)))
+        warped = np.asarray(self.frequency_warping_fn(edges), dtype=np.float64)
+        assert warped.shape == edges.shape, (warped.shape, edges.shape)
+        hz = _mel2hz(warped, mt.htk_mel).reshape(B, M + 2).astype(np.float32)
+        assert (np.diff(hz, axis=-1) > 0).all(), 'the warped filter edges must increase strictly'
+        return hz
+
+    def _statistics(self, x, lengths):
+        """``(x, mean, rstd)``: the running statistics for the tail kernel (updated first in training), or - statistics that are not
+        shared over b and t, batch statistics of ``Normalization`` in training - ``x`` normalised by ``self.norm`` and no statistics."""
+        norm = self.norm
+        batch_statistics = not isinstance(norm, InputNormalization) and norm.training and not norm.frozen_stats
+        if not norm.track_running_stats or batch_statistics:
+            return norm(x, lengths), None, None
+        if isinstance(norm, InputNormalization) and norm.training:
+            norm.update_running_stats(x, lengths)
+        return x, norm.running_mean, torch.rsqrt(norm.running_var + norm.eps)      # eps enters twice, as in _running_norm
+
+    def forward(self, x, seq_len=None, targets=None):
+        _lib.require_gpu(x)
+        with torch.no_grad():
+            B, training = x.shape[0], self.training
+            gain = partner = partner_gain = lam = edges = None
+            if self.scale is not None and training:
+                gain = self.scale.draw(B)
+            if self.superpose is not None and training:
+                partner, lam, gain, partner_gain, seq_len = self.superpose.draw(B, seq_len)
+                targets = self.superpose.mix_targets(targets, lam, partner)
+            if self.frequency_warping_fn is not None and training:
+                edges = self.warped_edges_hz(B)
+            mt = self.mel_transform
+            x, cos, sin = _ops.logmel_front(
+                x, mt._bands, self.filter_max_indices.cpu().numpy(), list(zip(*self.ipd_pairs)), edges_hz=edges,
+                bin_hz=mt.sample_rate / mt.stft_size, gain=gain, partner=partner, partner_gain=partner_gain, lam=lam, eps=mt.eps)
+
+            time_indices = taps = None
+            if self.time_warping is not None and training:
+                time_indices, seq_len = self.time_warping.draw(seq_len)
+            if self.blur is not None and training:
+                taps = self.blur.draw(B)
+            x = _ops.feature_shape(
+                x, time_indices=time_indices, taps=taps, seq_len=seq_len,
+                delta_kernel=None if self.deltas_extractor is None else self.deltas_extractor.kernel,
+                delta_delta_kernel=None if self.delta_deltas_extractor is None else self.delta_deltas_extractor.kernel)
+
+            lengths = _ops.lengths_as_frames(seq_len)
+            x, mean, rstd = self._statistics(x, lengths)
+            tail = dict(mean=mean, rstd=rstd, clamp=self.clamp, ipd_cos=cos, ipd_sin=sin, seq_len=None if mean is None else lengths)
+            if self.mixup is not None and training:
+                tail['partner'], tail['lam'], seq_len = self.mixup.draw(B, seq_len)
+                targets = self.mixup.mix_targets(targets, tail['lam'], tail['partner'])
+            if self.noise is not None and training:
+                tail['noise_scale'] = self.noise.draw(B)
+                tail['noise'] = torch.randn((B, x.shape[1] + 2 * len(self.ipd_pairs and self.ipd_pairs[0]), *x.shape[2:]), device=x.device)
+            if self.time_masking is not None and training:
+                tail['time_masks'] = self.time_masking.draw(B, x.shape[-1], seq_len)
+            if self.mel_masking is not None and training:
+                tail['freq_masks'] = self.mel_masking.draw(B, x.shape[-2])
+            x = _ops.feature_tail(x, **tail)
+        if targets is None:
+            return x, seq_len
+        return x, seq_len, targets
+
+    def inverse(self, x):
+        return self.mel_transform.inverse(self.norm.inverse(x).transpose(-2, -1)).sqrt().unsqueeze(-1)
 
 
 #: STFT size -> (R1, R2) of its FFT plan (csrc/stft.hip, with_plan)

@@ -331,19 +331,23 @@ class Normalization(nn.Module):
 class InputNormalization(Normalization):
     """Always normalises with the running statistics when they are tracked (``:265-290``)."""
 
+    def update_running_stats(self, x, sequence_lengths=None):
+        """Fold the masked batch statistics of ``x`` into the running statistics (one ``ptmi_norm_reduce`` launch, no elementwise pass)."""
+        with torch.no_grad():
+            xc = _check_input(x)
+            geom, stat_shape, n_groups = _geometry(xc.shape, self.statistics_axis, None, self.batch_axis,
+                                                   self.sequence_axis)
+            stats = _reduce(0, xc, None, _lengths(sequence_lengths, xc.device), None, None, None, geom,
+                            self.shift, n_groups)
+            denom = torch.clamp(stats[:, 2], min=1)
+            mean = (stats[:, 0] / denom).to(torch.float32).reshape(stat_shape)
+            power = (stats[:, 1] / denom).to(torch.float32).reshape(stat_shape)
+            self._update_running_stats(mean, power, stats[:, 2].to(torch.float32).reshape(stat_shape))
+
     def forward(self, x, sequence_lengths=None):
         if self.track_running_stats:
             if self.training:
-                with torch.no_grad():
-                    xc = _check_input(x)
-                    geom, stat_shape, n_groups = _geometry(xc.shape, self.statistics_axis, None, self.batch_axis,
-                                                           self.sequence_axis)
-                    stats = _reduce(0, xc, None, _lengths(sequence_lengths, xc.device), None, None, None, geom,
-                                    self.shift, n_groups)
-                    denom = torch.clamp(stats[:, 2], min=1)
-                    mean = (stats[:, 0] / denom).to(torch.float32).reshape(stat_shape)
-                    power = (stats[:, 1] / denom).to(torch.float32).reshape(stat_shape)
-                    self._update_running_stats(mean, power, stats[:, 2].to(torch.float32).reshape(stat_shape))
+                self.update_running_stats(x, sequence_lengths)
             x = self._running_norm(x, sequence_lengths)
         else:
             x = super().forward(x, sequence_lengths)

@@ -44,3 +44,4 @@ from . import seq_pool  # noqa: F401
 from .seq_pool import reverse_sequence  # noqa: F401
 from . import je_conv  # noqa: F401
 from . import je_conv2d  # noqa: F401
+from . import je_features  # noqa: F401
