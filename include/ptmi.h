@@ -1263,6 +1263,34 @@ int ptmi_je_feature_tail(const float* x, int64_t B, int32_t C, int32_t M, int64_
                          const int32_t* freq_onset, const int32_t* freq_offset, int32_t n_freq_masks, const int32_t* seq_len, float* out,
                          ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The contrast of padertorch/contrib/mk/modules/contrastive.py:343-471 (CPC1d.contrast) and the cross-entropy, argmax and "> -inf" count
+ * of its review (csrc/cpc_contrast.hip).  fp32, nothing of size K is written, no atomics, nothing read on the host: capturable.
+ * z [b, d, t] and z_hat [b, S d, t] with time contiguous; geom (HOST) = b, d, t, z batch stride, z feature stride, z_hat batch stride,
+ * z_hat feature stride, S, steps[S].  mode: 0 'time', 1 'all', 2 'batch'.  Step s: T_s = t - |s| >= 1; query q reads z_hat_s at frame
+ * q + max(-s, 0); in modes 0 / 1 key index k reads z at frame (k + max(s, 0)) mod t, the target of query q is key q of its own entry, and
+ * keys of that entry with 0 < |k - q| <= dist - 1 are -inf; in mode 2 the b keys of time position tau are z at frame tau + max(s, 0),
+ * log_batch_mask [b, b] (or NULL) is added, and key j stays iff #{i : score_i >= score_j} >= keep or j is the target.
+ * Limits (PTMI_E_UNSUPPORTED beyond): d <= ptmi_cpc_max_features() (512), S <= ptmi_cpc_max_steps() (16), b t < 2^31, and
+ * b <= ptmi_cpc_max_batch() (64) in mode 2.
+ *
+ * ptmi_cpc_query_tile / _key_tile : queries a workgroup owns (64) / key indices of a streamed tile (32): what the tests put t around
+ * ptmi_cpc_forward  : stats [4][sum_s b T_s] = ce | hit (0 / 1) | finite (int32 bits) | lse, step after step, each [b, T_s]; logits (or
+ *   NULL): the masked scaled scores, step after step, each [b, K, T_s] with K = t, b t, b.
+ * ptmi_cpc_backward : from g and lse [sum_s b T_s]: dz_hat [b, S d, t] (trimmed frames zero) and dz [b, d, t], contiguous, written whole;
+ *   in modes 0 / 1 either may be NULL.
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_cpc_max_features(void);
+int32_t ptmi_cpc_max_batch(void);
+int32_t ptmi_cpc_max_steps(void);
+int32_t ptmi_cpc_query_tile(void);
+int32_t ptmi_cpc_key_tile(void);
+int ptmi_cpc_forward(const float* z_hat, const float* z, const int64_t* geom, int32_t mode, float temperature, int32_t dist,
+                     const float* log_batch_mask, int32_t keep, float* stats, float* logits, ptmi_stream_t stream);
+int ptmi_cpc_backward(const float* z_hat, const float* z, const int64_t* geom, int32_t mode, float temperature, int32_t dist,
+                      const float* log_batch_mask, int32_t keep, const float* lse, const float* g, float* dz_hat, float* dz,
+                      ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

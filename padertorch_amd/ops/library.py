@@ -53,6 +53,7 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
                                                    ptmi_je_conv_transpose_*, ptmi_je_unpool_*   (ConvTranspose*, CNNTranspose*, Unpool*)
     torch.ops.ptmi.aam_prepare / aam_forward / aam_backward, batch_norm_rows_forward / _backward
                                                    ptmi_aam_*, ptmi_batch_norm_rows_*   (contrib/tcl/speaker_embeddings/loss.py, dvectors.py)
+    torch.ops.ptmi.cpc_forward / cpc_backward      ptmi_cpc_*   (contrib/mk/modules/contrastive.py: CPC1d.contrast + review's cross-entropy)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -2202,3 +2203,49 @@ def batch_norm_rows_backward(gy, x, stats, training):
     _lib.call('ptmi_batch_norm_rows_backward', gy.data_ptr(), x.data_ptr(), stats.data_ptr(), dx.data_ptr(), B, E, int(training),
               _lib.stream(x.device), timer='batch_norm_rows_backward')
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ CPC contrast (csrc/cpc_contrast.hip)
+def _cpc_geom(z_hat, z, steps, mode):
+    assert z.dim() == 3 and z_hat.dim() == 3 and z.dtype == z_hat.dtype == torch.float32, (z.shape, z_hat.shape, z.dtype, z_hat.dtype)
+    assert z.stride(2) == 1 and z_hat.stride(2) == 1, (z.stride(), z_hat.stride())
+    b, d, t = z.shape
+    S = len(steps)
+    assert z_hat.shape == (b, S * d, t), (z_hat.shape, z.shape, S)
+    lib = _lib.load()
+    if d > lib.ptmi_cpc_max_features() or S > lib.ptmi_cpc_max_steps() or (mode == 2 and b > lib.ptmi_cpc_max_batch()):
+        raise NotImplementedError(f'cpc_contrast: d = {d}, b = {b}, {S} steps; the kernels take d <= {lib.ptmi_cpc_max_features()} '
+                                  f'(ptmi_cpc_max_features), {lib.ptmi_cpc_max_steps()} steps and, with negatives_mode="batch", '
+                                  f'b <= {lib.ptmi_cpc_max_batch()} (ptmi_cpc_max_batch)')
+    rows = [b * (t - abs(s)) for s in steps]
+    K = (t, b * t, b)[mode]
+    return _lib.int64s(b, d, t, z.stride(0), z.stride(1), z_hat.stride(0), z_hat.stride(1), S, *steps), rows, K
+
+
+@_register('cpc_forward(Tensor z_hat, Tensor z, int[] steps, int mode, float temperature, int dist, Tensor? log_batch_mask, int keep, '
+           'bool dense) -> (Tensor, Tensor?)')
+def cpc_forward(z_hat, z, steps, mode, temperature, dist, log_batch_mask, keep, dense):
+    """``(stats [4, sum_s b T_s] = ce | hit | finite (int32 bits) | lse, dense logits (flat, step after step [b, K, T_s]) or None)``
+    (``ptmi_cpc_forward``; contrastive.py:343-471, :515-540)."""
+    geom, rows, K = _cpc_geom(z_hat, z, steps, mode)
+    _f32c(log_batch_mask)
+    stats = torch.empty((4, sum(rows)), dtype=torch.float32, device=z.device)
+    logits = torch.empty(sum(rows) * K, dtype=torch.float32, device=z.device) if dense else None
+    _lib.call('ptmi_cpc_forward', z_hat.data_ptr(), z.data_ptr(), geom, mode, temperature, dist, _lib.ptr(log_batch_mask), keep,
+              stats.data_ptr(), _lib.ptr(logits), _lib.stream(z.device), timer='cpc_forward')
+    return stats, logits
+
+
+@_register('cpc_backward(Tensor z_hat, Tensor z, int[] steps, int mode, float temperature, int dist, Tensor? log_batch_mask, int keep, '
+           'Tensor lse, Tensor g) -> (Tensor, Tensor)')
+def cpc_backward(z_hat, z, steps, mode, temperature, dist, log_batch_mask, keep, lse, g):
+    """``(dz_hat [b, S d, t], dz [b, d, t])`` from the gradient ``g`` of ``ce`` and the saved ``lse`` (both ``[sum_s b T_s]``): the scores
+    are recomputed, every element is written by one thread (``ptmi_cpc_backward``)."""
+    geom, rows, _ = _cpc_geom(z_hat, z, steps, mode)
+    _f32c(log_batch_mask, lse, g)
+    assert lse.shape == g.shape == (sum(rows),), (lse.shape, g.shape, rows)
+    dz_hat = torch.empty(z_hat.shape, dtype=torch.float32, device=z.device)
+    dz = torch.empty(z.shape, dtype=torch.float32, device=z.device)
+    _lib.call('ptmi_cpc_backward', z_hat.data_ptr(), z.data_ptr(), geom, mode, temperature, dist, _lib.ptr(log_batch_mask), keep,
+              lse.data_ptr(), g.data_ptr(), dz_hat.data_ptr(), dz.data_ptr(), _lib.stream(z.device), timer='cpc_backward')
+    return dz_hat, dz
