@@ -1039,6 +1039,55 @@ int ptmi_transformer_norm_residual_backward(const float* gy, const float* v, con
                                             double* workspace, ptmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * padertorch/contrib/mk/modules/transformer.py: attention with an additive float score bias (csrc/attention.hip, the BIAS = true
+ * instantiations), the per-head query / key preparation and the row norms with the residual add (csrc/mk_attention.hip).  fp32, no
+ * atomics, every reduction in one fixed order, no host reads.
+ *
+ * ptmi_attn_bias_forward / _backward : ptmi_attn_forward / _backward (operands, strides, lengths and causal as above, no byte mask)
+ *                       with s = scale q.k + kbias[b kbias_stride + j] - slope[h] |j - i| (:691-724).  kbias: fp32 DEVICE log-mask,
+ *                       one row of Tk per example, NULL: absent; a key with kbias = -inf is invisible like a masked one.  slope:
+ *                       fp32 DEVICE vector [H], NULL: absent.  Neither has a gradient.  Key tiles behind `lengths` are skipped.
+ *                       lse is [2, B, H, Tq] here: the row maximum and the log of the row sum, kept apart because the linear bias
+ *                       moves the scores hundreds away from zero, where their sum in one float would cost the backward 3e-5.
+ *                       The backward's delta is sum_j p_ij dp_ij / sum_j p_ij from the recomputed probabilities (one more pass
+ *                       over K and V) instead of rowsum(dout out), so the backward takes no `out` (strides: q k v dout dq dk dv).
+ * ptmi_mk_qk_prep_forward : q [B, Tq, H, dh] and k [B, Tk, H, dh] (contiguous, the projections' output; Tk = 0: q alone) in ONE launch:
+ *                       RMS norm over dh with the weights wq / wk [dh] (both NULL: skipped; eps as given), then the rotary rotation
+ *                       of the pairs (2i, 2i+1) by (t + 1) theta[2i] (theta [dh] DEVICE, the reference's buffer; NULL: skipped),
+ *                       then x / max(||x||, 1e-12) when l2.  Writes q_out / k_out in the operands' layout and, per row [B, T, H],
+ *                       the inverse RMS (q_irms / k_irms) and the inverse L2 norm (q_il2 / k_il2) of the stages in use.  dh even,
+ *                       2 <= dh <= ptmi_attn_max_head().
+ * ptmi_mk_qk_prep_backward : dq / dk from gq / gk, the forward's inputs and saved scalars in one launch; d wq / d wk [dh] as ordered
+ *                       fp64 slab sums (workspace: ptmi_mk_qk_prep_workspace_elems doubles; needed with wq only).
+ * ptmi_mk_row_norm_forward : rows of [rows, N]; s = a + res (res NULL: s = a, nothing written to `s`), y = norm(s).  kind 0: layer
+ *                       norm (stats [rows, 2] = mean, rstd), 1: RMS norm (stats = 0, rstd; no bias), 2: dynamic tanh tanh(alpha s) w
+ *                       + b (alpha: one DEVICE float; no stats).  weight / bias [N], NULL: 1 / 0.
+ * ptmi_mk_row_norm_backward : ds = gs + the adjoint of y in gy (gs NULL: absent) in one launch; dparams [2 N] = d weight | d bias as
+ *                       ordered fp64 column sums (NULL: skipped), dalpha [1] for kind 2; workspace: ptmi_mk_row_norm_workspace_elems
+ *                       doubles.
+ * ---------------------------------------------------------------------------------------------------------- */
+int ptmi_attn_bias_forward(const float* q, const float* k, const float* v, const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk,
+                           int32_t dh, int32_t dv, float scale, const void* lengths, int32_t lengths_int64, int32_t causal,
+                           const float* kbias, int64_t kbias_stride, const float* slope, float* out, float* lse, ptmi_stream_t stream);
+int ptmi_attn_bias_backward(const float* q, const float* k, const float* v, const float* dout, const float* lse, const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk, int32_t dh, int32_t dv, float scale,
+                            const void* lengths, int32_t lengths_int64, int32_t causal, const float* kbias, int64_t kbias_stride,
+                            const float* slope, float* delta, float* dq, float* dk, float* dv_out, ptmi_stream_t stream);
+int ptmi_mk_qk_prep_forward(const float* q, const float* k, const float* wq, const float* wk, const float* theta, int64_t B, int64_t Tq,
+                            int64_t Tk, int32_t H, int32_t dh, float eps, int32_t l2, float* q_out, float* k_out, float* q_irms,
+                            float* k_irms, float* q_il2, float* k_il2, ptmi_stream_t stream);
+int64_t ptmi_mk_qk_prep_workspace_elems(int64_t B, int64_t Tq, int64_t Tk, int32_t H, int32_t dh);
+int ptmi_mk_qk_prep_backward(const float* gq, const float* gk, const float* q, const float* k, const float* wq, const float* wk,
+                             const float* theta, const float* q_irms, const float* k_irms, const float* q_il2, const float* k_il2,
+                             int64_t B, int64_t Tq, int64_t Tk, int32_t H, int32_t dh, int32_t l2, float* dq, float* dk, float* dwq,
+                             float* dwk, double* workspace, ptmi_stream_t stream);
+int ptmi_mk_row_norm_forward(int32_t kind, const float* a, const float* res, const float* weight, const float* bias, const float* alpha,
+                             int64_t rows, int32_t N, float eps, float* s, float* y, float* stats, ptmi_stream_t stream);
+int64_t ptmi_mk_row_norm_workspace_elems(int64_t rows, int32_t N);
+int ptmi_mk_row_norm_backward(int32_t kind, const float* gy, const float* gs, const float* s, const float* stats, const float* weight,
+                              const float* alpha, int64_t rows, int32_t N, float* ds, float* dparams, float* dalpha, double* workspace,
+                              ptmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The GRU recurrence (csrc/gru.hip) and the sequence glue (csrc/seq_pool.hip) of padertorch/contrib/je/modules/rnn.py and reduce.py.
  * fp32, every launcher capturable, lengths and tables are device data, sums fp64 in a fixed order, no atomics.
  *

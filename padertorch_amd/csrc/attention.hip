@@ -19,6 +19,11 @@
 // Masks, as transformer.py:29-36 combines them (y + log(mask > 0)): element (i, j) is visible iff j < min(Tk, lengths[b]) (lengths
 // given), j <= i + Tk - Tq (causal: get_causal_mask, :259-260) and mask[b, h, i, j] != 0 (bytes, any strides).  A row without a visible
 // key is NaN in out, lse and the weights (softmax of all -inf), written as such; it contributes nothing to the gradients.
+//
+// Additive score bias (BIAS = true instantiations of the forward, dq and dkv kernels: ptmi_attn_bias_*; padertorch/contrib/mk/modules/
+// transformer.py:691-724): s = scale q.k + kbias[b, j] - slope[h] |j - i|, kbias an fp32 log-mask row per example, slope one value per
+// head; either may be absent.  A key with kbias = -inf is invisible like a masked one, so the online softmax never forms -inf - (-inf).
+// Neither term has a gradient.  BIAS = false compiles the score step without any of it.
 #include <math.h>
 
 #include "reduce.h"
@@ -48,6 +53,9 @@ struct AtArgs {
     int B, H, dh, dvn;
     float scale;
     AtMask M;
+    const float* kbias;            // BIAS only: [B, Tk] with row stride kbs, or null
+    const float* slope;            // BIAS only: [H], or null
+    long long kbs;
 };
 
 __device__ __forceinline__ long long at_klen(const AtMask& M, long long b) {
@@ -64,6 +72,30 @@ __device__ __forceinline__ bool at_visible(const AtMask& M, long long klen, long
     if (M.causal && j > i + M.Tk - M.Tq) return false;
     if (M.mask && !M.mask[b * M.ms[0] + h * M.ms[1] + i * M.ms[2] + j * M.ms[3]]) return false;
     return true;
+}
+
+// BIAS: is key j of example b visible (kbias != -inf), and the score with the additive terms.
+__device__ __forceinline__ bool at_bias_visible(const AtArgs& A, long long b, long long j) {
+    return !A.kbias || A.kbias[b * A.kbs + j] != -INFINITY;
+}
+
+template <bool BIAS>
+__device__ __forceinline__ float at_score(const AtArgs& A, float dot, long long b, int h, long long i, long long j) {
+    float s = dot * A.scale;
+    if constexpr (BIAS) {
+        if (A.kbias) s += A.kbias[b * A.kbs + j];
+        if (A.slope) s -= A.slope[h] * (float)(j > i ? j - i : i - j);
+    }
+    return s;
+}
+
+// log p of a score in the backward kernels.  BIAS: the linear bias puts scores - and with them the row maximum m - hundreds away from
+// zero, where one fp32 step is 3e-5: m + log l rounded to one float would scale a whole row of recomputed probabilities by that much.
+// So that path keeps (m, log l) apart; s - m is a difference of neighbours, and the probabilities are as exact as the forward's.
+template <bool BIAS>
+__device__ __forceinline__ float at_log_prob(float s, float lse, float logl) {
+    if constexpr (BIAS) return (s - lse) - logl;
+    return s - lse;
 }
 
 // One past the last key any query of rows [i0, i1) can see / the first query that can see a key >= j0.
@@ -145,7 +177,7 @@ __device__ __forceinline__ float at_row_sum(float v) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int NDB>
+template <int NDB, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_forward_kernel(const AtArgs A) {
     constexpr int LD = NDB * 16 + 4;
     __shared__ float Ks[kAtBN * LD], Vs[kAtBN * LD], Ps[4][16 * kAtPLD];
@@ -182,7 +214,9 @@ __global__ __launch_bounds__(256) void attn_forward_kernel(const AtArgs A) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 const long long j = t * kAtBN + nb * 16 + (lane & 15);
-                sv[nb] = at_visible(A.M, klen, b, h, i, j) ? s[nb][r] * A.scale : -INFINITY;
+                bool vis = at_visible(A.M, klen, b, h, i, j);
+                if constexpr (BIAS) vis = vis && at_bias_visible(A, b, j);
+                sv[nb] = vis ? at_score<BIAS>(A, s[nb][r], b, h, i, j) : -INFINITY;
             }
             const float mnew = fmaxf(m[r], at_row_max(fmaxf(sv[0], sv[1])));
             float alpha = 1.f, p0 = 0.f, p1 = 0.f;
@@ -212,7 +246,15 @@ __global__ __launch_bounds__(256) void attn_forward_kernel(const AtArgs A) {
             const int c = db * 16 + (lane & 15);
             if (c < A.dvn) orow[c] = dead ? NAN : o[db][r] / l[r];
         }
-        if ((lane & 15) == 0) A.lse_out[((long long)b * A.H + h) * Tq + i] = dead ? NAN : m[r] + logf(l[r]);
+        if ((lane & 15) == 0) {
+            const long long row = ((long long)b * A.H + h) * Tq + i;
+            if constexpr (BIAS) {                           // two planes, (m, log l): see at_log_prob
+                A.lse_out[row] = dead ? NAN : m[r];
+                A.lse_out[(long long)A.B * A.H * Tq + row] = dead ? NAN : logf(l[r]);
+            } else {
+                A.lse_out[row] = dead ? NAN : m[r] + logf(l[r]);
+            }
+        }
     }
 }
 
@@ -290,7 +332,69 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AtArgs A, float* 
     delta[idx] = s;
 }
 
+// The BIAS path's delta: sum_j p_ij dp_ij / sum_j p_ij with p and dp = dO V^T formed exactly as attn_dq_kernel and attn_dkv_kernel
+// form them (same operands, same k order), instead of dout . out.  The two are equal on paper; in fp32 `out` carries the rounding of
+// the forward's whole accumulation, which dout . out puts into every dp_ij - delta_i of the row at once: an error along the row's mean
+// key that the softmax adjoint of the reference does not have (measured on a two-layer encoder with diffuse attention: the query
+// gradient 2.6 times less accurate than torch's fp32, 1.2 times with this).  Dividing by the row's own sum of p makes sum_j dS_ij = 0
+// hold to rounding whatever the rounding of (m, log l).  Owns queries, streams K and V like attn_dq_kernel; no LDS image of P.
 template <int NDB>
+__global__ __launch_bounds__(256) void attn_delta_bias_kernel(const AtArgs A, float* __restrict__ delta) {
+    constexpr int LD = NDB * 16 + 4;
+    __shared__ float Ks[kAtBN * LD], Vs[kAtBN * LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = blockIdx.y;
+    const long long b = blockIdx.z, tile0 = (long long)blockIdx.x * kAtBM, q0 = tile0 + wave * 16;
+    const long long Tq = A.M.Tq, Tk = A.M.Tk;
+    const long long klen = at_klen(A.M, b);
+    const long long kend = at_key_end(A.M, klen, tile0 + kAtBM < Tq ? tile0 + kAtBM : Tq);
+    const long long ntiles = (kend + kAtBN - 1) / kAtBN;
+    const float* __restrict__ kb = A.k + b * A.ks[0] + h * A.ks[1];
+    const float* __restrict__ vb = A.v + b * A.vs[0] + h * A.vs[1];
+    float qa[NDB * 4], ga[NDB * 4];
+    at_load_rows<NDB>(qa, A.q + b * A.qs[0] + h * A.qs[1], A.qs[2], q0, Tq, A.dh, lane);
+    at_load_rows<NDB>(ga, A.dout + b * A.gs[0] + h * A.gs[1], A.gs[2], q0, Tq, A.dvn, lane);
+    float lse[4], logl[4], d[4], z[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long long i = q0 + (lane >> 4) * 4 + r;
+        const long long row = ((long long)b * A.H + h) * Tq + i;
+        lse[r] = i < Tq ? A.lse[row] : 0.f;
+        logl[r] = i < Tq ? A.lse[(long long)A.B * A.H * Tq + row] : 0.f;
+        d[r] = z[r] = 0.f;
+    }
+    for (long long t = 0; t < ntiles; ++t) {
+        __syncthreads();
+        at_stage<NDB>(Ks, kb, A.ks[2], t * kAtBN, Tk, A.dh);
+        at_stage<NDB>(Vs, vb, A.vs[2], t * kAtBN, Tk, A.dvn);
+        __syncthreads();
+        float pd[4] = {0.f, 0.f, 0.f, 0.f}, ps[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const at_f32x4 s = at_dot<NDB>(qa, Ks, nb, lane);
+            const at_f32x4 dp = at_dot<NDB>(ga, Vs, nb, lane);
+            const long long j = t * kAtBN + nb * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long i = q0 + (lane >> 4) * 4 + r;
+                if (at_visible(A.M, klen, b, h, i, j) && !isnan(lse[r]) && at_bias_visible(A, b, j)) {
+                    const float p = expf(at_log_prob<true>(at_score<true>(A, s[r], b, h, i, j), lse[r], logl[r]));
+                    pd[r] += p * dp[r];
+                    ps[r] += p;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[r] += at_row_sum(pd[r]), z[r] += at_row_sum(ps[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long long i = q0 + (lane >> 4) * 4 + r;
+        if (i < Tq && (lane & 15) == 0) delta[((long long)b * A.H + h) * Tq + i] = z[r] > 0.f ? d[r] / z[r] : 0.f;
+    }
+}
+
+template <int NDB, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_dq_kernel(const AtArgs A) {
     constexpr int LD = NDB * 16 + 4;
     __shared__ float Ks[kAtBN * LD], Vs[kAtBN * LD], Ps[4][16 * kAtPLD];
@@ -306,13 +410,15 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AtArgs A) {
     float qa[NDB * 4], ga[NDB * 4];
     at_load_rows<NDB>(qa, A.q + b * A.qs[0] + h * A.qs[1], A.qs[2], q0, Tq, A.dh, lane);
     at_load_rows<NDB>(ga, A.dout + b * A.gs[0] + h * A.gs[1], A.gs[2], q0, Tq, A.dvn, lane);
-    float lse[4], delta[4];
+    float lse[4], delta[4], logl[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const long long i = q0 + (lane >> 4) * 4 + r;
         const long long row = ((long long)b * A.H + h) * Tq + i;
         lse[r] = i < Tq ? A.lse[row] : 0.f;
         delta[r] = i < Tq ? A.delta[row] : 0.f;
+        logl[r] = 0.f;
+        if constexpr (BIAS) logl[r] = i < Tq ? A.lse[(long long)A.B * A.H * Tq + row] : 0.f;
     }
     at_f32x4 dq[NDB];
 #pragma unroll
@@ -332,7 +438,9 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AtArgs A) {
             for (int r = 0; r < 4; ++r) {
                 const long long i = q0 + (lane >> 4) * 4 + r;
                 float ds = 0.f;
-                if (at_visible(A.M, klen, b, h, i, j) && !isnan(lse[r])) ds = expf(s[r] * A.scale - lse[r]) * (dp[r] - delta[r]) * A.scale;
+                bool vis = at_visible(A.M, klen, b, h, i, j) && !isnan(lse[r]);
+                if constexpr (BIAS) vis = vis && at_bias_visible(A, b, j);
+                if (vis) ds = expf(at_log_prob<BIAS>(at_score<BIAS>(A, s[r], b, h, i, j), lse[r], logl[r])) * (dp[r] - delta[r]) * A.scale;
                 Pw[((lane >> 4) * 4 + r) * kAtPLD + nb * 16 + (lane & 15)] = ds;
             }
         }
@@ -352,10 +460,10 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AtArgs A) {
     }
 }
 
-template <int NDB>
+template <int NDB, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_dkv_kernel(const AtArgs A) {
     constexpr int LD = NDB * 16 + 4;
-    __shared__ float Qs[kAtBN * LD], Gs[kAtBN * LD], Ps[4][2][16 * kAtPLD], lse_s[kAtBN], delta_s[kAtBN];
+    __shared__ float Qs[kAtBN * LD], Gs[kAtBN * LD], Ps[4][2][16 * kAtPLD], lse_s[kAtBN], delta_s[kAtBN], logl_s[BIAS ? kAtBN : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.y;
     const long long b = blockIdx.z, tile0 = (long long)blockIdx.x * kAtBM, k0 = tile0 + wave * 16;
@@ -382,6 +490,7 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AtArgs A) {
             const long long row = ((long long)b * A.H + h) * Tq + i;
             lse_s[threadIdx.x] = i < Tq ? A.lse[row] : 0.f;
             delta_s[threadIdx.x] = i < Tq ? A.delta[row] : 0.f;
+            if constexpr (BIAS) logl_s[threadIdx.x] = i < Tq ? A.lse[(long long)A.B * A.H * Tq + row] : 0.f;
         }
         __syncthreads();
 #pragma unroll
@@ -391,12 +500,16 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AtArgs A) {
             const int qi = nb * 16 + (lane & 15);
             const long long i = t * kAtBN + qi;
             const float lse = lse_s[qi], delta = delta_s[qi];
+            float logl = 0.f;
+            if constexpr (BIAS) logl = logl_s[qi];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const long long j = k0 + (lane >> 4) * 4 + r;
                 float p = 0.f, ds = 0.f;
-                if (at_visible(A.M, klen, b, h, i, j) && !isnan(lse)) {          // (a row without a visible key has lse = delta = NaN)
-                    p = expf(s[r] * A.scale - lse);
+                bool vis = at_visible(A.M, klen, b, h, i, j) && !isnan(lse);          // (a row without a visible key has lse = delta = NaN)
+                if constexpr (BIAS) vis = vis && at_bias_visible(A, b, j);
+                if (vis) {
+                    p = expf(at_log_prob<BIAS>(at_score<BIAS>(A, s[r], b, h, i, j), lse, logl));
                     ds = p * (dp[r] - delta) * A.scale;
                 }
                 Pp[((lane >> 4) * 4 + r) * kAtPLD + qi] = p;
@@ -572,6 +685,16 @@ static int at_ndb(int d) { return d <= 16 ? 1 : (d <= 32 ? 2 : (d <= 64 ? 4 : 8)
         }                                                                                   \
     } while (0)
 
+#define PTMI_AT_LAUNCH_BIAS(kernel, ndb, grid, st, ...)                                           \
+    do {                                                                                          \
+        switch (ndb) {                                                                            \
+            case 1: hipLaunchKernelGGL((kernel<1, true>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
+            case 2: hipLaunchKernelGGL((kernel<2, true>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
+            case 4: hipLaunchKernelGGL((kernel<4, true>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
+            default: hipLaunchKernelGGL((kernel<8, true>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
+        }                                                                                         \
+    } while (0)
+
 static int at_shape(int32_t B, int32_t H, int64_t Tq, int64_t Tk, int32_t dh, int32_t dv) {
     PTMI_RETURN_IF(B < 1 || H < 1 || Tq < 1 || Tk < 1 || dh < 1 || dv < 1, PTMI_E_INVALID);
     PTMI_RETURN_IF(dh > kAtMaxHead || dv > kAtMaxHead || B > 65535 || H > 65535 || Tq > (1LL << 36) || Tk > (1LL << 36), PTMI_E_UNSUPPORTED);
@@ -646,6 +769,49 @@ int ptmi_attn_backward(const float* q, const float* k, const float* v, const flo
     rc = launch_status();
     PTMI_RETURN_IF(rc != PTMI_OK, rc);
     PTMI_AT_LAUNCH(attn_dq_kernel, ndb, dim3((unsigned)((Tq + kAtBM - 1) / kAtBM), (unsigned)H, (unsigned)B), st, A);
+    return launch_status();
+}
+
+int ptmi_attn_bias_forward(const float* q, const float* k, const float* v, const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk,
+                           int32_t dh, int32_t dv, float scale, const void* lengths, int32_t lengths_int64, int32_t causal,
+                           const float* kbias, int64_t kbias_stride, const float* slope, float* out, float* lse, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!q || !k || !v || !strides || !out || !lse, PTMI_E_INVALID);
+    int rc = at_shape(B, H, Tq, Tk, dh, dv);
+    PTMI_RETURN_IF(rc != PTMI_OK, rc);
+    AtArgs A = {};
+    A.q = q, A.k = k, A.v = v, A.out = out, A.lse_out = lse, A.B = B, A.H = H, A.dh = dh, A.dvn = dv, A.scale = scale;
+    A.kbias = kbias, A.kbs = kbias_stride, A.slope = slope;
+    at_strides(A.qs, strides), at_strides(A.ks, strides + 3), at_strides(A.vs, strides + 6), at_strides(A.os, strides + 9);
+    rc = at_mask(A.M, Tq, Tk, lengths, lengths_int64, causal, nullptr, nullptr);
+    PTMI_RETURN_IF(rc != PTMI_OK, rc);
+    const dim3 grid((unsigned)((Tq + kAtBM - 1) / kAtBM), (unsigned)H, (unsigned)B);
+    PTMI_AT_LAUNCH_BIAS(attn_forward_kernel, at_ndb(dh > dv ? dh : dv), grid, static_cast<hipStream_t>(stream), A);
+    return launch_status();
+}
+
+int ptmi_attn_bias_backward(const float* q, const float* k, const float* v, const float* dout, const float* lse, const int64_t* strides, int32_t B, int32_t H, int64_t Tq, int64_t Tk, int32_t dh, int32_t dv, float scale,
+                            const void* lengths, int32_t lengths_int64, int32_t causal, const float* kbias, int64_t kbias_stride,
+                            const float* slope, float* delta, float* dq, float* dk, float* dv_out, ptmi_stream_t stream) {
+    PTMI_RETURN_IF(!q || !k || !v || !dout || !lse || !strides || !delta || !dq || !dk || !dv_out, PTMI_E_INVALID);
+    int rc = at_shape(B, H, Tq, Tk, dh, dv);
+    PTMI_RETURN_IF(rc != PTMI_OK, rc);
+    AtArgs A = {};
+    A.q = q, A.k = k, A.v = v, A.dout = dout, A.lse = lse, A.delta = delta, A.dq = dq, A.dk = dk, A.dv = dv_out;
+    A.B = B, A.H = H, A.dh = dh, A.dvn = dv, A.scale = scale;
+    A.kbias = kbias, A.kbs = kbias_stride, A.slope = slope;
+    at_strides(A.qs, strides), at_strides(A.ks, strides + 3), at_strides(A.vs, strides + 6), at_strides(A.gs, strides + 9);
+    at_strides(A.dqs, strides + 12), at_strides(A.dks, strides + 15), at_strides(A.dvs, strides + 18);
+    rc = at_mask(A.M, Tq, Tk, lengths, lengths_int64, causal, nullptr, nullptr);
+    PTMI_RETURN_IF(rc != PTMI_OK, rc);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int ndb = at_ndb(dh > dv ? dh : dv);
+    PTMI_AT_LAUNCH(attn_delta_bias_kernel, ndb, dim3((unsigned)((Tq + kAtBM - 1) / kAtBM), (unsigned)H, (unsigned)B), st, A, delta);
+    rc = launch_status();
+    PTMI_RETURN_IF(rc != PTMI_OK, rc);
+    PTMI_AT_LAUNCH_BIAS(attn_dkv_kernel, ndb, dim3((unsigned)((Tk + kAtBM - 1) / kAtBM), (unsigned)H, (unsigned)B), st, A);
+    rc = launch_status();
+    PTMI_RETURN_IF(rc != PTMI_OK, rc);
+    PTMI_AT_LAUNCH_BIAS(attn_dq_kernel, ndb, dim3((unsigned)((Tq + kAtBM - 1) / kAtBM), (unsigned)H, (unsigned)B), st, A);
     return launch_status();
 }
 

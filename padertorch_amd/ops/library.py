@@ -54,6 +54,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.aam_prepare / aam_forward / aam_backward, batch_norm_rows_forward / _backward
                                                    ptmi_aam_*, ptmi_batch_norm_rows_*   (contrib/tcl/speaker_embeddings/loss.py, dvectors.py)
     torch.ops.ptmi.cpc_forward / cpc_backward      ptmi_cpc_*   (contrib/mk/modules/contrastive.py: CPC1d.contrast + review's cross-entropy)
+    torch.ops.ptmi.attn_bias_forward / _backward, mk_qk_prep_forward / _backward, mk_row_norm_forward / _backward
+                                                   ptmi_attn_bias_*, ptmi_mk_*   (contrib/mk/modules/transformer.py: MultiheadAttention, norms)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -1723,6 +1725,141 @@ def transformer_norm_residual_backward(gy, v, stats, gamma, lengths, want_params
               is64, B, T, N, dv.data_ptr(), _lib.ptr(dparams), _lib.ptr(ws), _lib.stream(v.device),
               timer='transformer_norm_residual_backward')
     return dv, dparams
+
+
+# ------------------------------------------------------------------------------------------------ contrib/mk transformer (csrc/mk_attention.hip)
+def _attn_bias(key_bias, slopes, B, H, Tk):
+    if key_bias is not None:
+        assert key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (B, Tk) and (key_bias.stride(1) == 1 or Tk == 1), \
+            (key_bias.dtype, key_bias.shape, key_bias.stride())
+    assert slopes is None or (slopes.dtype == torch.float32 and tuple(slopes.shape) == (H,) and slopes.is_contiguous()), slopes
+    return _lib.ptr(key_bias), (key_bias.stride(0) if key_bias is not None else 0), _lib.ptr(slopes)
+
+
+@_register('attn_bias_forward(Tensor q, Tensor k, Tensor v, Tensor? lengths, bool causal, Tensor? key_bias, Tensor? slopes, float scale) '
+           '-> (Tensor, Tensor)')
+def attn_bias_forward(q, k, v, lengths, causal, key_bias, slopes, scale):
+    """``attn_forward`` with the scores ``scale q.k + key_bias[b, j] - slopes[h] |j - i|`` (``ptmi_attn_bias_forward``; mk transformer.py:691-724)."""
+    B, H, Tq, dh = _attn_operand(q).shape
+    Tk, dv = _attn_operand(k).shape[2], _attn_operand(v).shape[3]
+    assert tuple(k.shape) == (B, H, Tk, dh) and tuple(v.shape) == (B, H, Tk, dv), (q.shape, k.shape, v.shape)
+    lengths, is64 = _lengths(lengths, B)
+    kb, kbs, sl = _attn_bias(key_bias, slopes, B, H, Tk)
+    out = _attn_heads_last(B, H, Tq, dv, q.device)
+    lse = torch.empty((2, B, H, Tq), dtype=torch.float32, device=q.device)      # (row maximum, log of the row sum): kept apart
+    strides = _lib.int64s(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3])
+    _lib.call('ptmi_attn_bias_forward', q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, B, H, Tq, Tk, dh, dv, scale, _lib.ptr(lengths), is64,
+              int(causal), kb, kbs, sl, out.data_ptr(), lse.data_ptr(), _lib.stream(q.device), timer='attn_bias_forward')
+    return out, lse
+
+
+@_register('attn_bias_backward(Tensor q, Tensor k, Tensor v, Tensor dout, Tensor lse, Tensor? lengths, bool causal, '
+           'Tensor? key_bias, Tensor? slopes, float scale) -> (Tensor, Tensor, Tensor)')
+def attn_bias_backward(q, k, v, dout, lse, lengths, causal, key_bias, slopes, scale):
+    """``(dq, dk, dv)`` as ``[B, H, T, d]`` views of contiguous ``[B, T, H, d]`` buffers (``ptmi_attn_bias_backward``); the forward's ``out`` is
+    not an operand: this path forms its row term from the recomputed probabilities."""
+    B, H, Tq, dh = _attn_operand(q).shape
+    Tk, dv = _attn_operand(k).shape[2], _attn_operand(v).shape[3]
+    assert tuple(_attn_operand(dout).shape) == (B, H, Tq, dv), dout.shape
+    assert tuple(lse.shape) == (2, B, H, Tq) and lse.is_contiguous(), lse.shape
+    lengths, is64 = _lengths(lengths, B)
+    kb, kbs, sl = _attn_bias(key_bias, slopes, B, H, Tk)
+    dev = q.device
+    dq, dk, dvv = _attn_heads_last(B, H, Tq, dh, dev), _attn_heads_last(B, H, Tk, dh, dev), _attn_heads_last(B, H, Tk, dv, dev)
+    delta = torch.empty((B, H, Tq), dtype=torch.float32, device=dev)
+    strides = _lib.int64s(*[s for t in (q, k, v, dout, dq, dk, dvv) for s in t.stride()[:3]])
+    _lib.call('ptmi_attn_bias_backward', q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), lse.data_ptr(), strides,
+              B, H, Tq, Tk, dh, dv, scale, _lib.ptr(lengths), is64, int(causal), kb, kbs, sl, delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+              dvv.data_ptr(), _lib.stream(dev), timer='attn_bias_backward')
+    return dq, dk, dvv
+
+
+def _qk_dims(q, k):
+    """``q [B, Tq, H, dh]``, ``k [B, Tk, H, dh]`` or None: contiguous fp32, 8-byte aligned rows (the kernel reads float2 pairs)."""
+    _f32c(q, k)
+    B, Tq, H, dh = q.shape
+    Tk = 0 if k is None else k.shape[1]
+    assert dh % 2 == 0 and q.data_ptr() % 8 == 0 and (k is None or (k.data_ptr() % 8 == 0 and (k.shape[0], *k.shape[2:]) == (B, H, dh))), \
+        (q.shape, None if k is None else k.shape)
+    return B, Tq, Tk, H, dh
+
+
+@_register('mk_qk_prep_forward(Tensor q, Tensor? k, Tensor? wq, Tensor? wk, Tensor? theta, bool l2, float eps) '
+           '-> (Tensor, Tensor?, Tensor?, Tensor?, Tensor?, Tensor?)')
+def mk_qk_prep_forward(q, k, wq, wk, theta, l2, eps):
+    """``(q', k', q_irms, k_irms, q_il2, k_il2)`` of ``q [B, Tq, H, dh]``, ``k [B, Tk, H, dh]`` (or None): RMS norm over ``dh`` with ``wq`` /
+    ``wk``, rotary rotation with ``theta [dh]``, L2 normalisation, each optional, one launch (``ptmi_mk_qk_prep_forward``)."""
+    B, Tq, Tk, H, dh = _qk_dims(q, k)
+    _f32c(wq, wk, theta)
+    assert (wq is None or wq.numel() == dh) and (wk is None or wk.numel() == dh) and (theta is None or theta.numel() == dh)
+    assert k is None or (wq is None) == (wk is None)
+
+    def rows(t, on):
+        return torch.empty(t.shape[:3], dtype=torch.float32, device=q.device) if t is not None and on else None
+    qo, ko = torch.empty_like(q), (None if k is None else torch.empty_like(k))
+    q_irms, k_irms, q_il2, k_il2 = rows(q, wq is not None), rows(k, wk is not None), rows(q, l2), rows(k, l2)
+    _lib.call('ptmi_mk_qk_prep_forward', q.data_ptr(), _lib.ptr(k), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(theta), B, Tq, Tk, H, dh, eps, int(l2),
+              qo.data_ptr(), _lib.ptr(ko), _lib.ptr(q_irms), _lib.ptr(k_irms), _lib.ptr(q_il2), _lib.ptr(k_il2), _lib.stream(q.device),
+              timer='mk_qk_prep_forward')
+    return qo, ko, q_irms, k_irms, q_il2, k_il2
+
+
+@_register('mk_qk_prep_backward(Tensor gq, Tensor? gk, Tensor q, Tensor? k, Tensor? wq, Tensor? wk, Tensor? theta, Tensor? q_irms, '
+           'Tensor? k_irms, Tensor? q_il2, Tensor? k_il2) -> (Tensor, Tensor?, Tensor?, Tensor?)')
+def mk_qk_prep_backward(gq, gk, q, k, wq, wk, theta, q_irms, k_irms, q_il2, k_il2):
+    """``(dq, dk, d wq, d wk)`` in one launch + the ordered fp64 sums of the weight gradients (``ptmi_mk_qk_prep_backward``)."""
+    lib = _lib.load()
+    B, Tq, Tk, H, dh = _qk_dims(q, k)
+    _qk_dims(gq, gk)
+    _f32c(wq, wk, theta, q_irms, k_irms, q_il2, k_il2)
+    assert gq.shape == q.shape and (k is None or gk.shape == k.shape)
+    dev = q.device
+    dq, dk = torch.empty_like(q), (None if k is None else torch.empty_like(k))
+    dwq = None if wq is None else torch.empty(dh, dtype=torch.float32, device=dev)
+    dwk = None if wk is None else torch.empty(dh, dtype=torch.float32, device=dev)
+    ws = None if wq is None else _doubles(lib.ptmi_mk_qk_prep_workspace_elems(B, Tq, Tk, H, dh), dev)
+    _lib.call('ptmi_mk_qk_prep_backward', gq.data_ptr(), _lib.ptr(gk), q.data_ptr(), _lib.ptr(k), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(theta),
+              _lib.ptr(q_irms), _lib.ptr(k_irms), _lib.ptr(q_il2), _lib.ptr(k_il2), B, Tq, Tk, H, dh, int(q_il2 is not None), dq.data_ptr(),
+              _lib.ptr(dk), _lib.ptr(dwq), _lib.ptr(dwk), _lib.ptr(ws), _lib.stream(dev), timer='mk_qk_prep_backward')
+    return dq, dk, dwq, dwk
+
+
+@_register('mk_row_norm_forward(int kind, Tensor a, Tensor? res, Tensor? weight, Tensor? bias, Tensor? alpha, float eps) '
+           '-> (Tensor?, Tensor, Tensor?)')
+def mk_row_norm_forward(kind, a, res, weight, bias, alpha, eps):
+    """``(s, y, stats)`` of ``a, res [..., N]``: ``s = a + res`` (None without ``res``), ``y`` the layer norm (``kind`` 0), RMS norm
+    (1) or dynamic tanh (2) of ``s``; ``stats [rows, 2]`` for kinds 0 and 1 (``ptmi_mk_row_norm_forward``)."""
+    _f32c(a, res, weight, bias, alpha)
+    N = a.shape[-1]
+    rows = a.numel() // N
+    assert (res is None or res.shape == a.shape) and all(p is None or p.numel() == N for p in (weight, bias)), (a.shape, N)
+    assert (alpha is not None and alpha.numel() == 1) if kind == 2 else alpha is None
+    s = None if res is None else torch.empty_like(a)
+    y = torch.empty_like(a)
+    stats = None if kind == 2 else torch.empty((rows, 2), dtype=torch.float32, device=a.device)
+    _lib.call('ptmi_mk_row_norm_forward', kind, a.data_ptr(), _lib.ptr(res), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(alpha), rows, N, eps,
+              _lib.ptr(s), y.data_ptr(), _lib.ptr(stats), _lib.stream(a.device), timer='mk_row_norm_forward')
+    return s, y, stats
+
+
+@_register('mk_row_norm_backward(int kind, Tensor gy, Tensor? gs, Tensor s, Tensor? stats, Tensor? weight, Tensor? alpha, bool want_params) '
+           '-> (Tensor, Tensor?, Tensor?)')
+def mk_row_norm_backward(kind, gy, gs, s, stats, weight, alpha, want_params):
+    """``(ds, dparams [2 N] = d weight | d bias or None, d alpha [1] or None)``: ``ds = gs +`` the norm's adjoint in ``gy``
+    (``ptmi_mk_row_norm_backward``)."""
+    lib = _lib.load()
+    _f32c(gy, gs, s, stats, weight, alpha)
+    N = s.shape[-1]
+    rows = s.numel() // N
+    assert gy.shape == s.shape and (gs is None or gs.shape == s.shape), (gy.shape, s.shape)
+    dev = s.device
+    ds = torch.empty_like(s)
+    dparams = torch.empty(2 * N, dtype=torch.float32, device=dev) if want_params else None
+    dalpha = torch.empty(1, dtype=torch.float32, device=dev) if kind == 2 else None
+    ws = _doubles(lib.ptmi_mk_row_norm_workspace_elems(rows, N), dev)
+    _lib.call('ptmi_mk_row_norm_backward', kind, gy.data_ptr(), _lib.ptr(gs), s.data_ptr(), _lib.ptr(stats), _lib.ptr(weight), _lib.ptr(alpha),
+              rows, N, ds.data_ptr(), _lib.ptr(dparams), _lib.ptr(dalpha), ws.data_ptr(), _lib.stream(dev), timer='mk_row_norm_backward')
+    return ds, dparams, dalpha
 
 
 # ------------------------------------------------------------------------------------------------ GRU + sequence glue (csrc/gru.hip, csrc/seq_pool.hip)
