@@ -1340,6 +1340,32 @@ int ptmi_cpc_backward(const float* z_hat, const float* z, const int64_t* geom, i
                       const float* log_batch_mask, int32_t keep, const float* lse, const float* g, float* dz_hat, float* dz,
                       ptmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The pairwise Gaussian KL divergence of padertorch/ops/losses/kl_divergence.py:17-60 (csrc/gauss_kl.hip).  fp32, contiguous: posteriors
+ * mu, sigma [B, D]; components m [K, D] with scale = scale_tril T [K, D, D] (full = 1: only the lower triangle is read) or the diagonal
+ * s [K, D] (full = 0).  Nothing of size B K D is written, no atomics, nothing read on the host: capturable.  Dp = D rounded up to 16.
+ * Limits (PTMI_E_UNSUPPORTED beyond): D <= ptmi_gkl_max_features() (64), B and K <= 2^25.
+ *
+ * ptmi_gkl_row_tile / _split_rows : rows a row-owning workgroup owns (64) / rows of one (component, split) workgroup of the backward
+ *   (1024): S = ceil(B / split_rows) partials per component.
+ * ptmi_gkl_workspace_elems : floats of the backward's workspace, S K (full Dp Dp + 3 Dp); 0 beyond the limits.
+ * ptmi_gkl_prepare  : L [K, Dp, Dp] = T^-1 padded with an identity (full only, else NULL), c [K, Dp] = column sums of L o L
+ *   (1 / s^2; 0 in the padding of the diagonal case), logdet [K] = sum_d log T_dd (log s_d).
+ * ptmi_gkl_forward  : kl [B, K] = logdet_k - sum_d log sigma_bd + (sum_d c_kd sigma_bd^2 + |L_k (m_k - mu_b)|^2 - D) / 2.
+ * ptmi_gkl_backward : from G = d loss / d kl [B, K]: dmu, dsigma [B, D], dm [K, D], dscale like scale (full: zeros above the diagonal),
+ *   each written whole; ws: ptmi_gkl_workspace_elems floats.
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t ptmi_gkl_max_features(void);
+int32_t ptmi_gkl_row_tile(void);
+int32_t ptmi_gkl_split_rows(void);
+int64_t ptmi_gkl_workspace_elems(int64_t B, int64_t K, int32_t D, int32_t full);
+int ptmi_gkl_prepare(const float* scale, int32_t full, int64_t K, int32_t D, float* L, float* c, float* logdet, ptmi_stream_t stream);
+int ptmi_gkl_forward(const float* mu, const float* sigma, const float* m, const float* L, const float* c, const float* logdet, int32_t full,
+                     int64_t B, int64_t K, int32_t D, float* kl, ptmi_stream_t stream);
+int ptmi_gkl_backward(const float* mu, const float* sigma, const float* m, const float* scale, const float* L, const float* c,
+                      const float* G, int32_t full, int64_t B, int64_t K, int32_t D, float* ws, float* dmu, float* dsigma, float* dm,
+                      float* dscale, ptmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Data parallelism: the gradient exchange of padertorch/train/trainer.py:396-442 (parallel_apply over the devices of ONE
  * process, gradients of the replicas summed at :426-428 - accumulated, NOT averaged) as one process per GPU and one RCCL

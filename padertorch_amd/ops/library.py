@@ -56,6 +56,8 @@ with CPU tensors fails in the dispatcher (``NotImplementedError: ... 'CPU' backe
     torch.ops.ptmi.cpc_forward / cpc_backward      ptmi_cpc_*   (contrib/mk/modules/contrastive.py: CPC1d.contrast + review's cross-entropy)
     torch.ops.ptmi.attn_bias_forward / _backward, mk_qk_prep_forward / _backward, mk_row_norm_forward / _backward
                                                    ptmi_attn_bias_*, ptmi_mk_*   (contrib/mk/modules/transformer.py: MultiheadAttention, norms)
+    torch.ops.ptmi.gkl_prepare / gkl_forward / gkl_backward
+                                                   ptmi_gkl_*   (ops/losses/kl_divergence.py: gaussian_kl_divergence)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -2386,3 +2388,59 @@ def cpc_backward(z_hat, z, steps, mode, temperature, dist, log_batch_mask, keep,
     _lib.call('ptmi_cpc_backward', z_hat.data_ptr(), z.data_ptr(), geom, mode, temperature, dist, _lib.ptr(log_batch_mask), keep,
               lse.data_ptr(), g.data_ptr(), dz_hat.data_ptr(), dz.data_ptr(), _lib.stream(z.device), timer='cpc_backward')
     return dz_hat, dz
+
+
+# ------------------------------------------------------------------------------------------------ pairwise Gaussian KL (csrc/gauss_kl.hip)
+def _gkl_dims(mu, sigma, m, scale):
+    _f32c(mu, sigma, m, scale)
+    (B, D), K = mu.shape, m.shape[0]
+    full = scale.dim() == 3
+    assert sigma.shape == (B, D) and m.shape == (K, D) and scale.shape == ((K, D, D) if full else (K, D)), \
+        (mu.shape, sigma.shape, m.shape, scale.shape)
+    if D > _lib.load().ptmi_gkl_max_features():
+        raise NotImplementedError(f'gaussian_kl_divergence: {D} features; the kernels take up to {_lib.load().ptmi_gkl_max_features()} '
+                                  f'(ptmi_gkl_max_features)')
+    return B, K, D, int(full)
+
+
+@_register('gkl_prepare(Tensor scale, int D) -> (Tensor?, Tensor, Tensor)')
+def gkl_prepare(scale, D):
+    """``scale_tril [K, D, D]`` -> ``(L = T^-1 [K, Dp, Dp] identity-padded, c [K, Dp] = column sums of L o L, logdet [K])``; the diagonal
+    ``s [K, D]`` -> ``(None, 1 / s^2, sum log s)`` (``ptmi_gkl_prepare``; kl_divergence.py:39-44)."""
+    _f32c(scale)
+    if D > _lib.load().ptmi_gkl_max_features():
+        raise NotImplementedError(f'gaussian_kl_divergence: {D} features; the kernels take up to {_lib.load().ptmi_gkl_max_features()} '
+                                  f'(ptmi_gkl_max_features)')
+    K, full, dp = scale.shape[0], int(scale.dim() == 3), -(-D // 16) * 16
+    L = torch.empty((K, dp, dp), dtype=torch.float32, device=scale.device) if full else None
+    c = torch.empty((K, dp), dtype=torch.float32, device=scale.device)
+    logdet = torch.empty(K, dtype=torch.float32, device=scale.device)
+    _lib.call('ptmi_gkl_prepare', scale.data_ptr(), full, K, D, _lib.ptr(L), c.data_ptr(), logdet.data_ptr(), _lib.stream(scale.device),
+              timer='gkl_prepare')
+    return L, c, logdet
+
+
+@_register('gkl_forward(Tensor mu, Tensor sigma, Tensor m, Tensor scale, Tensor? L, Tensor c, Tensor logdet) -> Tensor')
+def gkl_forward(mu, sigma, m, scale, L, c, logdet):
+    """``kl [B, K]`` from the prepared components: the row-owning kernel (``ptmi_gkl_forward``; kl_divergence.py:39-56)."""
+    B, K, D, full = _gkl_dims(mu, sigma, m, scale)
+    _f32c(L, c, logdet)
+    kl = torch.empty((B, K), dtype=torch.float32, device=mu.device)
+    _lib.call('ptmi_gkl_forward', mu.data_ptr(), sigma.data_ptr(), m.data_ptr(), _lib.ptr(L), c.data_ptr(), logdet.data_ptr(), full, B, K, D,
+              kl.data_ptr(), _lib.stream(mu.device), timer='gkl_forward')
+    return kl
+
+
+@_register('gkl_backward(Tensor mu, Tensor sigma, Tensor m, Tensor scale, Tensor? L, Tensor c, Tensor g) -> (Tensor, Tensor, Tensor, Tensor)')
+def gkl_backward(mu, sigma, m, scale, L, c, g):
+    """``(dmu, dsigma [B, D], dm [K, D], dscale like scale)`` from ``g = d loss / d kl [B, K]``: the row-owning kernel, the
+    (component, row split) kernel with its partials ``[S, K, ...]`` and the component finish (``ptmi_gkl_backward``); no atomics."""
+    B, K, D, full = _gkl_dims(mu, sigma, m, scale)
+    _f32c(L, c, g)
+    assert g.shape == (B, K), (g.shape, B, K)
+    ws = torch.empty(int(_lib.load().ptmi_gkl_workspace_elems(B, K, D, full)), dtype=torch.float32, device=mu.device)
+    dmu, dsigma, dm, dscale = torch.empty_like(mu), torch.empty_like(sigma), torch.empty_like(m), torch.empty_like(scale)
+    _lib.call('ptmi_gkl_backward', mu.data_ptr(), sigma.data_ptr(), m.data_ptr(), scale.data_ptr(), _lib.ptr(L), c.data_ptr(), g.data_ptr(),
+              full, B, K, D, ws.data_ptr(), dmu.data_ptr(), dsigma.data_ptr(), dm.data_ptr(), dscale.data_ptr(), _lib.stream(mu.device),
+              timer='gkl_backward')
+    return dmu, dsigma, dm, dscale

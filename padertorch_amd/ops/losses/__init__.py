@@ -1,6 +1,8 @@
 from . import regression
 from . import source_separation
+from . import kl_divergence
 from .regression import *  # noqa: F401,F403
+from .kl_divergence import *  # noqa: F401,F403
 from .source_separation import *  # noqa: F401,F403
 from .source_separation import pit_mse_ips_losses, dc_loss_batched  # noqa: F401
 from ..orpit import one_and_rest_permutation_invariant_loss  # noqa: F401,E402
